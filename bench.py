@@ -9,6 +9,10 @@ A "step" = one pass of the whole hot path over one resident batch of B synthetic
   one local-BA Jacobian/JtJ build (10 keyframes x 2000 points) per frame.
 Inputs are resident in HBM before the timed region; results stay in HBM.  value = frames of all ranks /
 max-over-ranks time.  See DESIGN.md (measurement) for the byte accounting behind `roofline`.
+
+A plain run sets up, warms up, times --steps steps and prints the line; --dump-outputs DIR also writes what the last step computed.
+--full adds, after the timed region, the per-stage times, `roofline` / `roofline_valu`, `cpu_baseline` and the `offline`, `stream` and
+`surface` blocks.
 """
 import argparse
 import json
@@ -29,18 +33,33 @@ if ROOT not in sys.path:
 W, H, LEVELS = 640, 480, 3
 
 
-def build_inputs(batch, rank):
+_TEX = None
+
+
+def _render_frame(job):
     from ygz_slam_amd import synth
-    tex, m = synth.make_texture(1 + rank, W, H)
+    i, pose, seed = job
+    im, d = synth.render(_TEX[0], _TEX[1], pose, W, H, 1.0, seed)
+    return synth.gray_to_bgr(im, i), d
+
+
+def build_inputs(batch, rank, workers=1):
+    """the seeded synthetic batch of one rank; workers > 1 renders it with a fork-based pool (same frames) -- only BEFORE the GPU
+    runtime is touched"""
+    global _TEX
+    from ygz_slam_amd import synth
+    _TEX = synth.make_texture(1 + rank, W, H)
     poses = synth.trajectory(batch, 11 + rank, 0.25)
     poses[0] = [0, 0, 0, 1, 0, 0, 0]
-    frames, depths = [], []
-    for i in range(batch):
-        im, d = synth.render(tex, m, poses[i], W, H, 1.0, 1000 * (rank + 1) + i)
-        frames.append(synth.gray_to_bgr(im, i))
-        depths.append(d)
+    jobs = [(i, poses[i], 1000 * (rank + 1) + i) for i in range(batch)]
+    if workers > 1 and batch > 1:
+        import multiprocessing as mp
+        with mp.get_context("fork").Pool(min(workers, batch)) as pool:
+            rendered = pool.map(_render_frame, jobs, chunksize=max(1, batch // (4 * workers)))
+    else:
+        rendered = [_render_frame(j) for j in jobs]
     ba = synth.ba_window(10, 2000, seed=7)
-    return np.stack(frames), poses, np.stack(depths), ba
+    return np.stack([f for f, _ in rendered]), poses, np.stack([d for _, d in rendered]), ba
 
 
 class Pipeline:
@@ -121,7 +140,7 @@ class Pipeline:
         c.build_pyramid(0, self.B, from_bgr=True)
         c.detect(0, self.B)
         self.kps = [c.get_keypoints(s) for s in range(self.B)]
-        self.kp_depth = [np.array([self.depths[s][int(p[1]), int(p[0])] for p in k["px"]]) for s, k in enumerate(self.kps)]
+        self.kp_depth = [self.depths[s][k["px"][:, 1].astype(np.int64), k["px"][:, 0].astype(np.int64)] for s, k in enumerate(self.kps)]
         for s in range(self.B):                               # Feature::_depth / _mappoint of the (deterministic) keypoints
             c.set_keypoint_depths(s, self.kp_depth[s], np.ones(len(self.kp_depth[s]), np.uint8))
         self.q = list(range(self.B))                          # current frame of pair i
@@ -171,6 +190,43 @@ class Pipeline:
         t("sparse_align", c.track_sparse_align)
         t("ba_linearize", lambda: c.ba_linearize_resident(0, self.B))
         return out
+
+
+def dump_outputs(pipe, out_dir, n_pairs=16, n_ba=4, seed=2024):
+    """What the last step left on the device, read back as a caller of the step would: the keypoint counts of the whole batch; keypoints,
+    cross-checked matches, LK tracks, direct projections and sparse-alignment poses of a fixed, seeded sample of n_pairs frame pairs;
+    the BA linearisations of the first n_ba of them.  Variable-length rows are concatenated over the sampled pairs
+    (the *_len arrays hold the rows per pair).  One DIR/<name>.npy per array, float32 / float64, 64 MB at most."""
+    c = pipe.ctx
+    c.synchronize()
+    pairs = np.sort(np.random.default_rng(seed).choice(pipe.B, min(n_pairs, pipe.B), replace=False))
+    out = {"pairs": pairs.astype(np.float64), "keypoint_count": c.get_keypoint_counts(0, pipe.B).astype(np.float64)}
+    rows = {}
+
+    def put(name, v, dtype):
+        rows.setdefault(name, []).append(np.asarray(v).astype(dtype))
+
+    for i in (int(p) for p in pairs):
+        kp = c.get_keypoints(i)
+        put("kp_px", kp["px"], np.float64); put("kp_level", kp["level"], np.float64); put("kp_score", kp["score"], np.float32)
+        put("kp_angle", kp["angle"], np.float32); put("kp_desc", kp["desc"], np.float32); put("kp_len", [len(kp["level"])], np.float64)
+        idx, dist = c.get_matches(i)
+        put("match_idx", idx, np.float64); put("match_dist", dist, np.float64); put("match_len", [len(idx)], np.float64)
+        pts, st, err = c.track_get_klt(i)
+        put("klt_pts", pts, np.float32); put("klt_status", st, np.float32); put("klt_err", err, np.float32); put("klt_len", [len(st)], np.float64)
+        ok, px, lvl = c.track_get_direct(i)
+        put("direct_ok", ok, np.float32); put("direct_px", px, np.float64); put("direct_level", lvl, np.float64); put("direct_len", [len(ok)], np.float64)
+        n_meas, T, iters = c.track_get_pose(i)
+        put("align_T", [T], np.float64); put("align_meas_iters", [[n_meas] + list(iters)], np.float64)
+    for i in (int(p) for p in pairs[:n_ba]):
+        for k, v in c.ba_download(i, *pipe.ba_dims[i]).items():
+            put("ba_" + k, [v], np.float64)
+    out.update({k: np.concatenate(v) for k, v in rows.items()})
+    total = sum(v.nbytes for v in out.values())
+    assert total <= 64 << 20, "outputs of %d bytes: over 64 MB" % total
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
 
 
 def cpu_baseline(pipe, budget_s=12.0):
@@ -831,7 +887,17 @@ def main():
     ap.add_argument("--upload", default="bgr", choices=["bgr", "gray"], help="stream mode: what crosses PCIe per frame (3 or 1 byte per pixel)")
     ap.add_argument("--size", default=None, choices=["vga", "720p"],
                     help="vga = BASELINE.json's metric (640x480, the default); 720p = its configs[4] frame size (1280x720, --batch 128 per GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="step / stream mode: also measure what the headline figure does not need, after the timed region: per-stage times, the "
+                         "rooflines (with the probed kernel's launch times inside the timed steps), the CPU baseline and, in the default mode, "
+                         "the `offline`, `stream` and `surface` blocks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="step / stream mode: after the timed steps, write what the last step computed for a fixed, seeded sample of the batch's "
+                         "frames (keypoints, matches, LK tracks, direct projections, sparse-alignment poses, BA linearisations) "
+                         "as DIR/<name>.npy, float32 / float64")
     a = ap.parse_args()
+    if a.dump_outputs is not None and a.mode not in ("step", "stream"):
+        ap.error("--dump-outputs: step and stream modes only")
     global W, H
     if a.size is None:
         a.size = "720p" if a.mode == "offline" else "vga"
@@ -846,10 +912,11 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
-    # extra blocks of the default line (measured after the timed region, so that the driver's record carries them): BASELINE configs[4]
+    # extra blocks of the --full line (measured after the timed region, so that the driver's record carries them): BASELINE configs[4]
     # (the offline run, sharded over the same ranks) and, at one GPU, the transfer-inclusive stream mode
-    extras = a.mode == "step" and a.size == "vga" and not a.no_extras and a.profile_part is None and os.environ.get("YGZ_BENCH_EXTRAS", "1") != "0"
+    extras = a.full and a.mode == "step" and a.size == "vga" and not a.no_extras and a.profile_part is None and os.environ.get("YGZ_BENCH_EXTRAS", "1") != "0"
     R_off = offline_render(a.offline_frames, rank, world) if extras else None      # host cores, before the GPU runtime is touched
+    inputs = build_inputs(a.batch, rank, workers=max(1, min(len(os.sched_getaffinity(0)), 16) // world))    # likewise; at most 16 host cores in all
     import torch
     dist = None
     if world > 1:
@@ -877,7 +944,7 @@ def main():
     n_buf = 2 if (a.double_buffer or a.mode == "stream") else 1
     streams = [torch.cuda.Stream() for _ in range(n_buf)]
     torch.cuda.set_stream(streams[0])
-    pipes = [Pipeline(a.batch, local_rank, rank, stream=streams[b].cuda_stream, overlap=not a.no_overlap) for b in range(n_buf)]
+    pipes = [Pipeline(a.batch, local_rank, rank, stream=streams[b].cuda_stream, overlap=not a.no_overlap, inputs=inputs) for b in range(n_buf)]
     for q in pipes:
         q.setup()
         if a.mode == "stream":
@@ -910,8 +977,9 @@ def main():
         one_step()
     barrier()
     probe_kernel = a.probe
-    pipe.ctx.probe_begin(probe_kernel, 8 * (a.steps + 1) * 8)
-    barrier()
+    if a.full:                                                # HIP events around the probed kernel's launches, for the roofline
+        pipe.ctx.probe_begin(probe_kernel, 8 * (a.steps + 1) * 8)
+        barrier()
     # per-step device times (median / p10 / p90): an event on the pipeline's stream at the start of every step and one
     # behind the last (after the side streams have joined); step k = the interval between events k and k + 1.  One resident batch only: with two,
     # consecutive steps run on different streams.
@@ -930,11 +998,13 @@ def main():
             if q.in_flight:
                 q.consume(); q.in_flight = False
     dt = time.perf_counter() - t0
-    probe_ms, probe_n = pipe.ctx.probe_end()
+    probe_ms, probe_n = pipe.ctx.probe_end() if a.full else (0.0, 0)
     if dist is not None:
         tt = torch.tensor([dt], dtype=torch.float64, device="cuda")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    if a.dump_outputs is not None and rank == 0:               # before anything else runs on the device
+        dump_outputs(pipes[(step_no[0] - 1) % n_buf], a.dump_outputs)
 
     # who took part: one line per rank (device index, UUID, name) gathered to rank 0, so that a record of an N > 1 run shows N ranks on N
     # distinct devices and the backend the collectives ran on
@@ -946,53 +1016,7 @@ def main():
         dist.all_gather_object(ranks, me)
     if rank == 0:
         frames = a.batch * a.steps * world
-        stages = pipe.stage_times() if a.profile_part is None else {}
         n_kp = float(np.mean([len(k["level"]) for k in pipe.kps]))
-        # dominant kernel (see profiles/): algorithmic bytes per launch (DESIGN.md "Measurement") / HIP-event duration
-        n_px = sum((W >> L) * (H >> L) for L in range(LEVELS))
-        alg = {"k_klt": a.batch * n_kp * 5 * 2 * 23 * 23,                  # 23x23 B window, 2 images, 5 levels per point
-               "k_sparse_align": a.batch * n_kp * 3 * 80.0,               # ~80 B per feature-level
-               "k_fast_select": a.batch * (n_px + 8 * 3000 + 100 * 3000),
-               "k_find_direct_projection": a.batch * n_kp * 220.0,
-               "k_hamming_nn": a.batch * 72000.0 * 0.5}.get(probe_kernel, 0.0)
-        avg_s = (probe_ms / max(probe_n, 1)) * 1e-3
-        ach = alg / avg_s / 1e9 if avg_s > 0 else 0.0
-        # HBM bytes per launch from the PMC passes of this same command (tools/collect_profiles.sh -> profiles/traffic.json)
-        traffic, traffic_stale = None, None
-        tpath = os.path.join(os.path.dirname(os.path.abspath(__file__)), "profiles", "traffic.json")
-        if os.path.exists(tpath):
-            tj = json.load(open(tpath))
-            # the 21x21 LK launches are k_klt3 (three points per wavefront) under the library's "k_klt" timer id
-            tname = {"k_klt": "k_klt3"}.get(probe_kernel, probe_kernel)
-            tname = tname if tname in tj.get("kernels", {}) else probe_kernel
-            if tj.get("batch") == a.batch and tname in tj.get("kernels", {}):
-                traffic = tj["kernels"][tname]["hbm_bytes"]
-            from ygz_slam_amd.srchash import kernel_source_hash
-            traffic_stale = tj.get("kernel_source_hash") != kernel_source_hash()     # the counters were collected on other kernel sources
-        # The limiter of the dominant kernel is VALU issue, not HBM (its counter traffic is BELOW the algorithmic bytes: the window re-reads
-        # hit L1 / L2).  `roofline` keeps the HBM view the contract asks for (achieved / peak / frac in GB/s, traffic from the PMC passes) and
-        # names the real bound; `roofline_valu` prices the same launches against the measured VALU issue ceiling of the kernel's opcode mix.
-        roofline = {"bound": "valu", "achieved": ach, "peak": 8000.0, "unit": "GB/s", "frac": ach / 8000.0, "traffic": traffic,
-                    "kernel": {"k_klt": "k_klt3"}.get(probe_kernel, probe_kernel), "launches": probe_n, "avg_launch_us": avg_s * 1e6, "algorithmic_bytes_per_launch": alg,
-                    "traffic_collected_on_other_kernel_sources": traffic_stale,
-                    "note": "frac is the HBM fraction (algorithmic bytes / launch time / 8 TB/s); the kernel is VALU-issue bound, see roofline_valu"}
-        roofline_valu = valu_roofline(pipe, a, probe_kernel, avg_s, n_kp)
-        if a.profile_part is None and a.mode == "step" and isinstance(roofline_valu, dict):
-            try:
-                roofline_valu["step_kernels"] = kernel_table(pipe, a, n_kp)
-                roofline_valu["step_kernels_note"] = ("every kernel of the step: HIP events around each of its launches in two extra steps (ms_in_step: beside the side "
-                                                      "streams) and with its stage issued alone (ms_alone); hbm_frac = algorithmic bytes (SURVEY 8d) / time / 8 TB/s; "
-                                                      "counter bytes from profiles/traffic.json, VALU instructions from profiles/valu_counts.json (guide peak: 1.2 G wave64 "
-                                                      "instructions / s / SIMD).  The events serialise nothing but add ~2 us per launch")
-            except Exception as e:
-                roofline_valu["step_kernels"] = {"error": repr(e)}
-        alone = roofline_valu.get("kernels", {}).get(roofline["kernel"], {}).get("alone") if isinstance(roofline_valu, dict) else None
-        if alone:                                             # the same kernel with the GPU to itself (in the step its launch shares the CUs with three side streams)
-            roofline["avg_launch_us_alone"] = alone["avg_launch_us"]
-            roofline["achieved_alone"] = alg / (alone["avg_launch_us"] * 1e-6) / 1e9
-            roofline["frac_alone"] = roofline["achieved_alone"] / 8000.0
-            roofline["how"] = ("frac: HIP events around every launch of the kernel inside the timed steps (profiles/r05_step_kernel_stats.md holds the same launches); "
-                               "frac_alone: 3 runs of the LK stage by itself after the timed region (profiles/r05_alone_kernel_stats.md)")
         step_ms = None
         if step_ev is not None:
             per = np.array([step_ev[k].elapsed_time(step_ev[k + 1]) for k in range(a.steps)])
@@ -1011,8 +1035,55 @@ def main():
                           "frames_per_gpu_per_step": a.batch, "resident_batches_per_gpu": n_buf, "keypoints_per_frame": n_kp,
                           "parallelism": "frames sharded x%d (replicas: no data-path collective in this mode; see the `offline` block)" % world},
                "ranks": {"world": world, "backend": (dist.get_backend() if dist is not None else None), "distinct_devices": len({r["uuid"] or r["local_rank"] for r in ranks}),
-                         "per_rank": ranks},
-               "stage_ms_per_batch": stages, "roofline": roofline, "roofline_valu": roofline_valu}
+                         "per_rank": ranks}}
+        if a.full:                                        # figures that take runs of their own, after the timed region
+            stages = pipe.stage_times() if a.profile_part is None else {}
+            # dominant kernel (see profiles/): algorithmic bytes per launch (DESIGN.md "Measurement") / HIP-event duration
+            n_px = sum((W >> L) * (H >> L) for L in range(LEVELS))
+            alg = {"k_klt": a.batch * n_kp * 5 * 2 * 23 * 23,                  # 23x23 B window, 2 images, 5 levels per point
+                   "k_sparse_align": a.batch * n_kp * 3 * 80.0,               # ~80 B per feature-level
+                   "k_fast_select": a.batch * (n_px + 8 * 3000 + 100 * 3000),
+                   "k_find_direct_projection": a.batch * n_kp * 220.0,
+                   "k_hamming_nn": a.batch * 72000.0 * 0.5}.get(probe_kernel, 0.0)
+            avg_s = (probe_ms / max(probe_n, 1)) * 1e-3
+            ach = alg / avg_s / 1e9 if avg_s > 0 else 0.0
+            # HBM bytes per launch from the PMC passes of this same command (tools/collect_profiles.sh -> profiles/traffic.json)
+            traffic, traffic_stale = None, None
+            tpath = os.path.join(os.path.dirname(os.path.abspath(__file__)), "profiles", "traffic.json")
+            if os.path.exists(tpath):
+                tj = json.load(open(tpath))
+                # the 21x21 LK launches are k_klt3 (three points per wavefront) under the library's "k_klt" timer id
+                tname = {"k_klt": "k_klt3"}.get(probe_kernel, probe_kernel)
+                tname = tname if tname in tj.get("kernels", {}) else probe_kernel
+                if tj.get("batch") == a.batch and tname in tj.get("kernels", {}):
+                    traffic = tj["kernels"][tname]["hbm_bytes"]
+                from ygz_slam_amd.srchash import kernel_source_hash
+                traffic_stale = tj.get("kernel_source_hash") != kernel_source_hash()     # the counters were collected on other kernel sources
+            # The limiter of the dominant kernel is VALU issue, not HBM (its counter traffic is BELOW the algorithmic bytes: the window re-reads
+            # hit L1 / L2).  `roofline` keeps the HBM view the contract asks for (achieved / peak / frac in GB/s, traffic from the PMC passes) and
+            # names the real bound; `roofline_valu` prices the same launches against the measured VALU issue ceiling of the kernel's opcode mix.
+            roofline = {"bound": "valu", "achieved": ach, "peak": 8000.0, "unit": "GB/s", "frac": ach / 8000.0, "traffic": traffic,
+                        "kernel": {"k_klt": "k_klt3"}.get(probe_kernel, probe_kernel), "launches": probe_n, "avg_launch_us": avg_s * 1e6, "algorithmic_bytes_per_launch": alg,
+                        "traffic_collected_on_other_kernel_sources": traffic_stale,
+                        "note": "frac is the HBM fraction (algorithmic bytes / launch time / 8 TB/s); the kernel is VALU-issue bound, see roofline_valu"}
+            roofline_valu = valu_roofline(pipe, a, probe_kernel, avg_s, n_kp)
+            if a.profile_part is None and a.mode == "step" and isinstance(roofline_valu, dict):
+                try:
+                    roofline_valu["step_kernels"] = kernel_table(pipe, a, n_kp)
+                    roofline_valu["step_kernels_note"] = ("every kernel of the step: HIP events around each of its launches in two extra steps (ms_in_step: beside the side "
+                                                          "streams) and with its stage issued alone (ms_alone); hbm_frac = algorithmic bytes (SURVEY 8d) / time / 8 TB/s; "
+                                                          "counter bytes from profiles/traffic.json, VALU instructions from profiles/valu_counts.json (guide peak: 1.2 G wave64 "
+                                                          "instructions / s / SIMD).  The events serialise nothing but add ~2 us per launch")
+                except Exception as e:
+                    roofline_valu["step_kernels"] = {"error": repr(e)}
+            alone = roofline_valu.get("kernels", {}).get(roofline["kernel"], {}).get("alone") if isinstance(roofline_valu, dict) else None
+            if alone:                                             # the same kernel with the GPU to itself (in the step its launch shares the CUs with three side streams)
+                roofline["avg_launch_us_alone"] = alone["avg_launch_us"]
+                roofline["achieved_alone"] = alg / (alone["avg_launch_us"] * 1e-6) / 1e9
+                roofline["frac_alone"] = roofline["achieved_alone"] / 8000.0
+                roofline["how"] = ("frac: HIP events around every launch of the kernel inside the timed steps (profiles/r05_step_kernel_stats.md holds the same launches); "
+                                   "frac_alone: 3 runs of the LK stage by itself after the timed region (profiles/r05_alone_kernel_stats.md)")
+            res.update(stage_ms_per_batch=stages, roofline=roofline, roofline_valu=roofline_valu)
         if a.mode == "stream":
             res["metric"] += ", frames streamed from host memory"
             res["stream"] = {"upload": a.upload, "h2d_bytes_per_step": pipe.h2d_bytes, "d2h_bytes_per_step": pipe.d2h_bytes,
@@ -1020,7 +1091,7 @@ def main():
                              "host_read_totals_last_step": list(getattr(pipes[(step_no[0] - 1) % n_buf], "last_counts", ())),
                              "note": "every step: H2D of the batch from page-locked memory, the 8-call hot path + good-match filter, D2H of all keypoint "
                                      "fields and the per-pair summary, host reads them; two batches in flight (upload of one under the kernels of the other)"}
-        if not a.no_cpu_baseline and world == 1:          # reported on rank 0 at N = 1 only
+        if a.full and not a.no_cpu_baseline and world == 1:          # reported on rank 0 at N = 1 only
             res["cpu_baseline"] = cpu_baseline(pipe)
     else:
         res = None

@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -20,7 +21,7 @@ def _last_json(out):
 
 def test_bench_contract_line_one_gpu():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "32", "--no-cpu-baseline",
-                        "--offline-frames", "64"],
+                        "--offline-frames", "64", "--full"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _last_json(r.stdout)
@@ -46,6 +47,33 @@ def test_bench_contract_line_one_gpu():
     assert d["value_with_transfers"] == st["bgr"]["value"] and "resident in HBM" in d["metric"]
     assert "frac_of_int8_peak" not in d["roofline_valu"]["mfma"]
     assert d["ranks"]["world"] == 1 and d["ranks"]["distinct_devices"] == 1 and len(d["ranks"]["per_rank"]) == 1
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """the plain run: the timed steps and the headline line only (nothing of --full), and --dump-outputs writes the last step's results"""
+    out = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--batch", "32",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = _last_json(r.stdout)
+    assert d["steps"] == 4 and d["warmup"] == 1 and d["unit"] == "frames/s" and d["higher_is_better"] is True and d["dtype"] == "u8/f32/f64"
+    assert abs(d["value"] - 32 * 1e3 / d["ms_per_step"]) <= 1e-6 * d["value"] and "resident in HBM" in d["metric"]
+    assert d["step_ms"]["steps"] == 4
+    for k in ("roofline", "roofline_valu", "stage_ms_per_batch", "cpu_baseline", "offline", "stream", "surface"):
+        assert k not in d, k
+    arrays = {f[:-4]: np.load(out / f) for f in os.listdir(out)}
+    assert all(f.endswith(".npy") for f in os.listdir(out)) and all(v.dtype in (np.float32, np.float64) for v in arrays.values())
+    assert sum(v.nbytes for v in arrays.values()) <= 64 << 20
+    pairs = arrays["pairs"].astype(int)
+    assert len(pairs) == 16 and np.all(np.diff(pairs) > 0) and 0 <= pairs[0] and pairs[-1] < 32
+    cnt = arrays["keypoint_count"]
+    assert cnt.shape == (32,) and np.all(cnt > 0)
+    assert np.array_equal(arrays["kp_len"], cnt[pairs]) and len(arrays["kp_level"]) == cnt[pairs].sum()
+    assert arrays["kp_desc"].shape == (cnt[pairs].sum(), 32) and np.all(arrays["kp_desc"] == np.rint(arrays["kp_desc"]))
+    for g, k in (("match", "match_idx"), ("klt", "klt_pts"), ("direct", "direct_px")):
+        assert len(arrays[g + "_len"]) == 16 and len(arrays[k]) == arrays[g + "_len"].sum() > 0
+    assert arrays["align_T"].shape == (16, 7) and np.all(np.isfinite(arrays["align_T"]))
+    assert arrays["ba_Hpp"].shape == (4, 10, 6, 6) and np.all(np.isfinite(arrays["ba_err"])) and arrays["ba_chi2"].shape == (4,)
 
 
 @pytest.mark.parametrize("mode", ["step", "offline"])

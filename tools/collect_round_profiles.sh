@@ -6,7 +6,7 @@
 #        alone : the same of `bench.py --profile-part alone` (every stage by itself)                          -> <round>_alone_kernel_stats.md
 #   2. --pmc FETCH_SIZE / WRITE_SIZE (own passes) of the step part -> pmc tables, traffic.json
 #   3. one SQ-counter pass over the stages -> sq counters, valu_counts.json
-#   4. the bench lines: default (with offline / stream / surface blocks), offline at 1024 / 512 / 256 / 128 frames, gray, surface
+#   4. the bench lines: default with --full (offline / stream / surface blocks), offline at 1024 / 512 / 256 / 128 frames, gray, surface
 #   5. the resident LM alone on the offline run's windows: phase timers + PMC traffic
 #   6. the surface loop: kernel table, device timeline of two frames (tools/surface_timeline.sh)
 # Outputs under gpurun_out/<round>p/; tools/collect_round_profiles.sh --copy (CPU, in the container) moves them into profiles/.
@@ -27,7 +27,7 @@ fi
 OUT=$R/gpurun_out/${ROUND}p
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-B="python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline"
+B="python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --full"
 for part in step alone; do
     rm -rf $OUT/raw_$part
     timeout 300 rocprofv3 --kernel-trace --stats -d $OUT/raw_$part -- $B --profile-part $part > $OUT/log_$part.txt 2>&1
@@ -48,7 +48,7 @@ cd $R
 NKP=$(timeout 300 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras 2>/dev/null | python -c "import json,sys; print(json.loads(sys.stdin.read().strip().splitlines()[-1])['config']['keypoints_per_frame'])")
 python tools/make_valu_counts.py $OUT/sq_counters_raw.md $OUT/valu_counts.json 256 $NKP
 cp $OUT/traffic.json $OUT/valu_counts.json $R/profiles/
-timeout 600 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+timeout 600 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
 for f in 1024 512 256 128; do timeout 300 python bench.py --mode offline --frames $f --steps 5 --warmup 2 --no-cpu-baseline > $OUT/bench_offline_f$f.json 2> $OUT/off_$f.err; done
 timeout 300 python bench.py --mode offline --frames 1024 --steps 5 --warmup 2 --no-cpu-baseline --upload gray > $OUT/bench_offline_f1024_gray.json 2> $OUT/off_gray.err
 YGZ_OFFLINE_TRACE=1 timeout 300 python bench.py --mode offline --frames 128 --steps 2 --warmup 1 --no-cpu-baseline 2>&1 > /dev/null | grep "offline host" | tail -14 > $OUT/offline128_trace.txt

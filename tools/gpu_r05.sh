@@ -73,7 +73,7 @@ import json; d=json.load(open('$OUT/surface.json'))['surface']; d.pop('what'); p
     ;;
 h)  # the whole GPU suite + the default bench line (after the pruning of the experiment forms)
     timeout 1200 python -m pytest tests -m gpu -x -q > $OUT/pytest.log 2>&1; grep -n "passed\|failed\|error" $OUT/pytest.log | tail -5
-    timeout 600 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; python - $OUT/bench_default.json <<'PY'
+    timeout 600 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; python - $OUT/bench_default.json <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 print("value %.0f ms/step %.3f" % (d["value"], d["ms_per_step"]), d.get("step_ms"))
