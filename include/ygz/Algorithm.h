@@ -6,4 +6,5 @@
 #include "ygz/Algorithm/SparseImageAlign.h"
 #include "ygz/Algorithm/CVUtils.h"
 #include "ygz/Algorithm/BA.h"
+#include "ygz/Algorithm/Initializer.h"
 #endif

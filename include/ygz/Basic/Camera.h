@@ -26,6 +26,8 @@ public:
     inline float cx() const { return _cx; }
     inline float cy() const { return _cy; }
     inline float focal() const { return _f; }
+    inline Matrix3d GetCameraMatrix() const                     // Camera.h:28-34
+    { Matrix3d m; m(0, 0) = _fx; m(0, 2) = _cx; m(1, 1) = _fy; m(1, 2) = _cy; m(2, 2) = 1; return m; }
 protected:
     float _fx, _fy, _cx, _cy, _f;
     float _k1, _k2, _p1, _p2;

@@ -110,6 +110,7 @@ namespace Sophus {
 class SO3 {
 public:
     SO3() { q_[0] = q_[1] = q_[2] = 0; q_[3] = 1; }
+    explicit SO3(const Matrix3d &R);                            // so3.cpp: Eigen's quaternion from a rotation matrix (trace branch, else the largest diagonal)
     static SO3 exp(const Vector3d &omega);                      // so3.cpp:171-202
     Vector3d log() const;                                       // so3.cpp:113-169
     SO3 inverse() const;
@@ -125,6 +126,7 @@ class SE3 {
 public:
     SE3() { t_[0] = t_[1] = t_[2] = 0; }
     SE3(const SO3 &so3, const Vector3d &t) : so3_(so3) { t_[0] = t[0]; t_[1] = t[1]; t_[2] = t[2]; }
+    SE3(const Matrix3d &R, const Vector3d &t) : so3_(R) { t_[0] = t[0]; t_[1] = t[1]; t_[2] = t[2]; }
     static SE3 exp(const Vector6d &upsilon_omega);              // se3.cpp:170-196
     Vector6d log() const;                                       // se3.cpp:198-220
     SE3 inverse() const;                                        // se3.cpp:77-84

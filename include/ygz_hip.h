@@ -40,7 +40,9 @@ extern "C" {
  * header would still link).  Bindings compare ygz_hip_abi_version() with the header they were written against at load time
  * (ygz_slam_amd/_lib.py, include/ygz/hip/Runtime.h).  5: ygz_hip_kf_row_bytes / ygz_hip_kf_store_create / ygz_hip_ba_build_windows
  * gained their trailing int (round 4); ygz_hip_get_stream / device_alloc / copy added (round 5).  6: ygz_ceres_options gained trust_region_strategy
- * (in the struct's tail padding: same size); ygz_hip_find_direct_projection_mp (+ _begin / _end), ygz_hip_sparse_align_residuals, ygz_hip_ba_light_barrier added (round 6). */
+ * (in the struct's tail padding: same size); ygz_hip_find_direct_projection_mp (+ _begin / _end), ygz_hip_sparse_align_residuals, ygz_hip_ba_light_barrier added (round 6).
+ * Still 6: the monocular Initializer added (ygz_init_params, ygz_init_result, ygz_hip_default_init_params, ygz_hip_initialize,
+ * ygz_hip_init_sample_sets, ygz_hip_init_hypotheses, ygz_hip_init_reconstruct) -- no existing argument list changed. */
 #define YGZ_HIP_ABI_VERSION 6
 
 typedef struct ygz_hip_ctx ygz_hip_ctx;
@@ -601,6 +603,56 @@ int  ygz_hip_bow_orientation(ygz_hip_ctx *ctx, const double *angle1, int n1, con
                              int *kept, int32_t *hist, int32_t *maxima);
 int  ygz_hip_bow_orientation_slots(ygz_hip_ctx *ctx, int n_pairs, const int32_t *slot1, const int32_t *slot2, const int32_t *match12,
                                    int32_t *kept, int32_t *hist, int32_t *maxima);
+
+/* ---- monocular initialisation: Initializer::TryInitialize (src/Algorithm/Initializer.cpp:9-87) ------------------------------
+ * H / F RANSAC over the reference's 8-point sample sets (a fresh cv::RNG per call), model choice rh = sh / (sh + sf) > 0.4, then
+ * ReconstructH (8 Faugeras solutions) or ReconstructF (4 solutions of E) with CheckRT per solution and point.  The arithmetic is that of
+ * tests/init_ref.c: every output is bit-identical to it. */
+#define YGZ_INIT_NONE  0
+#define YGZ_INIT_H     1
+#define YGZ_INIT_F     2
+#define YGZ_INIT_MAX_ITER 1024            /* bound of max_iter */
+typedef struct {                          /* Initializer::Option (Algorithm/Initializer.h:41-49) */
+    float  sigma;                         /* 2.0 */
+    float  sigma2;                        /* 4.0 */
+    int    max_iter;                      /* 200 RANSAC iterations (H and F each) */
+    double min_parallax;                  /* 1.0 degree (_min_parallex) */
+    int    min_triangulated;              /* 8 */
+    double good_point_ratio_h;            /* 0.9 */
+} ygz_init_params;
+typedef struct {
+    double  H21[9], F21[9];               /* best homography / fundamental matrix (row-major; 0 when no hypothesis scored above 0) */
+    double  R21[9], t21[3];               /* motion of the accepted solution, x2 = R21 x1 + t21 (|t21| = 1); I / 0 when not accepted */
+    double  T21[7];                       /* SE3(R21, t21) as qx qy qz qw tx ty tz (Sophus SO3(const Matrix3d &)) */
+    double  parallax;                     /* degrees, of the best solution (the 51st smallest parallax of its points) */
+    float   score_h, score_f, rh;         /* best scores (float sums in point order), rh = sh / (sh + sf) */
+    int32_t success;                      /* TryInitialize's return value */
+    int32_t model;                        /* YGZ_INIT_NONE / _H / _F: the model reconstructed from */
+    int32_t best_h, best_f;               /* winning hypotheses (-1: none scored above 0) */
+    int32_t n_inliers;                    /* inliers of the model reconstructed from */
+    int32_t solution;                     /* index of the best solution (0..7 for H, 0..3 for F; -1: none) */
+    int32_t n_good, second_good;          /* points of the best and of the second-best solution that pass CheckRT */
+    int32_t similar;                      /* F: solutions with more than 0.7 * n_good points (0 for H) */
+    int32_t n_triangulated;               /* set entries of triangulated_out */
+} ygz_init_result;
+void ygz_hip_default_init_params(ygz_init_params *p);
+/* The fused call: px1 / px2 [n][2] matched pixels of the reference and the current frame, K4 = fx fy cx cy (PinholeCamera::GetCameraMatrix),
+ * params NULL: defaults.  pts3d_out [n][3] (camera-1 coordinates) and triangulated_out [n] (may be NULL) hold the accepted solution's points
+ * (0 elsewhere and on failure).  One upload, the launches, one copy back and one wait.  8 <= n <= ygz_hip_max_keypoints (YGZ_E_INVALID /
+ * YGZ_E_CAPACITY before anything is launched); result->success is the reference's return value. */
+int  ygz_hip_initialize(ygz_hip_ctx *ctx, const double *px1, const double *px2, int n, const double K4[4], const ygz_init_params *params,
+                        ygz_init_result *result, double *pts3d_out, uint8_t *triangulated_out);
+/* stages, for tests and diagnosis.  The sample sets [max_iter][8] (host only, no context: they depend on n and max_iter alone). */
+int  ygz_hip_init_sample_sets(int n, int max_iter, int32_t *sets);
+/* every hypothesis: H21 / F21 [max_iter][9] and their scores [max_iter] (each may be NULL), the winners' inlier masks [n] (may be NULL) and
+ * in result the fields of the model choice (H21, F21, score_h, score_f, rh, model, best_h, best_f; the rest 0) */
+int  ygz_hip_init_hypotheses(ygz_hip_ctx *ctx, const double *px1, const double *px2, int n, const ygz_init_params *params, double *H21,
+                             double *F21, float *score_h, float *score_f, uint8_t *inliers_h, uint8_t *inliers_f, ygz_init_result *result);
+/* ReconstructH (model YGZ_INIT_H, M = H21) or ReconstructF (YGZ_INIT_F, M = F21) from a given model and its inlier mask [n]: result gets
+ * the reconstruction's fields (model, R21, t21, T21, parallax, success, n_inliers, solution, n_good, second_good, similar, n_triangulated; the rest 0) */
+int  ygz_hip_init_reconstruct(ygz_hip_ctx *ctx, const double *px1, const double *px2, int n, const double K4[4], const ygz_init_params *params,
+                              int model, const double M[9], const uint8_t *inliers, ygz_init_result *result, double *pts3d_out,
+                              uint8_t *triangulated_out);
 
 #ifdef __cplusplus
 }

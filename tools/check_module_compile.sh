@@ -5,7 +5,7 @@
 # names are created in a temporary directory for the duration of the check so that the compiler gets past the #include
 # lines (nothing is built, linked or kept -- g++ -fsyntax-only).
 # Expected result (recorded in INTEGRATION.md): every hot-path call and (round 6) the covisibility members of Frame resolve; what remains
-# is out of scope by SURVEY 2.1 -- the Initializer, highgui drawing (cv::circle, putText, imshow, waitKey, Scalar, CV_FONT_*) and boost::format.
+# is out of scope by SURVEY 2.1 -- highgui drawing (cv::circle, putText, imshow, waitKey, Scalar, CV_FONT_*) and boost::format.
 set -u
 REF=${1:-/root/reference}
 ROOT=$(cd "$(dirname "$0")/.." && pwd)

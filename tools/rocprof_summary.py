@@ -11,7 +11,7 @@ rows = list(cur.execute("select %s, count(*), sum(end-start), avg(end-start), mi
 tot = sum(r[2] for r in rows) or 1
 lines = ["| kernel | calls | total us | avg us | min us | max us | % |", "|---|---|---|---|---|---|---|"]
 for n, c, s, a, mn, mx in rows:
-    lines.append("| %s | %d | %.1f | %.2f | %.2f | %.2f | %.1f |" % (n.split("(")[0][:60], c, s / 1e3, a / 1e3, mn / 1e3, mx / 1e3, 100.0 * s / tot))
+    lines.append("| %s | %d | %.1f | %.2f | %.2f | %.2f | %.1f |" % (n.replace("(anonymous namespace)::", "").split("(")[0][:60], c, s / 1e3, a / 1e3, mn / 1e3, mx / 1e3, 100.0 * s / tot))
 out = "\n".join(lines)
 print(out)
 if len(sys.argv) > 2:

@@ -82,6 +82,50 @@ class BaStats(C.Structure):
                 ("lambda_final", C.c_double)]
 
 
+class InitParams(C.Structure):
+    _fields_ = [("sigma", C.c_float), ("sigma2", C.c_float), ("max_iter", C.c_int), ("min_parallax", C.c_double), ("min_triangulated", C.c_int),
+                ("good_point_ratio_h", C.c_double)]
+
+
+class InitResult(C.Structure):
+    _fields_ = [("H21", C.c_double * 9), ("F21", C.c_double * 9), ("R21", C.c_double * 9), ("t21", C.c_double * 3), ("T21", C.c_double * 7),
+                ("parallax", C.c_double), ("score_h", C.c_float), ("score_f", C.c_float), ("rh", C.c_float), ("success", C.c_int32),
+                ("model", C.c_int32), ("best_h", C.c_int32), ("best_f", C.c_int32), ("n_inliers", C.c_int32), ("solution", C.c_int32),
+                ("n_good", C.c_int32), ("second_good", C.c_int32), ("similar", C.c_int32), ("n_triangulated", C.c_int32)]
+
+    def to_dict(self):
+        d = {}
+        for name, ty in self._fields_:
+            v = getattr(self, name)
+            d[name] = np.array(v[:]) if hasattr(ty, "_length_") else v
+        return d
+
+
+def default_init_params():
+    p = InitParams()
+    load().ygz_hip_default_init_params(C.byref(p))
+    return p
+
+
+def _init_params(**kw):
+    p = default_init_params()
+    for k, v in kw.items():
+        if v is not None:
+            setattr(p, k, v)
+    return p
+
+
+def init_sample_sets(n, max_iter=200):
+    """the 8-point sample sets of Initializer::TryInitialize (Initializer.cpp:24-48): [max_iter][8], host only"""
+    s = np.zeros((max(max_iter, 1), 8), np.int32)
+    lib = load()
+    lib.ygz_hip_init_sample_sets.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int32)]
+    rc = lib.ygz_hip_init_sample_sets(n, max_iter, _p(s, C.c_int32))
+    if rc != OK:
+        raise YgzHipError(rc, "init_sample_sets")
+    return s
+
+
 # every symbol include/ygz_hip.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
     "ygz_hip_default_params", "ygz_hip_create", "ygz_hip_destroy", "ygz_hip_synchronize", "ygz_hip_join", "ygz_hip_set_overlap", "ygz_hip_error_string",
@@ -104,7 +148,10 @@ ABI_SYMBOLS = [
     "ygz_hip_kf_row_bytes", "ygz_hip_kf_store_create", "ygz_hip_kf_store_info", "ygz_hip_kf_store_put", "ygz_hip_kf_store_put_trel",
     "ygz_hip_kf_store_set_trel", "ygz_hip_kf_store_refresh", "ygz_hip_ba_reserve_windows", "ygz_hip_ba_build_windows", "ygz_hip_ba_pack_states", "ygz_hip_ba_mark_outliers", "ygz_hip_ba_get_outlier_stats", "ygz_hip_bow_orientation", "ygz_hip_bow_orientation_slots", "ygz_hip_ba_last_path",
     "ygz_hip_abi_version", "ygz_hip_ba_optimize_chi2", "ygz_hip_ba_set_team_placement", "ygz_hip_get_stream", "ygz_hip_get_device", "ygz_hip_make_current", "ygz_hip_device_alloc", "ygz_hip_device_free", "ygz_hip_copy",
+    "ygz_hip_default_init_params", "ygz_hip_initialize", "ygz_hip_init_sample_sets", "ygz_hip_init_hypotheses", "ygz_hip_init_reconstruct",
 ]
+INIT_SYMBOLS = ["ygz_hip_default_init_params", "ygz_hip_initialize", "ygz_hip_init_sample_sets", "ygz_hip_init_hypotheses", "ygz_hip_init_reconstruct"]
+INIT_NONE, INIT_H, INIT_F = 0, 1, 2
 
 SUMMARY_FIELDS = 32
 
@@ -831,6 +878,64 @@ class HipContext:
         self._chk(self.lib.ygz_hip_depth_from_triangulation(self._ctx, T, _p(fr, C.c_double), _p(fc, C.c_double), n, float(determinant_th),
                                                             _p(d1, C.c_double), _p(d2, C.c_double), _p(ok, C.c_uint8)), "depth_from_triangulation")
         return d1[:n], d2[:n], ok[:n]
+
+    # ---- monocular initialisation (Initializer::TryInitialize)
+
+    def _init_args(self, px1, px2):
+        px1 = np.ascontiguousarray(px1, np.float64).reshape(-1, 2)
+        px2 = np.ascontiguousarray(px2, np.float64).reshape(-1, 2)
+        if len(px1) != len(px2):
+            raise ValueError("px1 and px2 differ in length")
+        return px1, px2, len(px1)
+
+    def initialize(self, px1, px2, K4, **params):
+        """the fused call (ygz_hip_initialize): dict of the result fields, pts3d [n][3], triangulated [n] (bool).  params: the fields of
+        ygz_init_params (sigma, sigma2, max_iter, min_parallax, min_triangulated, good_point_ratio_h)"""
+        px1, px2, n = self._init_args(px1, px2)
+        K = (C.c_double * 4)(*[float(v) for v in K4])
+        prm, res = _init_params(**params), InitResult()
+        p3d, tri = np.zeros((max(n, 1), 3)), np.zeros(max(n, 1), np.uint8)
+        self.lib.ygz_hip_initialize.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double),
+                                                C.POINTER(InitParams), C.POINTER(InitResult), C.POINTER(C.c_double), C.POINTER(C.c_uint8)]
+        self._chk(self.lib.ygz_hip_initialize(self._ctx, _p(px1, C.c_double), _p(px2, C.c_double), n, K, C.byref(prm), C.byref(res),
+                                              _p(p3d, C.c_double), _p(tri, C.c_uint8)), "initialize")
+        d = res.to_dict()
+        d["pts3d"], d["triangulated"] = p3d[:n], tri[:n].astype(bool)
+        return d
+
+    def init_hypotheses(self, px1, px2, **params):
+        """every H / F hypothesis with its score, the winners' inlier masks and the model choice (ygz_hip_init_hypotheses)"""
+        px1, px2, n = self._init_args(px1, px2)
+        prm, res = _init_params(**params), InitResult()
+        it = prm.max_iter
+        H, F = np.zeros((max(it, 1), 3, 3)), np.zeros((max(it, 1), 3, 3))
+        sh, sf = np.zeros(max(it, 1), np.float32), np.zeros(max(it, 1), np.float32)
+        ih, jf = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.uint8)
+        self.lib.ygz_hip_init_hypotheses.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.POINTER(InitParams),
+                                                     C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                                     C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.POINTER(InitResult)]
+        self._chk(self.lib.ygz_hip_init_hypotheses(self._ctx, _p(px1, C.c_double), _p(px2, C.c_double), n, C.byref(prm), _p(H, C.c_double),
+                                                   _p(F, C.c_double), _p(sh, C.c_float), _p(sf, C.c_float), _p(ih, C.c_uint8), _p(jf, C.c_uint8),
+                                                   C.byref(res)), "init_hypotheses")
+        return dict(H21=H[:it], F21=F[:it], score_h=sh[:it], score_f=sf[:it], inliers_h=ih[:n].astype(bool), inliers_f=jf[:n].astype(bool),
+                    result=res.to_dict())
+
+    def init_reconstruct(self, px1, px2, K4, model, M, inliers, **params):
+        """ReconstructH (model INIT_H, M = H21) / ReconstructF (INIT_F, M = F21) from a given model (ygz_hip_init_reconstruct)"""
+        px1, px2, n = self._init_args(px1, px2)
+        K = (C.c_double * 4)(*[float(v) for v in K4])
+        Mm = (C.c_double * 9)(*[float(v) for v in np.asarray(M, np.float64).ravel()])
+        inl = np.ascontiguousarray(inliers, np.uint8).reshape(-1)
+        prm, res = _init_params(**params), InitResult()
+        p3d, tri = np.zeros((max(n, 1), 3)), np.zeros(max(n, 1), np.uint8)
+        self.lib.ygz_hip_init_reconstruct.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double),
+                                                      C.POINTER(InitParams), C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_uint8),
+                                                      C.POINTER(InitResult), C.POINTER(C.c_double), C.POINTER(C.c_uint8)]
+        self._chk(self.lib.ygz_hip_init_reconstruct(self._ctx, _p(px1, C.c_double), _p(px2, C.c_double), n, K, C.byref(prm), int(model), Mm,
+                                                    _p(inl, C.c_uint8), C.byref(res), _p(p3d, C.c_double), _p(tri, C.c_uint8)), "init_reconstruct")
+        d = res.to_dict()
+        d["pts3d"], d["triangulated"] = p3d[:n], tri[:n].astype(bool)
+        return d
 
     # ---- BoW
     def vocab_load(self, blob):
