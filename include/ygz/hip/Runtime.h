@@ -3,6 +3,8 @@
 // HBM slots (least-recently-used eviction, transparent re-upload) and remembers which host pyramid level mirrors
 // which (frame, level) so that cvutils::Align2D(const cv::Mat&, ...) can find the HBM copy of its image argument.
 // Environment: YGZ_HIP_DEVICE (default 0), YGZ_HIP_MAX_FRAMES (default 64).
+// Threading: one thread at a time uses the Runtime -- its context, its slots and the FindDirectProjection memo below, i.e. every class surface;
+// nothing here takes a lock.  Frames destroyed after the Runtime (during static destruction) leave it alone.
 #ifndef YGZ_HIP_RUNTIME_H_
 #define YGZ_HIP_RUNTIME_H_
 #include <cstdint>
@@ -10,6 +12,7 @@ struct ygz_hip_ctx;
 namespace ygz {
 struct Frame;
 namespace hip {
+class FdpMemo;
 class Runtime {
 public:
     static Runtime &Get();
@@ -19,6 +22,7 @@ public:
     void Release(Frame *f);
     void RegisterLevels(Frame *f);
     bool FindLevel(const uint8_t *data, Frame **f, int *level);
+    FdpMemo &Fdp();                     // the memo behind Matcher::FindDirectProjection (host/fdp_memo.h, the library's own)
 private:
     Runtime();
     ~Runtime();
@@ -29,10 +33,11 @@ private:
 // anything else -> LOG(ERROR) with the ABI's message and false, and the surface that called returns its failure value (false / 0 / unchanged
 // outputs).  Only a missing device -- there is no CPU path to fall back to -- throws (Runtime::ctx).
 bool check(int rc, const char *what);
-// Matcher::FindDirectProjection behind per-candidate callers (ygz_host.cpp: FdpMemo): one speculative launch per current frame, answers handed out
+// Matcher::FindDirectProjection behind per-candidate callers (fdp_memo.cpp: FdpMemo): one speculative launch per current frame, answers handed out
 // only on bit-equal inputs.  Environment YGZ_FDP_MEMO=0 (or SetFdpSpeculation(false)) makes every call its own n = 1 launch.  When the previous
-// current frame was served that way, the launch of the next one is queued at the end of Matcher::SparseImageAlignment (its pose is known there) and
-// collected at its first per-candidate call -- the caller's own FindCandidates runs in between; YGZ_FDP_PRELAUNCH=0: launch at the first call.
+// current frame was served per candidate, the launch of the next one is queued at the end of Matcher::SparseImageAlignment (its pose is known there)
+// and collected at its first per-candidate call -- the caller's own FindCandidates runs in between; a caller that changes the pose afterwards, or asks
+// about other keyframes, gets the launch at its first call.
 struct FdpMemoStats { unsigned long long hits = 0, single = 0, launches = 0, speculated = 0; double speculate_ms = 0; };
 void SetFdpSpeculation(bool on);
 void SetFdpBypass(bool on);             // true: calls take their own n = 1 launch and leave the memo as it is (to compare the two inside one loop)

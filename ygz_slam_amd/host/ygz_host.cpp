@@ -6,13 +6,13 @@
 #include "ygz/Algorithm.h"
 #include "ygz/hip/Runtime.h"
 #include "ygz_hip.h"
+#include "fdp_memo.h"
 #include "../csrc/se3_dev.h"
 #include "../csrc/ldlt6.h"
 #include <fstream>
 #include <stdexcept>
 #include <cstdlib>
 #include <chrono>
-#include <limits>
 
 int ygz_log::verbosity = 0;
 
@@ -71,6 +71,7 @@ std::string Config::Raw(const std::string &key) { auto it = cfg().find(key); ret
 
 // ------------------------------------------------------------------------------------------ Runtime (context + slots)
 namespace hip {
+namespace { bool runtime_destroyed = false; }      // set by ~Runtime; constant-initialised, so it outlives every Frame that Runtime::Release must skip
 struct Runtime::Impl {
     ygz_hip_ctx *ctx = nullptr;
     int max_frames = 0, levels = 0, cells = 0;
@@ -78,10 +79,12 @@ struct Runtime::Impl {
     std::vector<unsigned long long> stamp;
     unsigned long long clock = 0;
     std::map<const uint8_t *, std::pair<Frame *, int>> level_of;     // host level data -> (frame, level)
+    FdpMemo fdp;
 };
 Runtime &Runtime::Get() { static Runtime r; return r; }
 Runtime::Runtime() : p_(new Impl) {}
-Runtime::~Runtime() { if (p_->ctx) ygz_hip_destroy(p_->ctx); delete p_; }
+Runtime::~Runtime() { runtime_destroyed = true; ygz_hip_ctx *c = p_->ctx; delete p_; if (c) ygz_hip_destroy(c); }      // the slots and the memo go before the context
+FdpMemo &Runtime::Fdp() { return p_->fdp; }
 bool check(int rc, const char *what)
 {
     if (rc == YGZ_OK) return true;
@@ -110,10 +113,9 @@ ygz_hip_ctx *Runtime::ctx()
     return p_->ctx;
 }
 int Runtime::cells() { ctx(); return p_->cells; }
-void fdp_memo_forget(const Frame *f);
 void Runtime::Release(Frame *f)
 {
-    fdp_memo_forget(f);
+    p_->fdp.forget(f);
     for (auto it = p_->level_of.begin(); it != p_->level_of.end();) { if (it->second.first == f) it = p_->level_of.erase(it); else ++it; }
     if (f->_hip_slot >= 0 && f->_hip_slot < (int)p_->owner.size() && p_->owner[f->_hip_slot] == f) p_->owner[f->_hip_slot] = nullptr;
     f->_hip_slot = -1;
@@ -161,7 +163,7 @@ int Runtime::Resident(Frame *f)
 // ------------------------------------------------------------------------------------------ Frame
 PinholeCamera *Frame::_camera = nullptr;
 ORBVocabulary *Frame::_vocab = nullptr;
-Frame::~Frame() { if (!_features.empty()) CleanAllFeatures(); hip::Runtime::Get().Release(this); }
+Frame::~Frame() { if (!_features.empty()) CleanAllFeatures(); if (!hip::runtime_destroyed) hip::Runtime::Get().Release(this); }
 
 void hip::PyramidMirror::fetch(size_t L)
 {   // the first reader of a level pays for its copy (and nobody else pays for levels nobody reads)
@@ -772,318 +774,6 @@ int Matcher::BruteForceMatch(Frame *frame1, Frame *frame2, vector<DMatch> &match
     return (int)matches.size();
 }
 
-
-// ------------------------------------------------------------------------------------------ FindDirectProjection behind its per-candidate callers
-// LocalMapping::ProjectMapPoints calls Matcher::FindDirectProjection once per candidate (src/Module/LocalMapping.cpp:88-118, 1000-3800 calls per
-// frame) and CreateNewMapPoints once per matched feature pair (:447).  One call = upload, launch, download, synchronise: ~40 us, i.e. tens of
-// milliseconds per frame.  FindDirectProjection is a pure function of (both images, both poses, the reference observation, the map point's
-// position / the feature's depth, the prediction), so the first call of a current frame that misses runs ONE launch over every candidate the caller
-// can be expected to ask about (below) and keeps the answers; the calls that follow are a table look-up.  An answer is handed out only when every
-// input of the call equals the memoised one BIT FOR BIT -- anything else takes the n = 1 launch --, so results are identical to n = 1 calls
-// (tests/test_gpu_surface.py: the per-candidate loop with YGZ_FDP_MEMO=0 against the default).
-//
-// What is speculated, MapPoint overload: for the keyframe `ref` of the call and every keyframe the previous current frame asked about, every
-// feature of the keyframe that observes a good map point (mp->_obs[ref->_keyframe_id]), with the prediction FindCandidates makes
-// (Camera2Pixel(World2Camera(mp->_pos_world, curr->_TCW)), LocalMapping.cpp:58-59, evaluated by the launch itself and compared with the caller's).
-// A keyframe that was not covered gets its own launch on its first miss.  Feature overload: the matches the same Matcher object's last
-// SearchForTriangulation(ref, curr, ...) returned, with the depth and prediction CreateNewMapPoints forms from them (LocalMapping.cpp:416-446).
-namespace {
-inline bool same7(const SE3 &T, const double t7[7])
-{ return memcmp(T.so3_.q_, t7, 32) == 0 && memcmp(T.t_, t7 + 4, 24) == 0; }
-inline bool env_on(const char *name, bool dflt) { const char *e = getenv(name); return e ? atoi(e) != 0 : dflt; }
-
-struct FdpMemo {
-    struct Ref { Frame *f; double T[7]; };
-    struct Entry {                                     // inputs (compared on every look-up) and outputs of one candidate
-        const Frame *ref; const void *key;             // key: the MapPoint (MapPoint overload) or the reference Feature (Feature overload)
-        double a[3];                                   // mp->_pos_world | (fea->_depth, 0, 0)
-        double px_ref[2]; int32_t level;
-        double px_in[2], px_out[2]; int32_t sl; uint8_t ok;
-    };
-    Frame *curr = nullptr;
-    double T_cur[7];
-    std::vector<Ref> refs;                             // keyframes whose map-point candidates are in the table (MapPoint overload)
-    std::vector<Ref> feat_refs;                        // keyframes whose triangulation candidates are in the table (Feature overload)
-    std::vector<Entry> entries;
-    std::vector<int32_t> table;                        // open addressing over (ref, key), -1 = free
-    std::vector<Frame *> asked, asked_prev;            // keyframes the calls of this / the previous current frame named
-    hip::FdpMemoStats st;
-    bool enabled = env_on("YGZ_FDP_MEMO", true);
-    bool prelaunch = env_on("YGZ_FDP_PRELAUNCH", true);   // queue the frame's speculative launch at the end of Matcher::SparseImageAlignment (below)
-    bool bypass = false;                               // calls take the n = 1 launch and leave the memo alone (A/B inside one loop)
-    // a speculative launch that has been queued (ygz_hip_find_direct_projection_mp_begin) and not collected yet: what was asked
-    struct Gathered {                                  // the candidates of some keyframes: everything a launch needs except the current frame's pose
-        std::vector<Frame *> kfs; std::vector<int32_t> kf_slot; std::vector<double> kf_T;
-        std::vector<int32_t> ck, cl; std::vector<double> pos, cpx; std::vector<const MapPoint *> cmp;
-        std::vector<Entry> ent; std::vector<int32_t> tab;   // optional: the table entries of these candidates with their input fields, and the hash table over them (fdp_prebuild)
-        void reset() { kfs.clear(); kf_slot.clear(); kf_T.clear(); ck.clear(); cl.clear(); pos.clear(); cpx.clear(); cmp.clear(); ent.clear(); tab.clear(); }
-    };
-    struct Pending : Gathered { int n = 0; size_t first_ref = 0; } pend;
-    // candidates gathered while Matcher::SparseImageAlignment waited for its kernel (ygz_hip_set_wait_hook), for the launch that follows it
-    struct Pre : Gathered { Frame *curr = nullptr; std::vector<Frame *> batch; bool valid = false; } pre;
-
-    static size_t hash(const Frame *ref, const void *key)
-    { uint64_t h = (uint64_t)(uintptr_t)key * 0x9E3779B97F4A7C15ull ^ (uint64_t)(uintptr_t)ref * 0xC2B2AE3D27D4EB4Full; return (size_t)(h ^ (h >> 29)); }
-    void clear() { curr = nullptr; refs.clear(); feat_refs.clear(); entries.clear(); table.clear(); pend.n = 0; }   // (pre survives: it belongs to the frame about to begin)
-    void begin(Frame *c)
-    {   // a new current frame (or the same one with another pose): the answers of the last one are void, the keyframes it named are the guess
-        if (!asked.empty()) asked_prev.swap(asked);
-        asked.clear();
-        clear();
-        curr = c; c->_TCW.to7(T_cur);
-    }
-    bool valid_for(Frame *c) const { return curr == c && same7(c->_TCW, T_cur); }
-    const Ref *ref_of(const Frame *f) const { for (const Ref &r : refs) if (r.f == f) return &r; return nullptr; }
-    const Ref *feat_ref_of(const Frame *f) const { for (const Ref &r : feat_refs) if (r.f == f) return &r; return nullptr; }
-    void note_asked(Frame *f) { for (Frame *a : asked) if (a == f) return; asked.push_back(f); }
-    static void build_table(const std::vector<Entry> &ent, std::vector<int32_t> &tab)
-    {
-        size_t cap = 64;
-        while (cap < 2 * ent.size() + 2) cap <<= 1;
-        tab.assign(cap, -1);
-        for (size_t i = 0; i < ent.size(); ++i) {
-            size_t h = hash(ent[i].ref, ent[i].key) & (cap - 1);
-            while (tab[h] >= 0) h = (h + 1) & (cap - 1);
-            tab[h] = (int32_t)i;
-        }
-    }
-    void rebuild_table() { build_table(entries, table); }
-    const Entry *find(const Frame *ref, const void *key) const
-    {
-        if (table.empty()) return nullptr;
-        const size_t mask = table.size() - 1;
-        for (size_t h = hash(ref, key) & mask; table[h] >= 0; h = (h + 1) & mask) {
-            const Entry &e = entries[table[h]];
-            if (e.ref == ref && e.key == key) return &e;
-        }
-        return nullptr;
-    }
-};
-FdpMemo &fdp_memo() { static FdpMemo m; return m; }
-}  // namespace
-void hip::fdp_memo_forget(const Frame *f)
-{   // a frame that is (re)initialised or deleted takes every answer that involves it along
-    FdpMemo &M = fdp_memo();
-    auto drop = [&](std::vector<Frame *> &v) { v.erase(std::remove(v.begin(), v.end(), f), v.end()); };
-    drop(M.asked); drop(M.asked_prev);
-    M.pre.valid = false;
-    if (M.curr == f || M.ref_of(f) || M.feat_ref_of(f)) M.clear();
-}
-void hip::SetFdpSpeculation(bool on) { fdp_memo().enabled = on; if (!on) fdp_memo().clear(); }
-void hip::SetFdpBypass(bool on) { fdp_memo().bypass = on; }
-hip::FdpMemoStats hip::GetFdpMemoStats() { return fdp_memo().st; }
-void hip::ResetFdpMemoStats() { fdp_memo().st = hip::FdpMemoStats(); }
-
-namespace {
-// the answers of one launch over the gathered candidates become entries of the table
-void fdp_absorb(FdpMemo &M, const std::vector<Frame *> &kfs, const std::vector<int32_t> &ck, const std::vector<int32_t> &cl, const std::vector<const MapPoint *> &cmp,
-                const std::vector<double> &pos, const std::vector<double> &cpx, const std::vector<uint8_t> &vis, const std::vector<double> &proj,
-                const std::vector<uint8_t> &ok, const std::vector<double> &out, const std::vector<int32_t> &sl)
-{
-    const int n = (int)ck.size();
-    M.st.launches++; M.st.speculated += n;
-    M.entries.reserve(M.entries.size() + n);
-    for (int i = 0; i < n; ++i) {
-        if (!vis[i]) continue;                                         // FindCandidates drops it (LocalMapping.cpp:60-63): nobody asks
-        FdpMemo::Entry e;
-        e.ref = kfs[ck[i]]; e.key = cmp[i];
-        e.a[0] = pos[3 * i]; e.a[1] = pos[3 * i + 1]; e.a[2] = pos[3 * i + 2];
-        e.px_ref[0] = cpx[2 * i]; e.px_ref[1] = cpx[2 * i + 1]; e.level = cl[i];
-        e.px_in[0] = proj[2 * i]; e.px_in[1] = proj[2 * i + 1];
-        e.px_out[0] = out[2 * i]; e.px_out[1] = out[2 * i + 1]; e.sl = sl[i]; e.ok = ok[i];
-        M.entries.push_back(e);
-    }
-    M.rebuild_table();
-}
-// pure host work, no call into the context: every observation of a good map point in the keyframes of `batch` that hold an image (`skip_covered`: and
-// are not in the table yet), with the keyframes' poses and the HBM slots they sit in as of now
-void fdp_gather(const FdpMemo &M, const Frame *curr, const std::vector<Frame *> &batch, bool skip_covered, FdpMemo::Gathered &G)
-{
-    G.reset();
-    const int levels = curr->_option._pyramid_level;
-    for (Frame *r : batch)
-        if (r != curr && !r->_pyramid.empty() && !(skip_covered && M.ref_of(r)) && std::find(G.kfs.begin(), G.kfs.end(), r) == G.kfs.end()) G.kfs.push_back(r);
-    for (size_t k = 0; k < G.kfs.size(); ++k) {
-        Frame *r = G.kfs[k];
-        G.kf_slot.push_back(r->_hip_slot); double t7[7]; r->_TCW.to7(t7); G.kf_T.insert(G.kf_T.end(), t7, t7 + 7);
-        const size_t n0 = r->_features.size();
-        G.ck.reserve(G.ck.size() + n0); G.cl.reserve(G.cl.size() + n0); G.pos.reserve(G.pos.size() + 3 * n0); G.cpx.reserve(G.cpx.size() + 2 * n0); G.cmp.reserve(G.cmp.size() + n0);
-        for (const Feature *f : r->_features) {
-            const MapPoint *mp = f->_mappoint;
-            if (!mp || mp->_bad) continue;
-            // (whether f is the Feature the method reads, mp->_obs[ref->_keyframe_id] (Matcher.cpp:361), is settled at look-up time by comparing
-            // pixel and level: a tree look-up per feature here was a third of the gather)
-            if (f->_level < 0 || f->_level >= levels) continue;
-            G.ck.push_back((int32_t)k); G.cl.push_back(f->_level); G.cmp.push_back(mp);
-            G.pos.push_back(mp->_pos_world[0]); G.pos.push_back(mp->_pos_world[1]); G.pos.push_back(mp->_pos_world[2]);
-            G.cpx.push_back(f->_pixel[0]); G.cpx.push_back(f->_pixel[1]);
-        }
-    }
-}
-// the table entries of the gathered candidates with everything that is known before the launch (the inputs the look-up compares), and the hash table over
-// them -- host work that fits into the same wait as the gather; the launch's answers are filled in by fdp_collect
-void fdp_prebuild(FdpMemo::Gathered &G)
-{
-    const size_t n = G.ck.size();
-    G.ent.resize(n);
-    const double nan = std::numeric_limits<double>::quiet_NaN();
-    for (size_t i = 0; i < n; ++i) {
-        FdpMemo::Entry &e = G.ent[i];
-        e.ref = G.kfs[G.ck[i]]; e.key = G.cmp[i];
-        e.a[0] = G.pos[3 * i]; e.a[1] = G.pos[3 * i + 1]; e.a[2] = G.pos[3 * i + 2];
-        e.px_ref[0] = G.cpx[2 * i]; e.px_ref[1] = G.cpx[2 * i + 1]; e.level = G.cl[i];
-        e.px_in[0] = e.px_in[1] = nan; e.px_out[0] = e.px_out[1] = 0; e.sl = 0; e.ok = 0;      // no prediction equals NaN: unanswered until collected
-    }
-    FdpMemo::build_table(G.ent, G.tab);
-}
-// the gathered candidates against `curr` in one launch, appended to the memo.  defer: the launch is queued and collected by fdp_collect at the first
-// look-up (the caller's own FindCandidates runs in between)
-void fdp_launch(FdpMemo &M, Frame *curr, FdpMemo::Gathered &G, bool defer)
-{
-    hip::Runtime &rt = hip::Runtime::Get();
-    if (G.kfs.empty() || curr->_pyramid.empty()) return;
-    const int cs = rt.Resident(curr);
-    for (size_t k = 0; k < G.kfs.size(); ++k) if (rt.Resident(G.kfs[k]) != G.kf_slot[k] || G.kf_slot[k] < 0) return;   // (not resident when gathered, or more keyframes than HBM slots: no speculation)
-    if (curr->_hip_slot != cs) return;
-    for (size_t k = 0; k < G.kfs.size(); ++k) if (G.kfs[k]->_hip_slot != G.kf_slot[k]) return;
-    const size_t first_ref = M.refs.size();
-    for (size_t k = 0; k < G.kfs.size(); ++k) { FdpMemo::Ref R; R.f = G.kfs[k]; memcpy(R.T, &G.kf_T[7 * k], 56); M.refs.push_back(R); }
-    const int n = (int)G.ck.size();
-    if (n == 0) return;
-    if (defer) {
-        if (ygz_hip_find_direct_projection_mp_begin(rt.ctx(), cs, M.T_cur, (int)G.kfs.size(), G.kf_slot.data(), G.kf_T.data(), n, G.ck.data(), G.pos.data(), G.cpx.data(),
-                                                    G.cl.data()) != YGZ_OK) { M.refs.resize(first_ref); return; }
-        FdpMemo::Pending &P = M.pend;
-        P.n = n; P.first_ref = first_ref;
-        P.kfs.swap(G.kfs); P.kf_slot.swap(G.kf_slot); P.kf_T.swap(G.kf_T); P.ck.swap(G.ck); P.cl.swap(G.cl); P.pos.swap(G.pos); P.cpx.swap(G.cpx); P.cmp.swap(G.cmp);
-        P.ent.swap(G.ent); P.tab.swap(G.tab);
-        return;
-    }
-    std::vector<uint8_t> vis(n), ok(n); std::vector<double> proj(2 * (size_t)n), out(2 * (size_t)n); std::vector<int32_t> sl(n);
-    if (ygz_hip_find_direct_projection_mp(rt.ctx(), cs, M.T_cur, (int)G.kfs.size(), G.kf_slot.data(), G.kf_T.data(), n, G.ck.data(), G.pos.data(), G.cpx.data(),
-                                          G.cl.data(), nullptr, vis.data(), proj.data(), ok.data(), out.data(), sl.data()) != YGZ_OK) {
-        M.refs.resize(first_ref);                                      // nothing learnt; the calls take the n = 1 path (and report the error there)
-        return;
-    }
-    fdp_absorb(M, G.kfs, G.ck, G.cl, G.cmp, G.pos, G.cpx, vis, proj, ok, out, sl);
-}
-void fdp_speculate_mp(FdpMemo &M, Frame *curr, const std::vector<Frame *> &batch)
-{
-    struct Clock { double &acc; std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-                   ~Clock() { acc += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); } } clock_{ M.st.speculate_ms };
-    FdpMemo::Gathered G;
-    fdp_gather(M, curr, batch, true, G);
-    fdp_launch(M, curr, G, false);
-}
-// the queued launch, waited for and turned into table entries (first look-up of the frame)
-void fdp_collect(FdpMemo &M)
-{
-    struct Clock { double &acc; std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-                   ~Clock() { acc += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); } } clock_{ M.st.speculate_ms };
-    FdpMemo::Pending &P = M.pend;
-    const int n = P.n;
-    P.n = 0;
-    if (n <= 0) return;
-    std::vector<uint8_t> vis(n), ok(n); std::vector<double> proj(2 * (size_t)n), out(2 * (size_t)n); std::vector<int32_t> sl(n);
-    if (ygz_hip_find_direct_projection_mp_end(hip::Runtime::Get().ctx(), n, vis.data(), proj.data(), ok.data(), out.data(), sl.data()) != YGZ_OK) {
-        M.refs.resize(P.first_ref);                                    // (another _begin took its place, or the run failed): nothing learnt
-        return;
-    }
-    if (P.ent.size() == (size_t)n && M.entries.empty()) {              // entries and table were prepared with the gather: the answers go in, the table is adopted
-        M.st.launches++; M.st.speculated += n;
-        for (int i = 0; i < n; ++i) {
-            if (!vis[i]) continue;                                     // FindCandidates drops it (LocalMapping.cpp:60-63): nobody asks; its prediction stays NaN
-            FdpMemo::Entry &e = P.ent[i];
-            e.px_in[0] = proj[2 * i]; e.px_in[1] = proj[2 * i + 1];
-            e.px_out[0] = out[2 * i]; e.px_out[1] = out[2 * i + 1]; e.sl = sl[i]; e.ok = ok[i];
-        }
-        M.entries.swap(P.ent); M.table.swap(P.tab);
-        return;
-    }
-    fdp_absorb(M, P.kfs, P.ck, P.cl, P.cmp, P.pos, P.cpx, vis, proj, ok, out, sl);
-}
-// Queue the frame's speculative launch as soon as its pose is known -- the end of Matcher::SparseImageAlignment -- when the previous current frame was
-// served per candidate (an unchanged caller: Tracker -> LocalMapping::TrackLocalMap, LocalMapping.cpp:24-33).  LocalMapping::FindCandidates (0.2 ms of the
-// caller's std::map work per frame) then runs while the device evaluates the candidates; a caller that changes the pose afterwards, or asks about other
-// keyframes, falls back to the launch at its first call as before.
-// the wait hook of Matcher::SparseImageAlignment (called by ygz_hip_sparse_align between its launch and its wait): the gather of the launch that follows,
-// which does not depend on the pose being estimated
-void fdp_pregather_hook(void *user)
-{
-    FdpMemo &M = fdp_memo();
-    Frame *curr = static_cast<Frame *>(user);
-    struct Clock { double &acc; std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-                   ~Clock() { acc += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); } } clock_{ M.st.speculate_ms };
-    M.pre.valid = false; M.pre.curr = curr; M.pre.batch = M.asked;
-    fdp_gather(M, curr, M.pre.batch, false, M.pre);
-    fdp_prebuild(M.pre);
-    M.pre.valid = true;
-}
-bool fdp_prelaunch_wanted(Frame *curr)
-{
-    FdpMemo &M = fdp_memo();
-    return M.enabled && M.prelaunch && !M.bypass && !M.asked.empty() && !M.valid_for(curr);
-}
-void fdp_prelaunch(Frame *curr)
-{
-    FdpMemo &M = fdp_memo();
-    if (!fdp_prelaunch_wanted(curr)) { M.pre.valid = false; return; }
-    struct Clock { double &acc; std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-                   ~Clock() { acc += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); } } clock_{ M.st.speculate_ms };
-    M.begin(curr);
-    if (!(M.pre.valid && M.pre.curr == curr && M.pre.batch == M.asked_prev)) { fdp_gather(M, curr, M.asked_prev, false, M.pre); fdp_prebuild(M.pre); }   // (the hook did not run: now)
-    M.pre.valid = false;
-    fdp_launch(M, curr, M.pre, true);
-}
-// Feature overload: the pairs the same Matcher's last SearchForTriangulation(ref, curr, ...) returned, with the depth and prediction
-// LocalMapping::CreateNewMapPoints forms from them before it calls (src/Module/LocalMapping.cpp:405-447): both features without a map point, rays not
-// parallel (cos < 0.9998), DepthFromTriangulation(T12^-1, pt1, pt2) positive -> fea1->_depth = depth1, prediction = fea2->_pixel.  One launch; a call is
-// answered only if its feature, depth and prediction equal the speculated ones bit for bit.
-void fdp_speculate_feat(FdpMemo &M, Frame *ref, Frame *curr, const vector<pair<int, int>> &pairs)
-{
-    struct Clock { double &acc; std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-                   ~Clock() { acc += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); } } clock_{ M.st.speculate_ms };
-    hip::Runtime &rt = hip::Runtime::Get();
-    PinholeCamera *cam = Frame::_camera;
-    FdpMemo::Ref R; R.f = ref; ref->_TCW.to7(R.T);
-    M.feat_refs.push_back(R);
-    if (!cam || pairs.empty() || ref->_pyramid.empty() || curr->_pyramid.empty()) return;
-    const int levels = curr->_option._pyramid_level;
-    const SE3 T12 = ref->_TCW * curr->_TCW.inverse(), T21 = T12.inverse();
-    std::vector<const Feature *> cf; std::vector<double> pr, dep, pc; std::vector<int32_t> lvl;
-    for (const auto &pq : pairs) {
-        if (pq.first < 0 || pq.second < 0 || pq.first >= (int)ref->_features.size() || pq.second >= (int)curr->_features.size()) continue;
-        const Feature *fea1 = ref->_features[pq.first], *fea2 = curr->_features[pq.second];
-        if (fea1->_mappoint || fea2->_mappoint || fea1->_level < 0 || fea1->_level >= levels) continue;
-        const Vector3d pt1 = cam->Pixel2Camera(fea1->_pixel), pt2 = cam->Pixel2Camera(fea2->_pixel);
-        if (pt1.dot(pt2) / (pt1.norm() * pt2.norm()) >= 0.9998) continue;
-        double d1 = 0, d2 = 0;
-        if (!cvutils::DepthFromTriangulation(T21, pt1, pt2, d1, d2) || d1 < 0 || d2 < 0) continue;
-        cf.push_back(fea1); dep.push_back(d1); lvl.push_back(fea1->_level);
-        pr.push_back(fea1->_pixel[0]); pr.push_back(fea1->_pixel[1]); pc.push_back(fea2->_pixel[0]); pc.push_back(fea2->_pixel[1]);
-    }
-    const int n = (int)cf.size();
-    if (n == 0) return;
-    ygz_align_pair pair;
-    pair.ref_slot = rt.Resident(ref); pair.cur_slot = rt.Resident(curr);
-    if (ref->_hip_slot != pair.ref_slot || pair.ref_slot < 0 || pair.cur_slot < 0) return;
-    memcpy(pair.T_ref, R.T, 56); memcpy(pair.T_cur, M.T_cur, 56);
-    std::vector<double> out = pc; std::vector<int32_t> sl(n); std::vector<uint8_t> ok(n);
-    if (ygz_hip_find_direct_projection(rt.ctx(), &pair, pr.data(), dep.data(), lvl.data(), out.data(), sl.data(), ok.data(), n) != YGZ_OK) return;
-    M.st.launches++; M.st.speculated += n;
-    for (int i = 0; i < n; ++i) {
-        FdpMemo::Entry e;
-        e.ref = ref; e.key = cf[i];
-        e.a[0] = dep[i]; e.a[1] = e.a[2] = 0;
-        e.px_ref[0] = pr[2 * i]; e.px_ref[1] = pr[2 * i + 1]; e.level = lvl[i];
-        e.px_in[0] = pc[2 * i]; e.px_in[1] = pc[2 * i + 1];
-        e.px_out[0] = out[2 * i]; e.px_out[1] = out[2 * i + 1]; e.sl = sl[i]; e.ok = ok[i];
-        M.entries.push_back(e);
-    }
-    M.rebuild_table();
-}
-}  // namespace
-
 int Matcher::FindDirectProjectionBatch(Frame *ref, Frame *curr, const vector<Feature *> &feas, vector<Vector2d> &px_curr,
                                        vector<int> &search_level, vector<bool> &ok)
 {
@@ -1114,24 +804,11 @@ int Matcher::FindDirectProjectionBatch(Frame *ref, Frame *curr, const vector<Fea
 
 bool Matcher::FindDirectProjection(Frame *ref, Frame *curr, Feature *fea_ref, Vector2d &px_curr, int &search_level)
 {   // Matcher.cpp:385-417.  Called once per matched pair by LocalMapping::CreateNewMapPoints (:447): answered from one launch over the pairs of this
-    // object's last SearchForTriangulation(ref, curr, ...) when every input equals the speculated one bit for bit (FdpMemo above), else n = 1
+    // object's last SearchForTriangulation(ref, curr, ...) when every input equals the speculated one bit for bit (fdp_memo.cpp), else n = 1
     if (fea_ref->_depth < 0) { LOG(WARNING) << "invalid depth: " << fea_ref->_depth << endl; return false; }
     assert(fea_ref->_frame == ref);
-    FdpMemo &M = fdp_memo();
-    if (M.enabled && !M.bypass && ref == _tri_kf1 && curr == _tri_kf2) {
-        if (!M.valid_for(curr)) M.begin(curr);
-        const FdpMemo::Ref *R = M.feat_ref_of(ref);
-        if (R && !same7(ref->_TCW, R->T)) { Frame *c = curr; M.clear(); M.curr = c; c->_TCW.to7(M.T_cur); R = nullptr; }
-        if (!R) fdp_speculate_feat(M, ref, curr, _tri_pairs);
-        const FdpMemo::Entry *e = M.find(ref, fea_ref);
-        if (e && e->a[0] == fea_ref->_depth && e->px_ref[0] == fea_ref->_pixel[0] && e->px_ref[1] == fea_ref->_pixel[1] && e->level == fea_ref->_level
-              && e->px_in[0] == px_curr[0] && e->px_in[1] == px_curr[1]) {
-            M.st.hits++;
-            px_curr = Vector2d(e->px_out[0], e->px_out[1]); search_level = e->sl;
-            return e->ok != 0;
-        }
-        M.st.single++;
-    }
+    bool answered_ok = false;
+    if (ref == _tri_kf1 && curr == _tri_kf2 && hip::Runtime::Get().Fdp().answer_feat(ref, curr, fea_ref, _tri_pairs, px_curr, search_level, answered_ok)) return answered_ok;
     vector<Vector2d> px(1, px_curr); vector<int> sl; vector<bool> ok;
     FindDirectProjectionBatch(ref, curr, vector<Feature *>(1, fea_ref), px, sl, ok);
     px_curr = px[0]; search_level = sl[0];
@@ -1140,38 +817,14 @@ bool Matcher::FindDirectProjection(Frame *ref, Frame *curr, Feature *fea_ref, Ve
 
 bool Matcher::FindDirectProjection(Frame *ref, Frame *curr, MapPoint *mp, Vector2d &px_curr, int &search_level)
 {   // Matcher.cpp:356-383.  The reference does not test the sign of the depth in this overload; neither does the kernel (k_lmap_match)
-    Feature *fea = mp->_obs[ref->_keyframe_id];
-    if (!fea) {                                               // (the reference dereferences the null operator[] just inserted, Matcher.cpp:361: defined here as "no projection")
+    const auto it = mp->_obs.find(ref->_keyframe_id);
+    const Feature *fea = it == mp->_obs.end() ? nullptr : it->second;
+    if (!fea) {       // (the reference's mp->_obs[ref->_keyframe_id] inserts a null and dereferences it, Matcher.cpp:361: "no projection" here, _obs as it was)
         LOG(WARNING) << "Matcher::FindDirectProjection: map point " << mp->_id << " has no observation in keyframe " << ref->_keyframe_id << endl;
         return false;
     }
-    FdpMemo &M = fdp_memo();
-    if (M.enabled && !M.bypass) {
-        if (!M.valid_for(curr)) M.begin(curr);
-        if (M.pend.n) fdp_collect(M);                                   // the launch Matcher::SparseImageAlignment queued for this frame
-        M.note_asked(ref);
-        for (int pass = 0; pass < 2; ++pass) {
-            const FdpMemo::Ref *R = M.ref_of(ref);
-            if (R && !same7(ref->_TCW, R->T)) { Frame *c = curr; M.clear(); M.curr = c; c->_TCW.to7(M.T_cur); R = nullptr; }   // the keyframe moved (local BA)
-            if (R) {
-                const FdpMemo::Entry *e = M.find(ref, mp);
-                if (e && e->a[0] == mp->_pos_world[0] && e->a[1] == mp->_pos_world[1] && e->a[2] == mp->_pos_world[2]
-                      && e->px_ref[0] == fea->_pixel[0] && e->px_ref[1] == fea->_pixel[1] && e->level == fea->_level
-                      && e->px_in[0] == px_curr[0] && e->px_in[1] == px_curr[1]) {
-                    M.st.hits++;
-                    px_curr = Vector2d(e->px_out[0], e->px_out[1]); search_level = e->sl;
-                    return e->ok != 0;
-                }
-                break;                                                  // covered keyframe, unknown or changed candidate: n = 1
-            }
-            if (pass == 0) {
-                std::vector<Frame *> batch(1, ref);
-                if (M.refs.empty()) batch.insert(batch.end(), M.asked_prev.begin(), M.asked_prev.end());
-                fdp_speculate_mp(M, curr, batch);
-            }
-        }
-        M.st.single++;
-    }
+    bool answered_ok = false;
+    if (hip::Runtime::Get().Fdp().answer_mp(ref, curr, mp, fea, px_curr, search_level, answered_ok)) return answered_ok;
     hip::Runtime &rt = hip::Runtime::Get();
     const int32_t kf_slot = rt.Resident(ref), cs = rt.Resident(curr), ck = 0, lvl = fea->_level;
     double Tr[7], Tc[7]; ref->_TCW.to7(Tr); curr->_TCW.to7(Tc);
@@ -1249,20 +902,22 @@ bool Matcher::SparseImageAlignment(Frame *ref, Frame *current)
 {
     current->_TCW = ref->_TCW;
     // (an unchanged caller's next step is LocalMapping::TrackLocalMap: the candidates of its speculative FindDirectProjection launch are gathered while
-    // the alignment kernel runs and the launch is queued as soon as the pose is known -- fdp_prelaunch)
-    const bool pre = fdp_prelaunch_wanted(current);
-    if (pre) ygz_hip_set_wait_hook(hip::Runtime::Get().ctx(), &fdp_pregather_hook, current);
-    _align->run(ref, current);
-    if (pre) ygz_hip_set_wait_hook(hip::Runtime::Get().ctx(), nullptr, nullptr);
+    // the alignment kernel runs and the launch is queued as soon as the pose is known -- FdpMemo::prelaunch)
+    hip::FdpMemo &M = hip::Runtime::Get().Fdp();
+    {
+        struct WaitHook { ygz_hip_ctx *c = nullptr; ~WaitHook() { if (c) ygz_hip_set_wait_hook(c, nullptr, nullptr); } } hook;     // disarmed on every exit
+        if (M.prelaunch_wanted(current)) { hook.c = hip::Runtime::Get().ctx(); ygz_hip_set_wait_hook(hook.c, &hip::FdpMemo::pregather_hook, current); }
+        _align->run(ref, current);
+    }
     _TCR_esti = current->_TCW * ref->_TCW.inverse();
     if (_TCR_esti.log().norm() > _options._max_alignment_motion) {
         LOG(WARNING) << "Too large motion: " << _TCR_esti.log().norm() << ". Reject this estimation. " << endl;
         _TCR_esti = SE3();
         current->_TCW = ref->_TCW;
-        fdp_prelaunch(current);
+        M.prelaunch(current);
         return false;
     }
-    fdp_prelaunch(current);
+    M.prelaunch(current);
     return true;
 }
 
