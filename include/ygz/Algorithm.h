@@ -7,4 +7,5 @@
 #include "ygz/Algorithm/CVUtils.h"
 #include "ygz/Algorithm/BA.h"
 #include "ygz/Algorithm/Initializer.h"
+#include "ygz/Algorithm/Relocalizer.h"
 #endif

@@ -1,0 +1,54 @@
+// ygz/Algorithm/Relocalizer.h -- ygz::Relocalizer: the way out of VO_LOST.  Nothing in the reference: it fills the stub at
+// src/Module/VisualOdometry.cpp:101-104 ("try relocalization"), in the manner of ORB-SLAM2's Tracking::Relocalization -- BoW keyframe
+// retrieval, Matcher::SearchByBoW against each candidate, P3P RANSAC of all candidates in one device call (ygz_hip_pnp_ransac), then
+// ba::OptimizeCurrentPoseOnly on the inliers (ygz_slam_amd/host/ygz_reloc.cpp; the integration is in INTEGRATION.md).
+#ifndef YGZ_RELOCALIZER_H_
+#define YGZ_RELOCALIZER_H_
+
+#include "ygz/Basic.h"
+#include "ygz/Algorithm/FeatureDetector.h"
+#include "ygz/Algorithm/Matcher.h"
+
+namespace ygz
+{
+
+class Relocalizer
+{
+public:
+    struct Option
+    {
+        int _max_candidates = 5;            // keyframes tried, best BoW score first (at most YGZ_PNP_MAX_PROBLEMS)
+        double _min_score_ratio = 0.75;     // a candidate scores at least this fraction of the best score (and above 0)
+        int _min_bow_matches = 15;          // SearchByBoW matches with a map point that a candidate needs
+        int _ransac_iterations = 300;       // ORB-SLAM2 Tracking::Relocalization's values
+        double _ransac_chi2 = 5.991;
+        int _min_ransac_inliers = 10;
+        int _min_final_inliers = 50;        // features left after the pose-only BA
+        float _knn_ratio = 0.75f;           // SearchByBoW's ratio (the Matcher's own reads matcher.knnRatio through Get<int>: 0)
+    } _option;
+
+    struct Stats
+    {
+        int candidates = 0, pnp_problems = 0, ransac_inliers = 0, final_inliers = 0;
+        vector<int> bow_matches;            // per candidate, in candidate order
+    };
+
+    // current: a frame after InitFrame() that holds no features yet; true when its pose was recovered against one of the keyframes.  On
+    // success current->_features are the RANSAC inliers (map point set, after the pose-only BA), _TCW the refined pose and _ref_keyframe
+    // the keyframe; on failure the features, _TCW and the map are as they were.  _bow_vec / _feature_vec are left empty in every case.
+    bool Relocalize(Frame *current, const vector<Frame *> &keyframes);
+    bool Relocalize(Frame *current);        // every keyframe registered in Memory
+
+    Frame *GetMatchedKeyframe() const { return _matched; }
+    const Stats &GetStats() const { return _stats; }
+
+private:
+    FeatureDetector _detector;
+    Matcher _matcher;
+    Frame *_matched = nullptr;
+    Stats _stats;
+};
+
+}
+
+#endif // YGZ_RELOCALIZER_H_

@@ -254,7 +254,12 @@ public:
     bool empty() const { return n_words_ == 0; }
     // Vocabulary::transform(features, BowVector, FeatureVector, levelsup), Vocabulary.cpp:706-774
     void transform(const std::vector<cv::Mat> &features, BowVector &v, FeatureVector &fv, int levelsup) const;
+    // Vocabulary::score(a, b) with L1Scoring::score (ScoringObject.cpp:23-67): the merge over word ids of the L1-normalised vectors that
+    // transform produces, -0.5 * sum(|v - w| - |v| - |w|), in [0, 1].  Only the L1_NORM scoring type (0 in the file header, what an ORB
+    // vocabulary carries) is served: a vocabulary of any other scoring type logs an error and scores 0.
+    double score(const BowVector &a, const BowVector &b) const;
     int k_ = 0, L_ = 0, n_nodes_ = 0, n_words_ = 0;
+    int scoring_ = 0;                                           // the header's scoring type (0 = L1_NORM)
 };
 }  // namespace DBoW3
 typedef DBoW3::Vocabulary ORBVocabulary;

@@ -13,6 +13,7 @@ public:
     static MapPoint *CreateMapPoint();                                      // src/Basic/Memory.cpp:45-52
     static Frame *GetKeyFrame(const unsigned long &keyframe_id);
     static MapPoint *GetMapPoint(const unsigned long &id);
+    static int GetNumberFrames();                                           // registered keyframes (Memory.h:38)
     static void Clean();                                                    // forgets (does not delete)
 };
 }

@@ -42,7 +42,9 @@ extern "C" {
  * gained their trailing int (round 4); ygz_hip_get_stream / device_alloc / copy added (round 5).  6: ygz_ceres_options gained trust_region_strategy
  * (in the struct's tail padding: same size); ygz_hip_find_direct_projection_mp (+ _begin / _end), ygz_hip_sparse_align_residuals, ygz_hip_ba_light_barrier added (round 6).
  * Still 6: the monocular Initializer added (ygz_init_params, ygz_init_result, ygz_hip_default_init_params, ygz_hip_initialize,
- * ygz_hip_init_sample_sets, ygz_hip_init_hypotheses, ygz_hip_init_reconstruct) -- no existing argument list changed. */
+ * ygz_hip_init_sample_sets, ygz_hip_init_hypotheses, ygz_hip_init_reconstruct) -- no existing argument list changed.
+ * Still 6: the relocalisation's PnP RANSAC added (ygz_pnp_params, ygz_pnp_result, ygz_hip_default_pnp_params, ygz_hip_pnp_sample_sets,
+ * ygz_hip_pnp_ransac, ygz_hip_pnp_hypotheses) -- no existing argument list changed. */
 #define YGZ_HIP_ABI_VERSION 6
 
 typedef struct ygz_hip_ctx ygz_hip_ctx;
@@ -653,6 +655,43 @@ int  ygz_hip_init_hypotheses(ygz_hip_ctx *ctx, const double *px1, const double *
 int  ygz_hip_init_reconstruct(ygz_hip_ctx *ctx, const double *px1, const double *px2, int n, const double K4[4], const ygz_init_params *params,
                               int model, const double M[9], const uint8_t *inliers, ygz_init_result *result, double *pts3d_out,
                               uint8_t *triangulated_out);
+
+
+/* ---- relocalisation: 2D-3D pose by P3P RANSAC -- nothing in the reference; it fills the stub at src/Module/VisualOdometry.cpp:101-104
+ * ("try relocalization"), as ORB-SLAM2's Tracking::Relocalization does.  Several independent problems per call, one per candidate keyframe:
+ * problem p owns the correspondences offsets[p] .. offsets[p+1]-1, a world point pw [N][3] and a level-0 pixel px [N][2] each.  Per problem
+ * the sample sets of (n, max_iter) (3 indices per iteration, cv::RNG's scheme of Initializer.cpp:33-49), Lambda Twist P3P with up to 4
+ * solutions per sample, the inlier count of every (sample, solution) hypothesis (z > 0 and squared reprojection error <= chi2), the highest
+ * count (ties: smallest sample * 4 + solution).  The arithmetic is that of tests/pnp_ref.c: every output is
+ * bit-identical to it. */
+#define YGZ_PNP_MAX_ITER     1024         /* bound of max_iter */
+#define YGZ_PNP_MAX_PROBLEMS 64           /* problems per call */
+typedef struct {                          /* ORB-SLAM2 Tracking::Relocalization's values */
+    int    max_iter;                      /* 300 */
+    double chi2;                          /* 5.991: squared level-0 pixel error of an inlier (OptimizeCurrentPoseOnly's threshold) */
+    int    min_inliers;                   /* 10 */
+} ygz_pnp_params;
+typedef struct {
+    double  R[9], t[3];                   /* the winner: camera = R world + t (row-major); I / 0 when no hypothesis has an inlier */
+    double  T_cw[7];                      /* SE3(R, t) as qx qy qz qw tx ty tz (Sophus SO3(const Matrix3d &)) */
+    int32_t success;                      /* n_inliers >= min_inliers */
+    int32_t n_inliers;                    /* inliers of the winner */
+    int32_t best_sample, best_solution;   /* the winner (-1 / -1: every hypothesis scored 0) */
+    int32_t n_hypotheses;                 /* real solutions over all samples */
+} ygz_pnp_result;
+void ygz_hip_default_pnp_params(ygz_pnp_params *p);
+/* the sample sets [max_iter][3] of a problem of n correspondences (host only, no context: they depend on n and max_iter alone) */
+int  ygz_hip_pnp_sample_sets(int n, int max_iter, int32_t *sets);
+/* the fused call: K4 = fx fy cx cy, params NULL: defaults; results [n_problems], inliers [N] (may be NULL).  One upload, the launches, one
+ * copy back and one wait.  YGZ_E_INVALID: a null context or array, n_problems < 1, offsets not starting at 0, a problem of fewer than 4
+ * correspondences, max_iter outside [1, YGZ_PNP_MAX_ITER], chi2 <= 0; YGZ_E_CAPACITY: more than YGZ_PNP_MAX_PROBLEMS problems or a problem
+ * larger than ygz_hip_max_keypoints -- all before the device is touched. */
+int  ygz_hip_pnp_ransac(ygz_hip_ctx *ctx, int n_problems, const int32_t *offsets, const double *pw, const double *px, const double K4[4],
+                        const ygz_pnp_params *params, ygz_pnp_result *results, uint8_t *inliers);
+/* stage for tests: every hypothesis of ONE problem -- solutions [max_iter][4][12] (R row-major, t; 0 past n_solutions), n_solutions
+ * [max_iter], counts [max_iter][4] (0 past n_solutions); each may be NULL */
+int  ygz_hip_pnp_hypotheses(ygz_hip_ctx *ctx, const double *pw, const double *px, int n, const double K4[4], const ygz_pnp_params *params,
+                            double *solutions, int32_t *n_solutions, int32_t *counts);
 
 #ifdef __cplusplus
 }

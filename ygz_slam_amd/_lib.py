@@ -126,6 +126,43 @@ def init_sample_sets(n, max_iter=200):
     return s
 
 
+class PnpParams(C.Structure):
+    _fields_ = [("max_iter", C.c_int), ("chi2", C.c_double), ("min_inliers", C.c_int)]
+
+
+class PnpResult(C.Structure):
+    _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("T_cw", C.c_double * 7), ("success", C.c_int32), ("n_inliers", C.c_int32),
+                ("best_sample", C.c_int32), ("best_solution", C.c_int32), ("n_hypotheses", C.c_int32)]
+
+    def to_dict(self):
+        return InitResult.to_dict(self)
+
+
+def default_pnp_params():
+    p = PnpParams()
+    load().ygz_hip_default_pnp_params(C.byref(p))
+    return p
+
+
+def _pnp_params(**kw):
+    p = default_pnp_params()
+    for k, v in kw.items():
+        if v is not None:
+            setattr(p, k, v)
+    return p
+
+
+def pnp_sample_sets(n, max_iter=300):
+    """the 3-point sample sets of the relocalisation's P3P RANSAC (Initializer.cpp:33-49's scheme): [max_iter][3], host only"""
+    s = np.zeros((max(max_iter, 1), 3), np.int32)
+    lib = load()
+    lib.ygz_hip_pnp_sample_sets.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int32)]
+    rc = lib.ygz_hip_pnp_sample_sets(n, max_iter, _p(s, C.c_int32))
+    if rc != OK:
+        raise YgzHipError(rc, "pnp_sample_sets")
+    return s
+
+
 # every symbol include/ygz_hip.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
     "ygz_hip_default_params", "ygz_hip_create", "ygz_hip_destroy", "ygz_hip_synchronize", "ygz_hip_join", "ygz_hip_set_overlap", "ygz_hip_error_string",
@@ -149,9 +186,12 @@ ABI_SYMBOLS = [
     "ygz_hip_kf_store_set_trel", "ygz_hip_kf_store_refresh", "ygz_hip_ba_reserve_windows", "ygz_hip_ba_build_windows", "ygz_hip_ba_pack_states", "ygz_hip_ba_mark_outliers", "ygz_hip_ba_get_outlier_stats", "ygz_hip_bow_orientation", "ygz_hip_bow_orientation_slots", "ygz_hip_ba_last_path",
     "ygz_hip_abi_version", "ygz_hip_ba_optimize_chi2", "ygz_hip_ba_set_team_placement", "ygz_hip_get_stream", "ygz_hip_get_device", "ygz_hip_make_current", "ygz_hip_device_alloc", "ygz_hip_device_free", "ygz_hip_copy",
     "ygz_hip_default_init_params", "ygz_hip_initialize", "ygz_hip_init_sample_sets", "ygz_hip_init_hypotheses", "ygz_hip_init_reconstruct",
+    "ygz_hip_default_pnp_params", "ygz_hip_pnp_sample_sets", "ygz_hip_pnp_ransac", "ygz_hip_pnp_hypotheses",
 ]
 INIT_SYMBOLS = ["ygz_hip_default_init_params", "ygz_hip_initialize", "ygz_hip_init_sample_sets", "ygz_hip_init_hypotheses", "ygz_hip_init_reconstruct"]
 INIT_NONE, INIT_H, INIT_F = 0, 1, 2
+PNP_SYMBOLS = ["ygz_hip_default_pnp_params", "ygz_hip_pnp_sample_sets", "ygz_hip_pnp_ransac", "ygz_hip_pnp_hypotheses"]
+PNP_MAX_ITER, PNP_MAX_PROBLEMS = 1024, 64
 
 SUMMARY_FIELDS = 32
 
@@ -936,6 +976,45 @@ class HipContext:
         d = res.to_dict()
         d["pts3d"], d["triangulated"] = p3d[:n], tri[:n].astype(bool)
         return d
+
+    # ---- relocalisation pose (P3P RANSAC)
+
+    def pnp_ransac(self, pw, px, offsets, K4, **params):
+        """every problem p of offsets [P + 1] (correspondences offsets[p] .. offsets[p+1]-1 of pw [N][3], px [N][2]) in one call
+        (ygz_hip_pnp_ransac): a list of result dicts and the inlier mask [N] (bool).  params: max_iter, chi2, min_inliers"""
+        pw = np.ascontiguousarray(pw, np.float64).reshape(-1, 3)
+        px = np.ascontiguousarray(px, np.float64).reshape(-1, 2)
+        off = np.ascontiguousarray(offsets, np.int32).reshape(-1)
+        if len(pw) != len(px):
+            raise ValueError("pw and px differ in length")
+        P = len(off) - 1
+        K = (C.c_double * 4)(*[float(v) for v in K4])
+        prm = _pnp_params(**params)
+        res = (PnpResult * max(P, 1))()
+        inl = np.zeros(max(len(pw), 1), np.uint8)
+        self.lib.ygz_hip_pnp_ransac.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                                C.POINTER(C.c_double), C.POINTER(PnpParams), C.POINTER(PnpResult), C.POINTER(C.c_uint8)]
+        self._chk(self.lib.ygz_hip_pnp_ransac(self._ctx, P, _p(off, C.c_int32), _p(pw, C.c_double), _p(px, C.c_double), K, C.byref(prm),
+                                              res, _p(inl, C.c_uint8)), "pnp_ransac")
+        return [res[i].to_dict() for i in range(P)], inl[:len(pw)].astype(bool)
+
+    def pnp_hypotheses(self, pw, px, K4, **params):
+        """every hypothesis of one problem (ygz_hip_pnp_hypotheses): solutions [max_iter][4][12] (R row-major, t), n_solutions [max_iter],
+        counts [max_iter][4]"""
+        pw = np.ascontiguousarray(pw, np.float64).reshape(-1, 3)
+        px = np.ascontiguousarray(px, np.float64).reshape(-1, 2)
+        if len(pw) != len(px):
+            raise ValueError("pw and px differ in length")
+        n = len(pw)
+        K = (C.c_double * 4)(*[float(v) for v in K4])
+        prm = _pnp_params(**params)
+        it = max(prm.max_iter, 1)
+        sol, ns, cnt = np.zeros((it, 4, 12)), np.zeros(it, np.int32), np.zeros((it, 4), np.int32)
+        self.lib.ygz_hip_pnp_hypotheses.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double),
+                                                    C.POINTER(PnpParams), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        self._chk(self.lib.ygz_hip_pnp_hypotheses(self._ctx, _p(pw, C.c_double), _p(px, C.c_double), n, K, C.byref(prm), _p(sol, C.c_double),
+                                                  _p(ns, C.c_int32), _p(cnt, C.c_int32)), "pnp_hypotheses")
+        return dict(solutions=sol, n_solutions=ns, counts=cnt)
 
     # ---- BoW
     def vocab_load(self, blob):

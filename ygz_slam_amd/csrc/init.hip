@@ -16,6 +16,7 @@
 #include <cstring>
 #include <mutex>
 #include <map>
+#include <tuple>
 #include <vector>
 
 #define INIT_MODEL_LANES 32                 // k_init_models: lanes per block (the DLT system and V of a lane: 225 doubles of LDS)
@@ -694,34 +695,39 @@ __global__ __launch_bounds__(256) void k_init_accept(InitDev D)
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------------
-// cv::RNG (OpenCV core/operations.hpp): default state 0xffffffff, next() multiply-with-carry, uniform(int a, int b) = next() % (b - a) + a
-void sample_sets(int n, int max_iter, int32_t *sets)
+}  // namespace
+
+// cv::RNG (OpenCV core/operations.hpp): default state 0xffffffff, next() multiply-with-carry, uniform(int a, int b) = next() % (b - a) + a.
+// TryInitialize :33-48 draws k = 8 indices per iteration; the relocalisation's P3P (pnp.hip) draws k = 3 by the same scheme.
+void ygz_cvrng_sample_sets(int n, int max_iter, int k, int32_t *sets)
 {
     uint64_t st = 0xffffffffu;
     std::vector<int32_t> avail(n);
     for (int it = 0; it < max_iter; ++it) {
         int na = n;
         for (int i = 0; i < n; ++i) avail[i] = i;
-        for (int j = 0; j < 8; ++j) {                        // TryInitialize :33-48
+        for (int j = 0; j < k; ++j) {
             st = (uint64_t)(uint32_t)st * 4164903690u + (uint32_t)(st >> 32);
             const int r = (int)((uint32_t)st % (uint32_t)na);
-            sets[it * 8 + j] = avail[r];
+            sets[it * k + j] = avail[r];
             avail[r] = avail[na - 1];
             --na;
         }
     }
 }
 
-// the sets depend on (n, max_iter) only: drawn once per pair and kept
-const std::vector<int32_t> &cached_sets(int n, int max_iter)
+// the sets depend on (n, max_iter, k) only: drawn once per triple and kept
+const std::vector<int32_t> &ygz_cvrng_cached_sets(int n, int max_iter, int k)
 {
     static std::mutex mu;
-    static std::map<std::pair<int, int>, std::vector<int32_t>> cache;
+    static std::map<std::tuple<int, int, int>, std::vector<int32_t>> cache;
     std::lock_guard<std::mutex> lk(mu);
-    auto &v = cache[{ n, max_iter }];
-    if (v.empty()) { v.resize((size_t)max_iter * 8); sample_sets(n, max_iter, v.data()); }
+    auto &v = cache[std::make_tuple(n, max_iter, k)];
+    if (v.empty()) { v.resize((size_t)max_iter * k); ygz_cvrng_sample_sets(n, max_iter, k, v.data()); }
     return v;
 }
+
+namespace {
 
 size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
 
@@ -809,7 +815,7 @@ int run(ygz_hip_ctx *ctx, const double *px1, const double *px2, int n, const dou
     memcpy(up + L.in, &in, sizeof in);
     memcpy(up + L.px1, px1, (size_t)n * 16);
     memcpy(up + L.px2, px2, (size_t)n * 16);
-    if (what & RUN_HYP) memcpy(up + L.sets, cached_sets(n, it).data(), (size_t)it * 32);
+    if (what & RUN_HYP) memcpy(up + L.sets, ygz_cvrng_cached_sets(n, it, 8).data(), (size_t)it * 32);
     if (inl_in) memcpy(up + L.inl_in, inl_in, (size_t)n);
     const size_t up_bytes = inl_in ? L.in_end : L.inl_in;
     YGZ_HIPCHK(ctx, hipMemcpyAsync(dev, up, up_bytes, hipMemcpyHostToDevice, ctx->stream));
@@ -850,7 +856,7 @@ void ygz_hip_default_init_params(ygz_init_params *p)
 int ygz_hip_init_sample_sets(int n, int max_iter, int32_t *sets)
 {
     if (n < 8 || max_iter < 1 || max_iter > YGZ_INIT_MAX_ITER || !sets) return YGZ_E_INVALID;
-    sample_sets(n, max_iter, sets);
+    ygz_cvrng_sample_sets(n, max_iter, 8, sets);
     return YGZ_OK;
 }
 

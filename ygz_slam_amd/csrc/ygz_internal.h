@@ -10,7 +10,7 @@
 // the tracker's working images: every level inside a reflect-101 frame of KLT_B pixels (klt.hip; written by the pyramid kernels, image.hip)
 #define KLT_B      24          // >= window + 1, multiple of 4
 #define KLT_PW(w)  (((w) + 2 * KLT_B + 3) & ~3)      // framed row pitch, 4-byte aligned for any level width
-#define YGZ_N_SCRATCH  28
+#define YGZ_N_SCRATCH  29
 
 struct ygz_hip_ctx {
     ygz_hip_params prm;
@@ -194,6 +194,10 @@ enum { SCR_MATCH_Q = 0, SCR_MATCH_T, SCR_ALIGN_IN, SCR_ALIGN_OUT, SCR_SA_IN, SCR
        SCR_KLT_PTS, SCR_KLT_OUT, SCR_BA_0, SCR_BOW, SCR_LMAP, SCR_WIN, SCR_GEN_0 = 16 };
 
 int ygz_scratch(ygz_hip_ctx *ctx, int id, size_t bytes, void **out);
+// the RANSAC sample sets of cv::RNG's scheme (init.hip): a fresh generator (state 0xffffffff), per iteration k distinct indices of [0, n) by the
+// swap-remove of Initializer.cpp:33-48; [max_iter][k].  The cached form keeps one copy per (n, max_iter, k) for the process.
+void ygz_cvrng_sample_sets(int n, int max_iter, int k, int32_t *sets);
+const std::vector<int32_t> &ygz_cvrng_cached_sets(int n, int max_iter, int k);
 // page-locked host memory of (at least) the capacity of scratch buffer `id` (call after ygz_scratch); valid until the scratch grows
 int ygz_scratch_mirror(ygz_hip_ctx *ctx, int id, void **host);
 // `bytes` of page-locked host memory that stay valid until the next ygz_hip_synchronize (nullptr: allocation failed)

@@ -304,6 +304,7 @@ MapPoint *Memory::RegisterMapPoint(MapPoint *mp) { mp->_id = g_pt_id++; g_points
 MapPoint *Memory::CreateMapPoint() { return RegisterMapPoint(new MapPoint); }      // Memory.cpp:45-52
 Frame *Memory::GetKeyFrame(const unsigned long &id) { auto it = g_keyframes.find(id); return it == g_keyframes.end() ? nullptr : it->second; }
 MapPoint *Memory::GetMapPoint(const unsigned long &id) { auto it = g_points.find(id); return it == g_points.end() ? nullptr : it->second; }
+int Memory::GetNumberFrames() { return (int)g_keyframes.size(); }
 void Memory::Clean() { g_keyframes.clear(); g_points.clear(); g_kf_id = g_pt_id = 0; }
 
 // ------------------------------------------------------------------------------------------ FeatureDetector
@@ -626,6 +627,7 @@ bool Vocabulary::loadFromMemory(const void *blob, size_t bytes)
 {
     ygz::hip::Runtime &rt = ygz::hip::Runtime::Get();
     if (ygz_hip_vocab_load(rt.ctx(), blob, bytes) != YGZ_OK) return false;
+    memcpy(&scoring_, (const uint8_t *)blob + 16, 4);            // {nb_nodes, size_node, k, L, scoring, weighting}: ygz_hip_vocab_load checked the size
     return ygz_hip_vocab_info(rt.ctx(), &k_, &L_, &n_nodes_, &n_words_) == YGZ_OK;
 }
 bool Vocabulary::loadFromBinaryFile(const std::string &filename)
@@ -655,6 +657,26 @@ void Vocabulary::transform(const std::vector<cv::Mat> &features, BowVector &v, F
     double norm = 0.0;                                           // BowVector::normalize(L1)
     for (auto &kv : v) norm += fabs(kv.second);
     if (norm > 0.0) for (auto &kv : v) kv.second /= norm;
+}
+double Vocabulary::score(const BowVector &a, const BowVector &b) const
+{   // L1Scoring::score, ScoringObject.cpp:23-67
+    if (scoring_ != 0) { LOG(ERROR) << "Vocabulary::score: scoring type " << scoring_ << " is not served (L1_NORM only)" << std::endl; return 0.0; }
+    BowVector::const_iterator v1_it = a.begin(), v2_it = b.begin();
+    const BowVector::const_iterator v1_end = a.end(), v2_end = b.end();
+    double score = 0;
+    while (v1_it != v1_end && v2_it != v2_end) {
+        const WordValue &vi = v1_it->second;
+        const WordValue &wi = v2_it->second;
+        if (v1_it->first == v2_it->first) {
+            score += fabs(vi - wi) - fabs(vi) - fabs(wi);
+            ++v1_it; ++v2_it;
+        } else if (v1_it->first < v2_it->first) {
+            v1_it = a.lower_bound(v2_it->first);
+        } else {
+            v2_it = b.lower_bound(v1_it->first);
+        }
+    }
+    return -score / 2.0;
 }
 }  // namespace DBoW3
 namespace ygz {

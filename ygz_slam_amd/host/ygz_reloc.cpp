@@ -1,0 +1,174 @@
+// ygz::Relocalizer (include/ygz/Algorithm/Relocalizer.h): nothing in the reference -- it fills the stub at src/Module/VisualOdometry.cpp:101-104
+// ("try relocalization") the way ORB-SLAM2's Tracking::Relocalization does.  Extraction, the BoW transform, SearchByBoW and the pose-only BA
+// are the existing GPU paths; the P3P RANSAC of every candidate keyframe is one ygz_hip_pnp_ransac call (ygz_slam_amd/csrc/pnp.hip).
+// Error conventions of the other surfaces: a failed call logs and returns false, only a missing device throws.
+#include "ygz/Algorithm/Relocalizer.h"
+#include "ygz/Algorithm/BA.h"
+#include "ygz/hip/Runtime.h"
+#include "ygz_hip.h"
+#include <algorithm>
+#include <cstring>
+
+namespace ygz {
+
+namespace {
+struct Candidate {
+    Frame *kf;
+    double score;
+    vector<int> cur;                      // detected feature of the current frame per correspondence
+    vector<MapPoint *> mps;               // the keyframe feature's map point per correspondence
+    ygz_pnp_result res;
+    size_t first = 0;                     // offset of its correspondences in the call
+};
+}
+
+bool Relocalizer::Relocalize(Frame *current)
+{
+    vector<Frame *> kfs;
+    const int n = Memory::GetNumberFrames();
+    for (int id = 0; id < n; ++id) {
+        Frame *kf = Memory::GetKeyFrame((unsigned long)id);
+        if (kf) kfs.push_back(kf);
+    }
+    return Relocalize(current, kfs);
+}
+
+bool Relocalizer::Relocalize(Frame *current, const vector<Frame *> &keyframes)
+{
+    _stats = Stats();
+    _matched = nullptr;
+    // 1. refuse what cannot be relocalised, touching nothing
+    if (!current || current->_hip_slot < 0 || !current->_features.empty() || Frame::_vocab == nullptr || Frame::GetCamera() == nullptr)
+        return false;
+    const SE3 T_saved = current->_TCW;
+
+    // 2. extract: FAST / ORB on the GPU, the BoW transform
+    _detector.LoadParams();
+    _detector.Detect(current);
+    _detector.ComputeAngleAndDescriptor(current);
+    current->_bow_vec.clear(); current->_feature_vec.clear();
+    current->ComputeBoW();
+    const vector<Feature *> detected = current->_features;
+    auto finish = [&](bool ok) {
+        current->_bow_vec.clear(); current->_feature_vec.clear();
+        if (!ok) {
+            for (Feature *f : current->_features) if (std::find(detected.begin(), detected.end(), f) == detected.end()) delete f;
+            for (Feature *f : detected) delete f;
+            current->_features.clear();
+            current->_TCW = T_saved;
+        }
+        return ok;
+    };
+    if (detected.empty() || current->_bow_vec.empty()) return finish(false);
+
+    // 3. candidates by BoW score: >= _min_score_ratio of the best and > 0, best first, ties by keyframe id
+    vector<Candidate> cands;
+    for (Frame *kf : keyframes) {
+        if (!kf || kf->_bad || kf == current) continue;
+        Candidate c;
+        c.kf = kf;
+        c.score = Frame::_vocab->score(current->_bow_vec, kf->_bow_vec);
+        if (c.score > 0) cands.push_back(std::move(c));
+    }
+    std::sort(cands.begin(), cands.end(), [](const Candidate &a, const Candidate &b) {
+        return a.score != b.score ? a.score > b.score : a.kf->_keyframe_id < b.kf->_keyframe_id; });
+    if (!cands.empty()) {
+        const double floor = _option._min_score_ratio * cands[0].score;
+        size_t keep = 0;
+        const size_t cap = (size_t)std::max(0, std::min(_option._max_candidates, YGZ_PNP_MAX_PROBLEMS));
+        while (keep < cands.size() && keep < cap && cands[keep].score >= floor) ++keep;
+        cands.resize(keep);
+    }
+    _stats.candidates = (int)cands.size();
+
+    // 4. SearchByBoW against each candidate; the matches whose keyframe feature has a good map point (one per current feature)
+    _matcher._options.knnRatio = _option._knn_ratio;
+    vector<Candidate> probs;
+    for (Candidate &c : cands) {
+        map<int, int> matches;
+        _matcher.SearchByBoW(c.kf, current, matches);
+        vector<char> used(detected.size(), 0);
+        for (const auto &m : matches) {
+            if (m.first < 0 || m.first >= (int)c.kf->_features.size() || m.second < 0 || m.second >= (int)detected.size() || used[m.second]) continue;
+            MapPoint *mp = c.kf->_features[m.first]->_mappoint;
+            if (!mp || mp->_bad) continue;
+            used[m.second] = 1;
+            c.cur.push_back(m.second);
+            c.mps.push_back(mp);
+        }
+        _stats.bow_matches.push_back((int)c.cur.size());
+        if ((int)c.cur.size() >= std::max(_option._min_bow_matches, 4)) probs.push_back(std::move(c));
+    }
+    _stats.pnp_problems = (int)probs.size();
+    if (probs.empty()) return finish(false);
+
+    // 5. every candidate through one P3P RANSAC call
+    vector<int32_t> off(1, 0);
+    vector<double> pw, px;
+    for (Candidate &c : probs) {
+        c.first = px.size() / 2;
+        for (size_t k = 0; k < c.cur.size(); ++k) {
+            const Vector3d &P = c.mps[k]->_pos_world;
+            const Vector2d &u = detected[c.cur[k]]->_pixel;
+            pw.push_back(P[0]); pw.push_back(P[1]); pw.push_back(P[2]);
+            px.push_back(u[0]); px.push_back(u[1]);
+        }
+        off.push_back((int32_t)(px.size() / 2));
+    }
+    const Matrix3d K = Frame::GetCamera()->GetCameraMatrix();
+    const double K4[4] = { K(0, 0), K(1, 1), K(0, 2), K(1, 2) };
+    ygz_pnp_params prm;
+    prm.max_iter = _option._ransac_iterations; prm.chi2 = _option._ransac_chi2; prm.min_inliers = _option._min_ransac_inliers;
+    vector<ygz_pnp_result> res(probs.size());
+    vector<uint8_t> inl(px.size() / 2);
+    if (!hip::check(ygz_hip_pnp_ransac(hip::Runtime::Get().ctx(), (int)probs.size(), off.data(), pw.data(), px.data(), K4, &prm, res.data(),
+                                       inl.data()), "pnp_ransac"))
+        return finish(false);
+    for (size_t p = 0; p < probs.size(); ++p) probs[p].res = res[p];
+
+    // 6. refine: most RANSAC inliers first (ties: BoW score, then candidate order); the first with _min_final_inliers after the pose-only BA
+    vector<size_t> order(probs.size());
+    for (size_t p = 0; p < order.size(); ++p) order[p] = p;
+    std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) {
+        return probs[a].res.n_inliers != probs[b].res.n_inliers ? probs[a].res.n_inliers > probs[b].res.n_inliers : probs[a].score > probs[b].score; });
+    for (size_t p : order) {
+        const Candidate &c = probs[p];
+        if (!c.res.success) continue;
+        vector<Feature *> feats;
+        for (size_t k = 0; k < c.cur.size(); ++k) {
+            if (!inl[c.first + k]) continue;
+            const Feature *d = detected[c.cur[k]];
+            Feature *f = new Feature(d->_pixel, d->_level, d->_score);
+            f->_angle = d->_angle;
+            memcpy(f->_desc.data, d->_desc.data, 32);
+            f->_frame = current;
+            f->_mappoint = c.mps[k];
+            feats.push_back(f);
+        }
+        vector<int> found(feats.size());                 // the pose-only BA counts _cnt_found on the map points: undone if this candidate fails
+        for (size_t k = 0; k < feats.size(); ++k) found[k] = feats[k]->_mappoint->_cnt_found;
+        current->_features = feats;
+        current->_TCW = SE3::from7(c.res.T_cw);
+        ba::OptimizeCurrentPoseOnly(current);
+        int good = 0;
+        for (Feature *f : current->_features) good += !f->_bad;
+        if (_stats.ransac_inliers == 0) _stats.ransac_inliers = c.res.n_inliers;
+        if (good >= _option._min_final_inliers) {
+            for (Feature *f : detected) delete f;
+            current->_ref_keyframe = c.kf;
+            _matched = c.kf;
+            _stats.ransac_inliers = c.res.n_inliers;
+            _stats.final_inliers = good;
+            return finish(true);
+        }
+        for (size_t k = feats.size(); k-- > 0;) feats[k]->_mappoint->_cnt_found = found[k];
+        for (Feature *f : feats) delete f;
+        current->_features = detected;
+        current->_TCW = T_saved;
+    }
+    // 7. nothing passed
+    current->_features = detected;
+    return finish(false);
+}
+
+}  // namespace ygz
