@@ -183,6 +183,20 @@ __device__ __forceinline__ uint32_t klt_diff_pair(int x0, int x1)
     iw10 = cv_round_f(__fmul_rn(__fmul_rn(__fsub_rn(1.f, a), b), 16384.f));                     \
     iw11 = 16384 - iw00 - iw01 - iw10;                                                          \
     wtop = (uint32_t)iw00 | ((uint32_t)iw01 << 16); wbot = (uint32_t)iw10 | ((uint32_t)iw11 << 16)
+// The same weights as KLT_WEIGHTS, packed straight from float bits (k_klt3).  t = x * 16384 is exact for x = (1-a)(1-b) etc. in [0, 1],
+// and fma(x, 16384, 1.5 * 2^23) rounds t + 1.5 * 2^23 once: the sum lies in [2^23, 2^24), where the float grid is the integers, and
+// 1.5 * 2^23 is even, so the sum is 1.5 * 2^23 + rint(t) (ties to even) = 0x4B400000 + cv_round_f(t) in bits.  The low 16 bits are the
+// weight (<= 16384); the upper halves drop out of the 16-bit fields the packing keeps (three times 0x4B400000 is 0 mod 2^16, and
+// iw11 is kept mod 2^16 as the reference's (uint32_t)iw11 << 16 keeps it).
+// Saves the v_rndne and the v_cvt of every weight.  tests/test_klt_rewrites.py checks both steps against KLT_WEIGHTS.
+#define KLT_WBITS(x) __float_as_uint(__builtin_fmaf((x), 16384.f, 12582912.f))
+#define KLT_WEIGHTS_P(a, b)                                                                                           \
+    {                                                                                                                 \
+        const float ia_ = __fsub_rn(1.f, a), ib_ = __fsub_rn(1.f, b);                                                 \
+        const uint32_t w00_ = KLT_WBITS(__fmul_rn(ia_, ib_)), w01_ = KLT_WBITS(__fmul_rn(a, ib_)), w10_ = KLT_WBITS(__fmul_rn(ia_, b)); \
+        wtop = KLT_DXP(w00_, w01_);                                               /* iw00 | iw01 << 16 */            \
+        wbot = KLT_DXP(w10_, 16384u - (w00_ + w01_ + w10_));                     /* iw10 | (16384 - iw00 - iw01 - iw10) << 16 */ \
+    }
 
 // FULL: the 21-wide window (every active lane owns exactly 7 pixels) -- the per-pixel guards fold away
 template <bool FULL>
@@ -343,16 +357,82 @@ __global__ __launch_bounds__(64 * KLT_WPB) void k_klt(KltArgs A)
 // rows instead of 6 and 42), and the lanes of a point reduce with a fixed-order 21-lane tree.  Points of a wavefront iterate
 // until the slowest has converged; finished ones idle (their lanes are masked).  Integer terms are those of k_klt<> and the
 // oracle; float sums differ in order only.
-__device__ __forceinline__ float klt_seg21_sum(float v, int lane, int q, int seg)
+//
+// The 21-lane segment sum, a fixed tree over the segment's lanes q = 0..20 (q = lane - seg):
+//   v[q] += v[q + 16] (q < 5); v[q] += v[q + 8] (q < 8); v[q] += v[q + 4] (q < 4); v[q] += v[q + 2] (q < 2); v[q] += v[q + 1] (q < 1),
+// then lane q = 0 is broadcast to its segment.  The same additions of the same operands, with cheaper data movement:
+//   - +16: lanes 5..15 must keep their value (the +8 step reads them).  They add lane 63 instead, which idles and holds +0.0:
+//     v + 0 == v exactly for every v except -0, and no value of a segment sum is -0 (its inputs are conversions of integers or
+//     sums of absolute values, and a round-to-nearest sum is -0 only when both addends are).  No mask.
+//   - +8, +4, +2, +1: what a step leaves in lanes that no later step reads does not matter, so they add unconditionally.
+//   - +2, +1 stay inside one 16-lane DPP row for all three segments (lanes 0-3, 21-24, 42-45): v_add_f32 with a row_shl operand.
+//   - +16, +8, +4 and the broadcast cross a row for some segment: ds_bpermute, at lane addresses computed once per launch.
+// Every operand that reaches lane q = 0 is the one of the tree above, so the result is bit-identical to the masked form.
+struct KltSegIdx { int p16, p8, p4, bc; };          // ds_bpermute byte addresses (lane * 4)
+__device__ __forceinline__ KltSegIdx klt_seg_idx(int lane, int q, int sub, int seg)
 {
-    float t;
-    t = __shfl(v, lane + 16 < 63 ? lane + 16 : 63); if (q < 5) v = __fadd_rn(v, t);
-    t = __shfl(v, lane + 8 < 63 ? lane + 8 : 63);   if (q < 8) v = __fadd_rn(v, t);
-    t = __shfl(v, lane + 4 < 63 ? lane + 4 : 63);   if (q < 4) v = __fadd_rn(v, t);
-    t = __shfl(v, lane + 2 < 63 ? lane + 2 : 63);   if (q < 2) v = __fadd_rn(v, t);
-    t = __shfl(v, lane + 1 < 63 ? lane + 1 : 63);   if (q < 1) v = __fadd_rn(v, t);
-    return __shfl(v, seg);
+    KltSegIdx ix;
+    ix.p16 = 4 * (sub < 3 && q < 5 ? lane + 16 : 63);
+    ix.p8 = 4 * min(lane + 8, 63);
+    ix.p4 = 4 * min(lane + 4, 63);
+    ix.bc = 4 * seg;
+    return ix;
 }
+#define KLT_BPERM_F(addr, v) __int_as_float(__builtin_amdgcn_ds_bpermute((addr), __float_as_int(v)))
+#define KLT_ROW_SHL_F(v, n) __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x100 + (n), 0xF, 0xF, false))
+// lane 63 must hold +0.0 on entry (it idles: every input of it is 0.f)
+__device__ __forceinline__ float klt_seg21_sum(float v, const KltSegIdx &ix)
+{
+    v = __fadd_rn(v, KLT_BPERM_F(ix.p16, v));
+    v = __fadd_rn(v, KLT_BPERM_F(ix.p8, v));
+    v = __fadd_rn(v, KLT_BPERM_F(ix.p4, v));
+    v = __fadd_rn(v, KLT_ROW_SHL_F(v, 2));
+    v = __fadd_rn(v, KLT_ROW_SHL_F(v, 1));
+    return KLT_BPERM_F(ix.bc, v);
+}
+// two sums side by side: the two chains of LDS round trips overlap
+__device__ __forceinline__ void klt_seg21_sum2(float &u, float &v, const KltSegIdx &ix)
+{
+    u = __fadd_rn(u, KLT_BPERM_F(ix.p16, u)); v = __fadd_rn(v, KLT_BPERM_F(ix.p16, v));
+    u = __fadd_rn(u, KLT_BPERM_F(ix.p8, u));  v = __fadd_rn(v, KLT_BPERM_F(ix.p8, v));
+    u = __fadd_rn(u, KLT_BPERM_F(ix.p4, u));  v = __fadd_rn(v, KLT_BPERM_F(ix.p4, v));
+    u = __fadd_rn(u, KLT_ROW_SHL_F(u, 2));    v = __fadd_rn(v, KLT_ROW_SHL_F(v, 2));
+    u = __fadd_rn(u, KLT_ROW_SHL_F(u, 1));    v = __fadd_rn(v, KLT_ROW_SHL_F(v, 1));
+    u = KLT_BPERM_F(ix.bc, u);                v = KLT_BPERM_F(ix.bc, v);
+}
+
+// Window rows through a wave-uniform row base (SGPRs) and one 32-bit lane offset from it: global_load_dwordx3 v, v_off, s[base],
+// no 64-bit address arithmetic per row.  Frame bases are 4-byte aligned (hipMalloc'ed buffers, slot size pw * (h + 2 KLT_B) with
+// pw a multiple of 4), and so is every row of a frame: the byte shift of an 8-byte window row is the same for all rows of a window
+// (off & 3), and the aligned dwords are exactly those klt_load8 reads.  Offsets are from the frame's corner, so they are never negative
+// for an admissible window (x, y >= -win > -KLT_B).
+typedef const __attribute__((address_space(1))) uint8_t *klt_gbytes;
+// the four window rows of a frame from its corner, each base opaque to the optimiser: it would otherwise step from row to row with
+// 64-bit VALU adds on the lane address instead of keeping four SGPR bases
+__device__ __forceinline__ void klt_row_bases(klt_gbytes corner, int pitch, klt_gbytes (&row)[4])
+{
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        uint64_t a = (uint64_t)(corner + r * pitch);
+        asm("" : "+s"(a));
+        row[r] = (klt_gbytes)a;
+    }
+}
+// sh: the byte offset itself -- v_alignbyte reads only bits [1:0] of its shift operand, so no mask
+__device__ __forceinline__ void klt_load8_row(klt_gbytes row /* wave-uniform */, uint32_t off_al, uint32_t sh, uint32_t &lo, uint32_t &hi)
+{
+    klt_gptr q = (klt_gptr)(row + off_al);
+    const uint32_t d0 = q[0], d1 = q[1], d2 = q[2];
+    lo = __builtin_amdgcn_alignbyte(d1, d0, sh);
+    hi = __builtin_amdgcn_alignbyte(d2, d1, sh);
+}
+// (double)fabsf(x) < 0.01 without FP64: 0.01 is no float, and 0.01f (0x3C23D70A = 0.0099999997764825820922851562) is the largest float
+// below it, so for every float f: (double)f < 0.01  <=>  f <= 0.01f (NaN: false on both sides).  tests/test_klt_rewrites.py checks it.
+#define KLT_ABS_LT_001(x) (fabsf(x) <= 0.01f)
+// (double)dx * dx + (double)dy * dy: a product of two floats has at most 48 significant bits and lies inside the normal FP64 range,
+// so both products are exact and one fma (one rounding of dx^2 + dy^2) gives the bits of the two multiplies and the add.
+__device__ __forceinline__ double klt_norm2_d(float dx, float dy)
+{ return __builtin_fma((double)dx, (double)dx, (double)dy * (double)dy); }
 
 // (Round 4 also measured fetching only three of a lane's four window rows and taking the fourth from the lane that owns the next row triple
 // through the LDS crossbar -- two ds_bpermute instead of a gather: bit-identical and SLOWER, 2.68 against 2.52 ms per 512 pairs; the dependent
@@ -366,6 +446,8 @@ __global__ __launch_bounds__(256) void k_klt3(KltArgs A)
     const int first = (bx * 4 + wv) * 3;
     if (first >= n) return;                                  // wave-uniform
     const int sub = lane / 21, q = lane - 21 * sub, rt = q / 3, x0 = 7 * (q - 3 * rt), row0 = 3 * rt, seg = sub < 3 ? 21 * sub : 63;
+    const int rowb = row0 + KLT_B, colb = x0 + KLT_B;      // the lane's window corner in frame coordinates: (y + rowb) * pw + x + colb
+    const KltSegIdx six = klt_seg_idx(lane, q, sub, seg);
     const int pi = first + sub;
     const bool live = sub < 3 && pi < n;                     // lane 63 and the lanes of points past the end idle
     const size_t p = (size_t)pair * A.cells + (live ? pi : first);
@@ -382,9 +464,13 @@ __global__ __launch_bounds__(256) void k_klt3(KltArgs A)
     for (int level = A.max_level; level >= 0; --level) {
         const int w = A.w[level], h = A.h[level];
         const int pw = KLT_PW(w);
-        const size_t psz = (size_t)pw * (h + 2 * KLT_B), org = (size_t)KLT_B * pw + KLT_B;
-        const uint8_t *I = A.pad[level] + ref_slot * psz + org, *J = A.pad[level] + cur_slot * psz + org;
-        klt_gptr D = (klt_gptr)(reinterpret_cast<const uint32_t *>(A.deriv[level]) + ref_slot * psz + org);
+        const size_t psz = (size_t)pw * (h + 2 * KLT_B);
+        // frame corners (wave-uniform): lane offsets from here are (y + KLT_B) * pw + x + KLT_B >= 0, see klt_load8_row
+        const klt_gbytes Ib = (klt_gbytes)(A.pad[level] + ref_slot * psz), Jb = (klt_gbytes)(A.pad[level] + cur_slot * psz);
+        const klt_gbytes Db = (klt_gbytes)(reinterpret_cast<const uint8_t *>(A.deriv[level]) + ref_slot * psz * 4);
+        klt_gbytes Ir[4], Jr[4], Dr[4];
+        klt_row_bases(Ib, pw, Ir); klt_row_bases(Jb, pw, Jr); klt_row_bases(Db, 4 * pw, Dr);
+        const int lo = __mul24(rowb, pw) + colb;                   // the lane's offset of a window at (0, 0): y * pw + x + lo per window
         const float s = __int_as_float((127 - level) << 23);       // (float)(1. / (1 << level)), exact
         float prevx = __fmul_rn(ppx, s), prevy = __fmul_rn(ppy, s);
         float nx, ny;
@@ -395,19 +481,18 @@ __global__ __launch_bounds__(256) void k_klt3(KltArgs A)
         const int ipx = (int)floorf(prevx), ipy = (int)floorf(prevy);
         const bool in_lv = live && !(ipx < -win || ipx >= w || ipy < -win || ipy >= h);
         if (live && !in_lv && level == 0) { status = false; errv = 0.f; }
-        float a = __fsub_rn(prevx, (float)ipx), b = __fsub_rn(prevy, (float)ipy);
-        int iw00, iw01, iw10, iw11;
+        float a = __fsub_rn(prevx, floorf(prevx)), b = __fsub_rn(prevy, floorf(prevy));   // == prevx - (float)ipx wherever it is used
         uint32_t wtop, wbot;
-        KLT_WEIGHTS(a, b);
+        KLT_WEIGHTS_P(a, b);
         // the lane's 3 x 7 patch values stay in registers for the whole level: image << 5, and the derivatives of two
         // consecutive pixels per register (dx_k | dx_k+1 << 16, same for dy) -- the layout v_dot2 wants for the mismatch sums
         int cI[21]; uint32_t pDx[11], pDy[11];                      // cI = 256 - (patch value << 9), see KLT_DIFF9P; only read where in_lv
         float sA11 = 0.f, sA12 = 0.f, sA22 = 0.f;
         if (in_lv) {
-            const int o = __mul24(ipy + row0, pw) + ipx + x0;
+            const uint32_t o = (uint32_t)(__mul24(ipy, pw) + ipx + lo), oa = o & ~3u, o4 = o << 2;
             uint32_t il[4], ih[4];
 #pragma unroll
-            for (int r = 0; r < 4; ++r) klt_load8(I + o + r * pw, il[r], ih[r]);
+            for (int r = 0; r < 4; ++r) klt_load8_row(Ir[r], oa, o, il[r], ih[r]);
             // the (short) casts of the reference are value-preserving (0 <= ival <= 255 << 5, |Scharr| <= 16 * 255): the raw sums are
             // packed two pixels per register with one v_perm, and the A-matrix sums run on the packed pairs (11 v_dot2 each
             // instead of 21 multiply-adds; exact: 21 products < 2^29)
@@ -415,8 +500,9 @@ __global__ __launch_bounds__(256) void k_klt3(KltArgs A)
 #pragma unroll
             for (int r = 0; r < 3; ++r) {
                 uint32_t d0[8], d1[8];
+                klt_gptr D0 = (klt_gptr)(Dr[r] + o4), D1 = (klt_gptr)(Dr[r + 1] + o4);
 #pragma unroll
-                for (int kk = 0; kk < 8; ++kk) { d0[kk] = D[o + r * pw + kk]; d1[kk] = D[o + (r + 1) * pw + kk]; }
+                for (int kk = 0; kk < 8; ++kk) { d0[kk] = D0[kk]; d1[kk] = D1[kk]; }
 #pragma unroll
                 for (int kk = 0; kk < 7; ++kk) {
                     const int ival = klt_dot2(KLT_PAIR(il[r + 1], ih[r + 1], kk), wbot, klt_dot2_sacc(KLT_PAIR(il[r], ih[r], kk), wtop, 256)) >> 9;
@@ -434,8 +520,8 @@ __global__ __launch_bounds__(256) void k_klt3(KltArgs A)
             for (int kk = 0; kk < 11; ++kk) { q11 = klt_dot2(pDx[kk], pDx[kk], q11); q12 = klt_dot2(pDx[kk], pDy[kk], q12); q22 = klt_dot2(pDy[kk], pDy[kk], q22); }
             sA11 = (float)q11; sA12 = (float)q12; sA22 = (float)q22;
         }
-        const float A11 = __fmul_rn(klt_seg21_sum(sA11, lane, q, seg), FLT_SCALE), A12 = __fmul_rn(klt_seg21_sum(sA12, lane, q, seg), FLT_SCALE),
-                    A22 = __fmul_rn(klt_seg21_sum(sA22, lane, q, seg), FLT_SCALE);
+        klt_seg21_sum2(sA11, sA12, six);
+        const float A11 = __fmul_rn(sA11, FLT_SCALE), A12 = __fmul_rn(sA12, FLT_SCALE), A22 = __fmul_rn(klt_seg21_sum(sA22, six), FLT_SCALE);
         float Dd = __fsub_rn(__fmul_rn(A11, A22), __fmul_rn(A12, A12));
         const float dif = __fsub_rn(A11, A22);
         const float minEig = __fdiv_rn(__fsub_rn(__fadd_rn(A22, A11),
@@ -447,23 +533,25 @@ __global__ __launch_bounds__(256) void k_klt3(KltArgs A)
         nx = it_ok ? __fsub_rn(nx, half) : nx; ny = it_ok ? __fsub_rn(ny, half) : ny;
         float pdx = 0.f, pdy = 0.f;
         bool done = !it_ok;
+        // the lane sums of the mismatch, kept across iterations: a lane that no longer evaluates keeps its last sums instead of being
+        // zeroed every iteration.  Only lane 63 is read by another segment (the +16 step of klt_seg21_sum), and it never evaluates: +0.0.
+        float sb1 = 0.f, sb2 = 0.f;
         for (int j = 0; j < A.max_count; ++j) {
-            if (__ballot(!done) == 0ull) break;
+            if (__builtin_amdgcn_ballot_w64(!done) == 0ull) break;      // the lane mask itself (__ballot rebuilds it with two VALU ops)
             const int inx = (int)floorf(nx), iny = (int)floorf(ny);
             if (!done && (inx < -win || inx >= w || iny < -win || iny >= h)) {
                 if (level == 0) status = false;
                 done = true;
             }
             const bool act = !done;
-            a = __fsub_rn(nx, (float)inx); b = __fsub_rn(ny, (float)iny);
-            KLT_WEIGHTS(a, b);
-            float sb1 = 0.f, sb2 = 0.f;
+            a = __fsub_rn(nx, floorf(nx)); b = __fsub_rn(ny, floorf(ny));
+            KLT_WEIGHTS_P(a, b);
             if (act) {
-                const int o = __mul24(iny + row0, pw) + inx + x0;
+                const uint32_t o = (uint32_t)(__mul24(iny, pw) + inx + lo), oa = o & ~3u;
                 uint32_t jl[4], jh[4];
 #pragma unroll
-                for (int r = 0; r < 4; ++r) klt_load8(J + o + r * pw, jl[r], jh[r]);
-                int a1 = 0, a2 = 0;                                  // 21 terms, |diff * I| < 2^26: exact in int32
+                for (int r = 0; r < 4; ++r) klt_load8_row(Jr[r], oa, o, jl[r], jh[r]);
+                int a1, a2;                                          // 21 terms, |diff * I| < 2^26: exact in int32
                 int df[22];                                          // S + c, the >> 9 happens in klt_diff_pair
                 df[21] = 0;
 #pragma unroll
@@ -474,19 +562,21 @@ __global__ __launch_bounds__(256) void k_klt3(KltArgs A)
 #pragma unroll
                 for (int kk = 0; kk < 11; ++kk) {                    // (diff_2k, diff_2k+1) . (dx_2k, dx_2k+1): |diff| < 2^14 fits int16
                     const uint32_t dp = klt_diff_pair(df[2 * kk], df[2 * kk + 1]);
-                    a1 = klt_dot2(dp, pDx[kk], a1);
-                    a2 = klt_dot2(dp, pDy[kk], a2);
+                    a1 = kk ? klt_dot2(dp, pDx[kk], a1) : klt_dot2_sacc(dp, pDx[0], 0);     // the first one from an SGPR zero: no v_mov
+                    a2 = kk ? klt_dot2(dp, pDy[kk], a2) : klt_dot2_sacc(dp, pDy[0], 0);
                 }
                 sb1 = (float)a1; sb2 = (float)a2;
             }
-            const float b1 = __fmul_rn(klt_seg21_sum(sb1, lane, q, seg), FLT_SCALE), b2 = __fmul_rn(klt_seg21_sum(sb2, lane, q, seg), FLT_SCALE);
+            float t1 = sb1, t2 = sb2;
+            klt_seg21_sum2(t1, t2, six);
+            const float b1 = __fmul_rn(t1, FLT_SCALE), b2 = __fmul_rn(t2, FLT_SCALE);
             if (act) {
                 const float dx = __fmul_rn(__fsub_rn(__fmul_rn(A12, b2), __fmul_rn(A22, b1)), Dd);
                 const float dy = __fmul_rn(__fsub_rn(__fmul_rn(A12, b1), __fmul_rn(A11, b2)), Dd);
                 nx = __fadd_rn(nx, dx); ny = __fadd_rn(ny, dy);
                 outx = __fadd_rn(nx, half); outy = __fadd_rn(ny, half);
-                if ((double)dx * (double)dx + (double)dy * (double)dy <= A.epsilon) done = true;
-                else if (j > 0 && (double)fabsf(__fadd_rn(dx, pdx)) < 0.01 && (double)fabsf(__fadd_rn(dy, pdy)) < 0.01) {
+                if (klt_norm2_d(dx, dy) <= A.epsilon) done = true;
+                else if (j > 0 && KLT_ABS_LT_001(__fadd_rn(dx, pdx)) && KLT_ABS_LT_001(__fadd_rn(dy, pdy))) {
                     outx = __fsub_rn(outx, __fmul_rn(dx, 0.5f)); outy = __fsub_rn(outy, __fmul_rn(dy, 0.5f));
                     done = true;
                 }
@@ -498,14 +588,14 @@ __global__ __launch_bounds__(256) void k_klt3(KltArgs A)
             const float qx = __fsub_rn(outx, half), qy = __fsub_rn(outy, half);
             const int inx = (int)floorf(qx), iny = (int)floorf(qy);
             if (want && (inx < -win || inx >= w || iny < -win || iny >= h)) { status = false; want = false; }
-            const float aa = __fsub_rn(qx, (float)inx), bb = __fsub_rn(qy, (float)iny);
-            KLT_WEIGHTS(aa, bb);
+            const float aa = __fsub_rn(qx, floorf(qx)), bb = __fsub_rn(qy, floorf(qy));
+            KLT_WEIGHTS_P(aa, bb);
             float se = 0.f;
             if (want) {
-                const int o = __mul24(iny + row0, pw) + inx + x0;
+                const uint32_t o = (uint32_t)(__mul24(iny, pw) + inx + lo), oa = o & ~3u;
                 uint32_t jl[4], jh[4];
 #pragma unroll
-                for (int r = 0; r < 4; ++r) klt_load8(J + o + r * pw, jl[r], jh[r]);
+                for (int r = 0; r < 4; ++r) klt_load8_row(Jr[r], oa, o, jl[r], jh[r]);
 #pragma unroll
                 for (int r = 0; r < 3; ++r) {
 #pragma unroll
@@ -515,7 +605,7 @@ __global__ __launch_bounds__(256) void k_klt3(KltArgs A)
                     }
                 }
             }
-            const float tot = klt_seg21_sum(se, lane, q, seg);
+            const float tot = klt_seg21_sum(se, six);
             if (want) errv = __fdiv_rn(__fmul_rn(tot, 1.f), (float)(32 * win * win));
         }
     }
