@@ -8,4 +8,5 @@
 #include "ygz/Algorithm/BA.h"
 #include "ygz/Algorithm/Initializer.h"
 #include "ygz/Algorithm/Relocalizer.h"
+#include "ygz/Algorithm/LoopClosing.h"
 #endif

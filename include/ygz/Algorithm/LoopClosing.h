@@ -1,0 +1,98 @@
+// ygz/Algorithm/LoopClosing.h -- ygz::LoopClosing: loop detection.  The reference leaves the stage empty: LocalMapping.cpp:330 ends each
+// keyframe with "put this keyframe into the loop-detection queue" and no code, and include/ygz/loop_closing.h is an empty `class LoopClosing {}`.
+// This class takes that name and follows ORB-SLAM2's LoopClosing::DetectLoop (BoW candidates, KeyFrameDatabase::DetectLoopCandidates, the
+// covisibility-group consistency) and LoopClosing::ComputeSim3 (SearchByBoW per candidate, then Sim3 RANSAC and the 7-dof refinement of every
+// candidate in one device call, ygz_hip_sim3_ransac).  It detects only: no pose, map point, feature, observation or connection changes
+// (ygz_slam_amd/host/ygz_loop.cpp; the integration is in INTEGRATION.md).
+#ifndef YGZ_LOOP_CLOSING_H_
+#define YGZ_LOOP_CLOSING_H_
+
+#include "ygz/Basic.h"
+#include "ygz/Algorithm/Matcher.h"
+#include <set>
+
+namespace ygz
+{
+
+// a similarity: X -> s (R X) + t
+struct Sim3
+{
+    SO3 R;
+    Vector3d t = Vector3d(0, 0, 0);
+    double s = 1.0;
+
+    Sim3() {}
+    Sim3(const SO3 &R_, const Vector3d &t_, double s_) : R(R_), t(t_), s(s_) {}
+    explicit Sim3(const SE3 &T) : R(T.so3()), t(T.translation()), s(1.0) {}
+
+    Vector3d operator*(const Vector3d &p) const { return s * (R * p) + t; }
+    Sim3 operator*(const Sim3 &o) const { return Sim3(R * o.R, s * (R * o.t) + t, s * o.s); }
+    Sim3 operator*(const SE3 &T) const { return *this * Sim3(T); }
+    Sim3 inverse() const { const SO3 Ri = R.inverse(); return Sim3(Ri, -(1.0 / s) * (Ri * t), 1.0 / s); }
+    // qx qy qz qw tx ty tz s: SE3::to7's order, then the scale (the layout of ygz_sim3_result's S12)
+    void to8(double out[8]) const
+    { for (int i = 0; i < 4; ++i) out[i] = R.q_[i]; for (int i = 0; i < 3; ++i) out[4 + i] = t[i]; out[7] = s; }
+    static Sim3 from8(const double in[8])
+    { Sim3 S; for (int i = 0; i < 4; ++i) S.R.q_[i] = in[i]; for (int i = 0; i < 3; ++i) S.t[i] = in[4 + i]; S.s = in[7]; return S; }
+};
+
+class LoopClosing
+{
+public:
+    struct Option
+    {
+        int _min_kf_gap = 10;                   // keyframes after the last accepted loop (and after id 0) before another is detected
+        int _consistency_th = 3;                // consecutive consistent detections a candidate needs
+        double _min_common_words_ratio = 0.8;   // shared words above this fraction of the largest count
+        double _acc_score_ratio = 0.75;         // group scores above this fraction of the best
+        int _acc_covisibles = 10;               // covisibles of a candidate that join its group score
+        float _knn_ratio = 0.75f;               // SearchByBoW's ratio
+        int _min_bow_matches = 20;              // map-point pairs a candidate needs before RANSAC
+        int _ransac_iterations = 300;           // ORB-SLAM2 LoopClosing::ComputeSim3 / Optimizer::OptimizeSim3's values
+        double _ransac_chi2 = 9.210;
+        int _min_inliers = 20;
+        double _refine_chi2 = 10;
+        bool _fix_scale = false;                // true for stereo / RGB-D maps
+    } _option;
+
+    struct Stats
+    {
+        double min_score = 0;                   // minScore of the last DetectLoop
+        vector<unsigned long> candidates;       // the group representatives of the last DetectLoop, by keyframe id
+        vector<double> acc_scores;              // their group scores
+        vector<int> consistency;                // their consistency (the largest over the previous groups they extend; 0 for a new group)
+        vector<unsigned long> consistent;       // the enough-consistent ones, by keyframe id
+        vector<int> bow_pairs;                  // per enough-consistent candidate: the map-point pairs of SearchByBoW (last ComputeSim3)
+        vector<int> ransac_inliers;             // per enough-consistent candidate: -1 when it did not reach the device
+        vector<int> refined_inliers;            // likewise
+    };
+
+    // kf: a keyframe of the map with its covisibility (_connected_keyframe_weights); true when some loop candidate is consistent enough
+    bool DetectLoop(Frame *kf, const vector<Frame *> &keyframes);
+    bool DetectLoop(Frame *kf);             // every keyframe registered in Memory
+    // the geometric check of the last DetectLoop's candidates; true when one of them is accepted
+    bool ComputeSim3();
+
+    Frame *GetMatchedKeyframe() const { return _matched; }
+    const Sim3 &GetSim3() const { return _S12; }                      // loop keyframe's camera -> current keyframe's camera
+    const Sim3 &GetCorrectedPose() const { return _Scw; }             // S12 * T_2w
+    const vector<pair<MapPoint *, MapPoint *>> &GetMatches() const { return _matches; }   // (current, loop) refined inlier pairs
+    const Stats &GetStats() const { return _stats; }
+
+private:
+    typedef pair<std::set<unsigned long>, int> ConsistentGroup;      // keyframe ids, consistency
+    vector<ConsistentGroup> _consistent_groups;
+    vector<Frame *> _enough_consistent;
+    map<unsigned long, double> _acc_score;
+    Frame *_current = nullptr;
+    unsigned long _last_loop_kf_id = 0;
+    Matcher _matcher;
+    Frame *_matched = nullptr;
+    Sim3 _S12, _Scw;
+    vector<pair<MapPoint *, MapPoint *>> _matches;
+    Stats _stats;
+};
+
+}
+
+#endif // YGZ_LOOP_CLOSING_H_

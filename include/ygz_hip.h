@@ -44,7 +44,9 @@ extern "C" {
  * Still 6: the monocular Initializer added (ygz_init_params, ygz_init_result, ygz_hip_default_init_params, ygz_hip_initialize,
  * ygz_hip_init_sample_sets, ygz_hip_init_hypotheses, ygz_hip_init_reconstruct) -- no existing argument list changed.
  * Still 6: the relocalisation's PnP RANSAC added (ygz_pnp_params, ygz_pnp_result, ygz_hip_default_pnp_params, ygz_hip_pnp_sample_sets,
- * ygz_hip_pnp_ransac, ygz_hip_pnp_hypotheses) -- no existing argument list changed. */
+ * ygz_hip_pnp_ransac, ygz_hip_pnp_hypotheses) -- no existing argument list changed.
+ * Still 6: the loop detection's Sim3 RANSAC added (ygz_sim3_params, ygz_sim3_result, ygz_hip_default_sim3_params, ygz_hip_sim3_ransac,
+ * ygz_hip_sim3_hypotheses) -- no existing argument list changed. */
 #define YGZ_HIP_ABI_VERSION 6
 
 typedef struct ygz_hip_ctx ygz_hip_ctx;
@@ -692,6 +694,52 @@ int  ygz_hip_pnp_ransac(ygz_hip_ctx *ctx, int n_problems, const int32_t *offsets
  * [max_iter], counts [max_iter][4] (0 past n_solutions); each may be NULL */
 int  ygz_hip_pnp_hypotheses(ygz_hip_ctx *ctx, const double *pw, const double *px, int n, const double K4[4], const ygz_pnp_params *params,
                             double *solutions, int32_t *n_solutions, int32_t *counts);
+
+/* ---- loop detection: Sim3 by RANSAC and a 7-dof refinement -- nothing in the reference; LocalMapping.cpp:330 leaves the loop-detection
+ * queue as a comment, and this is ORB-SLAM2's LoopClosing::ComputeSim3 (Sim3Solver + Optimizer::OptimizeSim3).  Several independent problems
+ * per call, one per candidate keyframe: problem p owns the pairs offsets[p] .. offsets[p+1]-1, each a current-keyframe point X1 [N][3] in the
+ * current camera, a candidate point X2 [N][3] in the candidate's camera, their level-0 pixels px1, px2 [N][2] and pyramid levels levels
+ * [N][2] (sigma^2 = 4^level).  Per problem the sample sets of ygz_hip_pnp_sample_sets(n, max_iter), Horn's closed form per sample (S12 with
+ * S12 X2 ~ X1), the inlier count of every sample (both projections in front and within chi2 sigma^2 of the pixel), the highest count (ties:
+ * smallest sample); with min_inliers of them, g2o's LM on S12 over two Huber edges per inlier, a second round without the pairs above
+ * chi2_refine.  The arithmetic is that of tests/sim3_ref.c: every output is bit-identical to it. */
+#define YGZ_SIM3_MAX_ITER     1024        /* bound of max_iter */
+#define YGZ_SIM3_MAX_PROBLEMS 64          /* problems per call */
+typedef struct {                          /* ORB-SLAM2 LoopClosing::ComputeSim3 / Optimizer::OptimizeSim3's values */
+    int    max_iter;                      /* 300 */
+    double chi2;                          /* 9.210: RANSAC inlier threshold, times sigma^2 of the level */
+    int    min_inliers;                   /* 20: for RANSAC success and for the refined count */
+    double chi2_refine;                   /* 10: the edges' outlier threshold, and the Huber width sqrt(chi2_refine) */
+    int    iters_first;                   /* 5: LM iterations of the first round */
+    int    iters_more;                    /* 10: of the second round when the first dropped a pair */
+    int    iters_again;                   /* 5: of the second round otherwise */
+    int    fix_scale;                     /* 0; 1: s = 1 (6-dof) */
+} ygz_sim3_params;
+typedef struct {
+    double  S12[8];                       /* qx qy qz qw tx ty tz s (the order of SE3::to7, then s): S12 X2 = s R X2 + t; identity without a winner */
+    double  S21[8];                       /* its inverse */
+    double  chi2_ransac;                  /* sum of rho over the winner's inliers before the refinement (0 without one) */
+    double  chi2_refined;                 /* sum of rho over the kept pairs after it */
+    int32_t success;                      /* n_inliers >= min_inliers and n_refined >= min_inliers */
+    int32_t n_hypotheses;                 /* valid samples */
+    int32_t best_sample;                  /* the winner (-1: every sample scored 0) */
+    int32_t n_inliers;                    /* RANSAC inliers of the winner */
+    int32_t n_refined;                    /* pairs with both chi2 <= chi2_refine after the refinement (0 when it did not run) */
+    int32_t lm_iterations;                /* LM iterations of both rounds */
+} ygz_sim3_result;
+void ygz_hip_default_sim3_params(ygz_sim3_params *p);
+/* the fused call: K4 = fx fy cx cy, params NULL: defaults; results [n_problems]; inliers [N] (may be NULL): bit 0 a RANSAC inlier of the
+ * winner, bit 1 a refined inlier.  One upload, the launches, one copy back and one wait.  YGZ_E_INVALID: a null context or array,
+ * n_problems < 1, offsets not starting at 0, a problem of fewer than 3 pairs, max_iter outside [1, YGZ_SIM3_MAX_ITER], chi2 or chi2_refine
+ * <= 0, a negative iteration count; YGZ_E_CAPACITY: more than YGZ_SIM3_MAX_PROBLEMS problems or a problem larger than ygz_hip_max_keypoints
+ * -- all before the device is touched. */
+int  ygz_hip_sim3_ransac(ygz_hip_ctx *ctx, int n_problems, const int32_t *offsets, const double *X1, const double *X2, const double *px1,
+                         const double *px2, const int32_t *levels, const double K4[4], const ygz_sim3_params *params, ygz_sim3_result *results,
+                         uint8_t *inliers);
+/* stage for tests: every sample of ONE problem -- hyps [max_iter][16] (S12 then S21; identities when invalid), valid [max_iter], counts
+ * [max_iter] (0 when invalid); each may be NULL */
+int  ygz_hip_sim3_hypotheses(ygz_hip_ctx *ctx, const double *X1, const double *X2, const double *px1, const double *px2, const int32_t *levels,
+                             int n, const double K4[4], const ygz_sim3_params *params, double *hyps, int32_t *valid, int32_t *counts);
 
 #ifdef __cplusplus
 }

@@ -163,6 +163,34 @@ def pnp_sample_sets(n, max_iter=300):
     return s
 
 
+class Sim3Params(C.Structure):
+    _fields_ = [("max_iter", C.c_int), ("chi2", C.c_double), ("min_inliers", C.c_int), ("chi2_refine", C.c_double), ("iters_first", C.c_int),
+                ("iters_more", C.c_int), ("iters_again", C.c_int), ("fix_scale", C.c_int)]
+
+
+class Sim3Result(C.Structure):
+    _fields_ = [("S12", C.c_double * 8), ("S21", C.c_double * 8), ("chi2_ransac", C.c_double), ("chi2_refined", C.c_double),
+                ("success", C.c_int32), ("n_hypotheses", C.c_int32), ("best_sample", C.c_int32), ("n_inliers", C.c_int32),
+                ("n_refined", C.c_int32), ("lm_iterations", C.c_int32)]
+
+    def to_dict(self):
+        return InitResult.to_dict(self)
+
+
+def default_sim3_params():
+    p = Sim3Params()
+    load().ygz_hip_default_sim3_params(C.byref(p))
+    return p
+
+
+def _sim3_params(**kw):
+    p = default_sim3_params()
+    for k, v in kw.items():
+        if v is not None:
+            setattr(p, k, v)
+    return p
+
+
 # every symbol include/ygz_hip.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
     "ygz_hip_default_params", "ygz_hip_create", "ygz_hip_destroy", "ygz_hip_synchronize", "ygz_hip_join", "ygz_hip_set_overlap", "ygz_hip_error_string",
@@ -187,11 +215,14 @@ ABI_SYMBOLS = [
     "ygz_hip_abi_version", "ygz_hip_ba_optimize_chi2", "ygz_hip_ba_set_team_placement", "ygz_hip_get_stream", "ygz_hip_get_device", "ygz_hip_make_current", "ygz_hip_device_alloc", "ygz_hip_device_free", "ygz_hip_copy",
     "ygz_hip_default_init_params", "ygz_hip_initialize", "ygz_hip_init_sample_sets", "ygz_hip_init_hypotheses", "ygz_hip_init_reconstruct",
     "ygz_hip_default_pnp_params", "ygz_hip_pnp_sample_sets", "ygz_hip_pnp_ransac", "ygz_hip_pnp_hypotheses",
+    "ygz_hip_default_sim3_params", "ygz_hip_sim3_ransac", "ygz_hip_sim3_hypotheses",
 ]
 INIT_SYMBOLS = ["ygz_hip_default_init_params", "ygz_hip_initialize", "ygz_hip_init_sample_sets", "ygz_hip_init_hypotheses", "ygz_hip_init_reconstruct"]
 INIT_NONE, INIT_H, INIT_F = 0, 1, 2
 PNP_SYMBOLS = ["ygz_hip_default_pnp_params", "ygz_hip_pnp_sample_sets", "ygz_hip_pnp_ransac", "ygz_hip_pnp_hypotheses"]
 PNP_MAX_ITER, PNP_MAX_PROBLEMS = 1024, 64
+SIM3_SYMBOLS = ["ygz_hip_default_sim3_params", "ygz_hip_sim3_ransac", "ygz_hip_sim3_hypotheses"]
+SIM3_MAX_ITER, SIM3_MAX_PROBLEMS = 1024, 64
 
 SUMMARY_FIELDS = 32
 
@@ -1015,6 +1046,51 @@ class HipContext:
         self._chk(self.lib.ygz_hip_pnp_hypotheses(self._ctx, _p(pw, C.c_double), _p(px, C.c_double), n, K, C.byref(prm), _p(sol, C.c_double),
                                                   _p(ns, C.c_int32), _p(cnt, C.c_int32)), "pnp_hypotheses")
         return dict(solutions=sol, n_solutions=ns, counts=cnt)
+
+    # ---- loop detection (Sim3 RANSAC and refinement)
+
+    @staticmethod
+    def _sim3_arrays(X1, X2, px1, px2, levels):
+        X1 = np.ascontiguousarray(X1, np.float64).reshape(-1, 3)
+        X2 = np.ascontiguousarray(X2, np.float64).reshape(-1, 3)
+        px1 = np.ascontiguousarray(px1, np.float64).reshape(-1, 2)
+        px2 = np.ascontiguousarray(px2, np.float64).reshape(-1, 2)
+        lv = np.ascontiguousarray(levels, np.int32).reshape(-1, 2)
+        if not (len(X1) == len(X2) == len(px1) == len(px2) == len(lv)):
+            raise ValueError("X1, X2, px1, px2 and levels differ in length")
+        return X1, X2, px1, px2, lv
+
+    def sim3_ransac(self, X1, X2, px1, px2, levels, offsets, K4, **params):
+        """every problem p of offsets [P + 1] (pairs offsets[p] .. offsets[p+1]-1) in one call (ygz_hip_sim3_ransac): a list of result dicts
+        and the mask [N] (uint8: bit 0 RANSAC inlier, bit 1 refined inlier).  params: the fields of ygz_sim3_params"""
+        X1, X2, px1, px2, lv = self._sim3_arrays(X1, X2, px1, px2, levels)
+        off = np.ascontiguousarray(offsets, np.int32).reshape(-1)
+        P = len(off) - 1
+        K = (C.c_double * 4)(*[float(v) for v in K4])
+        prm = _sim3_params(**params)
+        res = (Sim3Result * max(P, 1))()
+        mask = np.zeros(max(len(X1), 1), np.uint8)
+        dp = C.POINTER(C.c_double)
+        self.lib.ygz_hip_sim3_ransac.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int32), dp, dp, dp, dp, C.POINTER(C.c_int32), dp,
+                                                 C.POINTER(Sim3Params), C.POINTER(Sim3Result), C.POINTER(C.c_uint8)]
+        self._chk(self.lib.ygz_hip_sim3_ransac(self._ctx, P, _p(off, C.c_int32), _p(X1, C.c_double), _p(X2, C.c_double), _p(px1, C.c_double),
+                                               _p(px2, C.c_double), _p(lv, C.c_int32), K, C.byref(prm), res, _p(mask, C.c_uint8)), "sim3_ransac")
+        return [res[i].to_dict() for i in range(P)], mask[:len(X1)]
+
+    def sim3_hypotheses(self, X1, X2, px1, px2, levels, K4, **params):
+        """every sample of one problem (ygz_hip_sim3_hypotheses): hyps [max_iter][16] (S12 then S21), valid [max_iter], counts [max_iter]"""
+        X1, X2, px1, px2, lv = self._sim3_arrays(X1, X2, px1, px2, levels)
+        K = (C.c_double * 4)(*[float(v) for v in K4])
+        prm = _sim3_params(**params)
+        it = max(prm.max_iter, 1)
+        hyp, val, cnt = np.zeros((it, 16)), np.zeros(it, np.int32), np.zeros(it, np.int32)
+        dp = C.POINTER(C.c_double)
+        self.lib.ygz_hip_sim3_hypotheses.argtypes = [C.c_void_p, dp, dp, dp, dp, C.POINTER(C.c_int32), C.c_int, dp, C.POINTER(Sim3Params), dp,
+                                                     C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        self._chk(self.lib.ygz_hip_sim3_hypotheses(self._ctx, _p(X1, C.c_double), _p(X2, C.c_double), _p(px1, C.c_double), _p(px2, C.c_double),
+                                                   _p(lv, C.c_int32), len(X1), K, C.byref(prm), _p(hyp, C.c_double), _p(val, C.c_int32),
+                                                   _p(cnt, C.c_int32)), "sim3_hypotheses")
+        return dict(hyps=hyp, valid=val, counts=cnt)
 
     # ---- BoW
     def vocab_load(self, blob):
