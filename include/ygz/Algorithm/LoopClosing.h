@@ -2,39 +2,25 @@
 // keyframe with "put this keyframe into the loop-detection queue" and no code, and include/ygz/loop_closing.h is an empty `class LoopClosing {}`.
 // This class takes that name and follows ORB-SLAM2's LoopClosing::DetectLoop (BoW candidates, KeyFrameDatabase::DetectLoopCandidates, the
 // covisibility-group consistency) and LoopClosing::ComputeSim3 (SearchByBoW per candidate, then Sim3 RANSAC and the 7-dof refinement of every
-// candidate in one device call, ygz_hip_sim3_ransac).  It detects only: no pose, map point, feature, observation or connection changes
+// candidate in one device call, ygz_hip_sim3_ransac) with its second half, SearchLoopMapPoints: the accepted candidate's pairs widened by
+// Matcher::SearchBySim3, then the map points of the loop keyframe's neighbourhood pulled in by Matcher::SearchByProjection, and the "enough
+// matches in total" decision.  It detects only: no pose, map point, feature, observation or connection changes
 // (ygz_slam_amd/host/ygz_loop.cpp; the integration is in INTEGRATION.md).
 #ifndef YGZ_LOOP_CLOSING_H_
 #define YGZ_LOOP_CLOSING_H_
 
 #include "ygz/Basic.h"
+#include "ygz/Basic/Sim3.h"
 #include "ygz/Algorithm/Matcher.h"
 #include <set>
 
 namespace ygz
 {
 
-// a similarity: X -> s (R X) + t
-struct Sim3
-{
-    SO3 R;
-    Vector3d t = Vector3d(0, 0, 0);
-    double s = 1.0;
-
-    Sim3() {}
-    Sim3(const SO3 &R_, const Vector3d &t_, double s_) : R(R_), t(t_), s(s_) {}
-    explicit Sim3(const SE3 &T) : R(T.so3()), t(T.translation()), s(1.0) {}
-
-    Vector3d operator*(const Vector3d &p) const { return s * (R * p) + t; }
-    Sim3 operator*(const Sim3 &o) const { return Sim3(R * o.R, s * (R * o.t) + t, s * o.s); }
-    Sim3 operator*(const SE3 &T) const { return *this * Sim3(T); }
-    Sim3 inverse() const { const SO3 Ri = R.inverse(); return Sim3(Ri, -(1.0 / s) * (Ri * t), 1.0 / s); }
-    // qx qy qz qw tx ty tz s: SE3::to7's order, then the scale (the layout of ygz_sim3_result's S12)
-    void to8(double out[8]) const
-    { for (int i = 0; i < 4; ++i) out[i] = R.q_[i]; for (int i = 0; i < 3; ++i) out[4 + i] = t[i]; out[7] = s; }
-    static Sim3 from8(const double in[8])
-    { Sim3 S; for (int i = 0; i < 4; ++i) S.R.q_[i] = in[i]; for (int i = 0; i < 3; ++i) S.t[i] = in[4 + i]; S.s = in[7]; return S; }
-};
+// ygz::Sim3 is defined in ygz/Basic/Sim3.h (Matcher.h names it too) and exposed here as before:
+//   struct Sim3 { SO3 R; Vector3d t; double s; Sim3(); Sim3(R, t, s); explicit Sim3(const SE3 &);
+//                 Vector3d operator*(const Vector3d &) const; Sim3 operator*(const Sim3 &) const; Sim3 operator*(const SE3 &) const;
+//                 Sim3 inverse() const; void to8(double out[8]) const; static Sim3 from8(const double in[8]); };
 
 class LoopClosing
 {
@@ -53,6 +39,9 @@ public:
         int _min_inliers = 20;
         double _refine_chi2 = 10;
         bool _fix_scale = false;                // true for stereo / RGB-D maps
+        int _min_total_matches = 40;            // matches of the current keyframe SearchLoopMapPoints needs to accept the loop
+        float _sim3_search_th = 7.5f;           // SearchBySim3's window, level-0 pixels
+        float _projection_search_th = 10.0f;    // SearchByProjection's
     } _option;
 
     struct Stats
@@ -65,6 +54,9 @@ public:
         vector<int> bow_pairs;                  // per enough-consistent candidate: the map-point pairs of SearchByBoW (last ComputeSim3)
         vector<int> ransac_inliers;             // per enough-consistent candidate: -1 when it did not reach the device
         vector<int> refined_inliers;            // likewise
+        int sim3_added = 0;                     // last SearchLoopMapPoints: pairs SearchBySim3 added to the refined inliers
+        int projection_added = 0;               // matches SearchByProjection added from the loop map points
+        int total_matches = 0;                  // features of the current keyframe with a loop map point
     };
 
     // kf: a keyframe of the map with its covisibility (_connected_keyframe_weights); true when some loop candidate is consistent enough
@@ -72,11 +64,18 @@ public:
     bool DetectLoop(Frame *kf);             // every keyframe registered in Memory
     // the geometric check of the last DetectLoop's candidates; true when one of them is accepted
     bool ComputeSim3();
+    // valid after a ComputeSim3() that returned true: GetMatches() seeds a per-feature match vector of the current keyframe,
+    // SearchBySim3(current, matched, ..., S12, 7.5) widens it, the good map points of the matched keyframe and of its connected keyframes
+    // (keyframes in _keyframe_id order, features in index order, each point once) are the loop map points, SearchByProjection(current, S_cw,
+    // loop points, ..., 10) pulls them in; true when the matches reach _min_total_matches.  Changes nothing in the map.
+    bool SearchLoopMapPoints();
 
     Frame *GetMatchedKeyframe() const { return _matched; }
     const Sim3 &GetSim3() const { return _S12; }                      // loop keyframe's camera -> current keyframe's camera
     const Sim3 &GetCorrectedPose() const { return _Scw; }             // S12 * T_2w
     const vector<pair<MapPoint *, MapPoint *>> &GetMatches() const { return _matches; }   // (current, loop) refined inlier pairs
+    const vector<MapPoint *> &GetCurrentMatchedPoints() const { return _current_matched; }   // per feature of the current keyframe: its loop map point or nullptr (last SearchLoopMapPoints)
+    const vector<MapPoint *> &GetLoopMapPoints() const { return _loop_points; }             // the loop map points it searched
     const Stats &GetStats() const { return _stats; }
 
 private:
@@ -90,6 +89,7 @@ private:
     Frame *_matched = nullptr;
     Sim3 _S12, _Scw;
     vector<pair<MapPoint *, MapPoint *>> _matches;
+    vector<MapPoint *> _current_matched, _loop_points;
     Stats _stats;
 };
 

@@ -4,6 +4,7 @@
 #ifndef YGZ_MATCHER_H_
 #define YGZ_MATCHER_H_
 #include "ygz/Basic/Common.h"
+#include "ygz/Basic/Sim3.h"
 namespace ygz {
 struct Frame;
 struct MapPoint;
@@ -44,6 +45,32 @@ public:
     // reference's order is the heap-address order of a std::map<Feature*, ...>.  Returns the number of matched points.
     int ProjectMapPoints(Frame *current, const std::set<Frame *> &local_keyframes, const std::set<MapPoint *> &local_map_points);
     bool SparseImageAlignment(Frame *ref, Frame *current);                                  // Matcher.cpp:468-492
+
+    // ---- descriptor searches guided by projection -- nothing in the reference; ORB-SLAM2's ORBmatcher::SearchByProjection(pKF, Scw, ...),
+    // SearchBySim3 and Fuse(pKF, Scw, ...) over one device primitive (ygz_hip_search_by_projection).  A map point's
+    // attributes are derived on the host, once per call (PointAttributes):
+    //   descriptor  _distinctive_desc when it holds 32 bytes, else the descriptor of the reference observation = the _obs entry of the lowest
+    //               key with a non-null feature and frame;
+    //   dmax        |P - O_ref| 2^level_ref (the reference observation's camera centre and pyramid level);
+    //   normal      the mean over _obs, in key order, of the unit rays (P - O_k) / |P - O_k|, not renormalised (ORB-SLAM2's UpdateNormalAndDepth);
+    //   a point with no usable observation is skipped.
+    struct PointAttr { uint8_t desc[32]; double dmax = 0; Vector3d normal = Vector3d(0, 0, 0); };
+    static bool PointAttributes(const MapPoint *mp, PointAttr &out);
+    // points projected into kf with (R, t / s, 1) of Scw, the viewing-angle test, Hamming distance <= 50 (ORB-SLAM2's TH_LOW, not _options.th_low) and the claim: `matched`
+    // has one entry per feature of kf, its non-null entries mark taken keypoints; points that are bad or already in `matched` are skipped.
+    // Fills `matched`, returns the number of new matches.
+    int SearchByProjection(Frame *kf, const Sim3 &Scw, const vector<MapPoint *> &points, vector<MapPoint *> &matched, float th);
+    // kf1's map points into kf2 with S21 * T_1w and kf2's into kf1 with S12 * T_2w (the scale is kept) in one device call: no viewing-angle
+    // test, Hamming distance <= 100 (TH_HIGH), no claim; the sources skipped are the features already in matches12 (one entry per feature
+    // of kf1: a map point of kf2 or nullptr) on side 1 and their map points' features on side 2; a target keypoint needs a good map point;
+    // a pair is added when both directions agree.  Returns the number of pairs added.
+    int SearchBySim3(Frame *kf1, Frame *kf2, vector<MapPoint *> &matches12, const Sim3 &S12, float th);
+    // which feature of each keyframe a point would merge into (what ORB-SLAM2's Fuse decides, without acting on it): one problem per
+    // keyframe with (R, t / s, 1) of Scw[k], the viewing-angle test, Hamming distance <= 50, no claim; points that are bad or already
+    // observed by that keyframe are skipped.  feature_of_point[k][i] = feature index of kfs[k] or -1.  Read-only; returns the number of
+    // (keyframe, point) hits.
+    int SearchFuseCandidates(const vector<Frame *> &kfs, const vector<Sim3> &Scw, const vector<MapPoint *> &points, float th,
+                             vector<vector<int>> &feature_of_point);
     SE3 GetTCR() const { return _TCR_esti; }
 private:
     SparseImgAlign *_align;

@@ -46,7 +46,9 @@ extern "C" {
  * Still 6: the relocalisation's PnP RANSAC added (ygz_pnp_params, ygz_pnp_result, ygz_hip_default_pnp_params, ygz_hip_pnp_sample_sets,
  * ygz_hip_pnp_ransac, ygz_hip_pnp_hypotheses) -- no existing argument list changed.
  * Still 6: the loop detection's Sim3 RANSAC added (ygz_sim3_params, ygz_sim3_result, ygz_hip_default_sim3_params, ygz_hip_sim3_ransac,
- * ygz_hip_sim3_hypotheses) -- no existing argument list changed. */
+ * ygz_hip_sim3_hypotheses) -- no existing argument list changed.
+ * Still 6: the projection-guided descriptor search added (ygz_proj_problem, ygz_proj_params, ygz_hip_default_proj_params,
+ * ygz_hip_search_by_projection, ygz_hip_projection_candidates) -- no existing argument list changed. */
 #define YGZ_HIP_ABI_VERSION 6
 
 typedef struct ygz_hip_ctx ygz_hip_ctx;
@@ -740,6 +742,54 @@ int  ygz_hip_sim3_ransac(ygz_hip_ctx *ctx, int n_problems, const int32_t *offset
  * [max_iter] (0 when invalid); each may be NULL */
 int  ygz_hip_sim3_hypotheses(ygz_hip_ctx *ctx, const double *X1, const double *X2, const double *px1, const double *px2, const int32_t *levels,
                              int n, const double K4[4], const ygz_sim3_params *params, double *hyps, int32_t *valid, int32_t *counts);
+
+/* ---- loop closing: descriptor search guided by projection -- nothing in the reference; the primitive under ORB-SLAM2's
+ * ORBmatcher::SearchBySim3, SearchByProjection(pKF, Scw, points, matched, th) and Fuse(pKF, Scw, points, th, replace).  A problem is one
+ * target keyframe and one point set.  Per point, in this order: pt_skip set -> culled; Xc = s (R Pw) + t with R from the quaternion as
+ * written (se3_dev.h's quat_to_R_d), kept when z > 0; u = fx (x / z) + cx, v likewise, kept when 0 <= u < image_width and 0 <= v <
+ * image_height (the context's); d = |Xc|, culled when d < 0.8 dmax / 2^(L-1) or d > 1.2 dmax (L = the context's pyramid_levels); with
+ * pt_normal culled when Xc . (R n) < 0.5 d; the predicted level = the smallest n in [0, L-1] with dmax / d <= 2^n (L-1 when there is none);
+ * the candidates = the keypoints that are not taken, with |kx - u| < r and |ky - v| < r for r = th 2^pred, and pred - 1 <= level <= pred;
+ * the point's list = the candidates with a 256-bit Hamming distance <= th_dist sorted by (distance, keypoint index), cut to the first
+ * YGZ_PROJ_TOPK (a point with more is "overflowed").  Then the claim: claim == 0, a point's match is the head of its list; claim == 1, the
+ * points are walked in index order and each takes the first entry of its list that no earlier point took (ORB-SLAM2's sequential
+ * vpMatched[bestIdx] = pMP loop).  The arithmetic is that of tests/proj_ref.c: every output is bit-identical to it. */
+#define YGZ_PROJ_MAX_PROBLEMS 64          /* problems per call */
+#define YGZ_PROJ_TOPK         8           /* entries of a point's candidate list */
+#define YGZ_PROJ_MAX_POINTS   65536       /* points per call, over all problems */
+typedef struct {
+    const double  *kp_px;     /* [n_kp][2] level-0 pixels */
+    const int32_t *kp_level;  /* [n_kp] */
+    const uint8_t *kp_desc;   /* [n_kp][32] */
+    const uint8_t *kp_taken;  /* [n_kp] or NULL: a taken keypoint is never a candidate */
+    int            n_kp;
+    const double  *pw;        /* [n_pt][3] world position */
+    const uint8_t *pt_desc;   /* [n_pt][32] */
+    const double  *pt_dmax;   /* [n_pt] scale-invariance distance: |P - O_ref| 2^level_ref */
+    const double  *pt_normal; /* [n_pt][3] or NULL: no viewing-angle test */
+    const uint8_t *pt_skip;   /* [n_pt] or NULL */
+    int            n_pt;
+    double         S[8];      /* qx qy qz qw tx ty tz s, world -> target camera: Xc = s (R Pw) + t */
+} ygz_proj_problem;
+typedef struct {
+    double th;                /* 10: window radius at level 0, pixels */
+    int    th_dist;           /* 50: largest Hamming distance of a candidate (ORBmatcher::TH_LOW) */
+    int    claim;             /* 1 */
+} ygz_proj_params;
+void ygz_hip_default_proj_params(ygz_proj_params *p);
+/* the fused call: K4 = fx fy cx cy, params NULL: defaults.  The outputs are concatenated over the problems and may each be NULL: match [N]
+ * keypoint index or -1, dist [N] that match's Hamming distance or -1, pred_level [N] the predicted level or -1 for a point culled before the
+ * search, counts [n_problems][2] = matches, overflowed points.  One upload, the launch, one copy back and one wait; the claim is resolved
+ * inside the call.  YGZ_E_INVALID: a null context, problem or required array, n_problems < 1, n_kp < 1 or n_pt < 1, th <= 0, th_dist
+ * outside [0, 256], s <= 0 or a non-finite S; YGZ_E_CAPACITY: more than YGZ_PROJ_MAX_PROBLEMS problems, n_kp above ygz_hip_max_keypoints,
+ * more than YGZ_PROJ_MAX_POINTS points in the call -- all before the device is touched. */
+int  ygz_hip_search_by_projection(ygz_hip_ctx *ctx, int n_problems, const ygz_proj_problem *problems, const double K4[4],
+                                  const ygz_proj_params *params, int32_t *match, int32_t *dist, int32_t *pred_level, int32_t *counts);
+/* stage for tests: the candidate lists of ONE problem before any claim -- cand_idx / cand_dist [n_pt][YGZ_PROJ_TOPK] (-1 past the list),
+ * n_cand [n_pt] the candidates within th_dist (above YGZ_PROJ_TOPK: overflowed, the list holds the first YGZ_PROJ_TOPK), pred_level [n_pt];
+ * each may be NULL */
+int  ygz_hip_projection_candidates(ygz_hip_ctx *ctx, const ygz_proj_problem *problem, const double K4[4], const ygz_proj_params *params,
+                                   int32_t *cand_idx, int32_t *cand_dist, int32_t *n_cand, int32_t *pred_level);
 
 #ifdef __cplusplus
 }

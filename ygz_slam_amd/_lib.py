@@ -191,6 +191,65 @@ def _sim3_params(**kw):
     return p
 
 
+class ProjProblem(C.Structure):
+    """ygz_proj_problem (include/ygz_hip.h)"""
+    _fields_ = [("kp_px", C.POINTER(C.c_double)), ("kp_level", C.POINTER(C.c_int32)), ("kp_desc", C.POINTER(C.c_uint8)),
+                ("kp_taken", C.POINTER(C.c_uint8)), ("n_kp", C.c_int), ("pw", C.POINTER(C.c_double)), ("pt_desc", C.POINTER(C.c_uint8)),
+                ("pt_dmax", C.POINTER(C.c_double)), ("pt_normal", C.POINTER(C.c_double)), ("pt_skip", C.POINTER(C.c_uint8)), ("n_pt", C.c_int),
+                ("S", C.c_double * 8)]
+
+
+class ProjParams(C.Structure):
+    _fields_ = [("th", C.c_double), ("th_dist", C.c_int), ("claim", C.c_int)]
+
+
+def default_proj_params():
+    p = ProjParams()
+    load().ygz_hip_default_proj_params(C.byref(p))
+    return p
+
+
+def _proj_params(**kw):
+    p = default_proj_params()
+    for k, v in kw.items():
+        if v is not None:
+            setattr(p, k, v)
+    return p
+
+
+def proj_problems(problems):
+    """a ygz_proj_problem array from dicts (kp_px, kp_level, kp_desc, pw, pt_desc, pt_dmax, S; kp_taken, pt_normal, pt_skip optional or None;
+    n_kp / n_pt override the array lengths) and the arrays that must outlive it"""
+    arr = (ProjProblem * max(len(problems), 1))()
+    keep = []
+    for q, d in enumerate(problems):
+        def get(name, dtype, shape, ctype):
+            a = d.get(name)
+            if a is None:                                   # a null pointer: optional, or for the library to refuse
+                return C.POINTER(ctype)(), None
+            a = np.ascontiguousarray(a, dtype).reshape(shape)
+            keep.append(a)
+            return _p(a, ctype), len(a)
+        b = arr[q]
+        b.kp_px, nk = get("kp_px", np.float64, (-1, 2), C.c_double)
+        b.kp_level, n1 = get("kp_level", np.int32, (-1,), C.c_int32)
+        b.kp_desc, n2 = get("kp_desc", np.uint8, (-1, 32), C.c_uint8)
+        b.kp_taken, n3 = get("kp_taken", np.uint8, (-1,), C.c_uint8)
+        b.pw, npt = get("pw", np.float64, (-1, 3), C.c_double)
+        b.pt_desc, m1 = get("pt_desc", np.uint8, (-1, 32), C.c_uint8)
+        b.pt_dmax, m2 = get("pt_dmax", np.float64, (-1,), C.c_double)
+        b.pt_normal, m3 = get("pt_normal", np.float64, (-1, 3), C.c_double)
+        b.pt_skip, m4 = get("pt_skip", np.uint8, (-1,), C.c_uint8)
+        ks, ps = [v for v in (nk, n1, n2, n3) if v is not None], [v for v in (npt, m1, m2, m3, m4) if v is not None]
+        if len(set(ks)) > 1 or len(set(ps)) > 1:
+            raise ValueError("problem %d: arrays differ in length" % q)
+        b.n_kp, b.n_pt = int(d.get("n_kp", ks[0] if ks else 0)), int(d.get("n_pt", ps[0] if ps else 0))
+        if (ks and b.n_kp > ks[0]) or (ps and b.n_pt > ps[0]):
+            raise ValueError("problem %d: n_kp / n_pt above the array lengths" % q)
+        b.S = (C.c_double * 8)(*[float(v) for v in d["S"]])
+    return arr, keep
+
+
 # every symbol include/ygz_hip.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
     "ygz_hip_default_params", "ygz_hip_create", "ygz_hip_destroy", "ygz_hip_synchronize", "ygz_hip_join", "ygz_hip_set_overlap", "ygz_hip_error_string",
@@ -216,6 +275,7 @@ ABI_SYMBOLS = [
     "ygz_hip_default_init_params", "ygz_hip_initialize", "ygz_hip_init_sample_sets", "ygz_hip_init_hypotheses", "ygz_hip_init_reconstruct",
     "ygz_hip_default_pnp_params", "ygz_hip_pnp_sample_sets", "ygz_hip_pnp_ransac", "ygz_hip_pnp_hypotheses",
     "ygz_hip_default_sim3_params", "ygz_hip_sim3_ransac", "ygz_hip_sim3_hypotheses",
+    "ygz_hip_default_proj_params", "ygz_hip_search_by_projection", "ygz_hip_projection_candidates",
 ]
 INIT_SYMBOLS = ["ygz_hip_default_init_params", "ygz_hip_initialize", "ygz_hip_init_sample_sets", "ygz_hip_init_hypotheses", "ygz_hip_init_reconstruct"]
 INIT_NONE, INIT_H, INIT_F = 0, 1, 2
@@ -223,6 +283,8 @@ PNP_SYMBOLS = ["ygz_hip_default_pnp_params", "ygz_hip_pnp_sample_sets", "ygz_hip
 PNP_MAX_ITER, PNP_MAX_PROBLEMS = 1024, 64
 SIM3_SYMBOLS = ["ygz_hip_default_sim3_params", "ygz_hip_sim3_ransac", "ygz_hip_sim3_hypotheses"]
 SIM3_MAX_ITER, SIM3_MAX_PROBLEMS = 1024, 64
+PROJ_SYMBOLS = ["ygz_hip_default_proj_params", "ygz_hip_search_by_projection", "ygz_hip_projection_candidates"]
+PROJ_MAX_PROBLEMS, PROJ_TOPK, PROJ_MAX_POINTS = 64, 8, 65536
 
 SUMMARY_FIELDS = 32
 
@@ -1091,6 +1153,43 @@ class HipContext:
                                                    _p(lv, C.c_int32), len(X1), K, C.byref(prm), _p(hyp, C.c_double), _p(val, C.c_int32),
                                                    _p(cnt, C.c_int32)), "sim3_hypotheses")
         return dict(hyps=hyp, valid=val, counts=cnt)
+
+    # ---- loop closing (descriptor search guided by projection)
+
+    def search_by_projection(self, problems, K4, **params):
+        """every problem (a dict, see proj_problems) in one call (ygz_hip_search_by_projection): match, dist, pred_level [N] concatenated over
+        the problems and counts [P][2] (matches, overflowed points).  params: the fields of ygz_proj_params"""
+        arr, keep = proj_problems(problems)
+        P = len(problems)
+        N = sum(int(arr[q].n_pt) for q in range(P))
+        K = (C.c_double * 4)(*[float(v) for v in K4])
+        prm = _proj_params(**params)
+        match, dist, pred = (np.full(max(N, 1), -2, np.int32) for _ in range(3))
+        counts = np.zeros((max(P, 1), 2), np.int32)
+        ip = C.POINTER(C.c_int32)
+        self.lib.ygz_hip_search_by_projection.argtypes = [C.c_void_p, C.c_int, C.POINTER(ProjProblem), C.POINTER(C.c_double), C.POINTER(ProjParams),
+                                                          ip, ip, ip, ip]
+        self._chk(self.lib.ygz_hip_search_by_projection(self._ctx, P, arr, K, C.byref(prm), _p(match, C.c_int32), _p(dist, C.c_int32),
+                                                        _p(pred, C.c_int32), _p(counts, C.c_int32)), "search_by_projection")
+        del keep
+        return dict(match=match[:N], dist=dist[:N], pred_level=pred[:N], counts=counts[:P])
+
+    def projection_candidates(self, problem, K4, **params):
+        """the candidate lists of one problem before any claim (ygz_hip_projection_candidates): cand_idx, cand_dist [n_pt][8], n_cand [n_pt],
+        pred_level [n_pt]"""
+        arr, keep = proj_problems([problem])
+        n = int(arr[0].n_pt)
+        K = (C.c_double * 4)(*[float(v) for v in K4])
+        prm = _proj_params(**params)
+        ci, cd = np.full((max(n, 1), PROJ_TOPK), -2, np.int32), np.full((max(n, 1), PROJ_TOPK), -2, np.int32)
+        nc, pred = np.full(max(n, 1), -2, np.int32), np.full(max(n, 1), -2, np.int32)
+        ip = C.POINTER(C.c_int32)
+        self.lib.ygz_hip_projection_candidates.argtypes = [C.c_void_p, C.POINTER(ProjProblem), C.POINTER(C.c_double), C.POINTER(ProjParams),
+                                                           ip, ip, ip, ip]
+        self._chk(self.lib.ygz_hip_projection_candidates(self._ctx, arr, K, C.byref(prm), _p(ci, C.c_int32), _p(cd, C.c_int32), _p(nc, C.c_int32),
+                                                         _p(pred, C.c_int32)), "projection_candidates")
+        del keep
+        return dict(cand_idx=ci[:n], cand_dist=cd[:n], n_cand=nc[:n], pred_level=pred[:n])
 
     # ---- BoW
     def vocab_load(self, blob):

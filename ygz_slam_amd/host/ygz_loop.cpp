@@ -252,4 +252,42 @@ bool LoopClosing::ComputeSim3()
     return true;
 }
 
+// ORB-SLAM2 LoopClosing::ComputeSim3's second half.  (Re-running the 7-dof refinement on the widened pairs, as ORB-SLAM2 does between the two
+// searches, needs a refine-only entry of the C ABI: not here, S12 stays the one ComputeSim3 found.)
+bool LoopClosing::SearchLoopMapPoints()
+{
+    _current_matched.clear();
+    _loop_points.clear();
+    _stats.sim3_added = _stats.projection_added = _stats.total_matches = 0;
+    Frame *kf = _current;
+    if (!kf || !_matched || _matches.empty()) return false;
+    // 1. the refined inlier pairs, per feature of the current keyframe
+    _current_matched.assign(kf->_features.size(), nullptr);
+    map<const MapPoint *, MapPoint *> loop_of;
+    for (const auto &m : _matches) loop_of[m.first] = m.second;
+    for (size_t i = 0; i < kf->_features.size(); ++i) {
+        auto it = loop_of.find(kf->_features[i]->_mappoint);
+        if (kf->_features[i]->_mappoint && it != loop_of.end()) _current_matched[i] = it->second;
+    }
+    // 2. more pairs with the loop keyframe itself, by mutual projection with S12
+    _stats.sim3_added = _matcher.SearchBySim3(kf, _matched, _current_matched, _S12, _option._sim3_search_th);
+    // 3. the loop map points: the matched keyframe and its connected keyframes by keyframe id, features by index, each point once
+    vector<Frame *> group(1, _matched);
+    for (const auto &c : _matched->_connected_keyframe_weights)
+        if (c.first && !c.first->_bad && c.first != _matched) group.push_back(c.first);
+    std::sort(group.begin(), group.end(), [](const Frame *a, const Frame *b) { return a->_keyframe_id < b->_keyframe_id; });
+    std::set<MapPoint *> seen;
+    for (Frame *g : group)
+        for (Feature *f : g->_features) {
+            MapPoint *mp = f->_mappoint;
+            if (!mp || mp->_bad || !seen.insert(mp).second) continue;
+            _loop_points.push_back(mp);
+        }
+    // 4. pulled into the current keyframe with the corrected pose
+    _stats.projection_added = _matcher.SearchByProjection(kf, _Scw, _loop_points, _current_matched, _option._projection_search_th);
+    // 5. enough matches in total
+    for (const MapPoint *mp : _current_matched) if (mp) ++_stats.total_matches;
+    return _stats.total_matches >= _option._min_total_matches;
+}
+
 }  // namespace ygz

@@ -1,0 +1,204 @@
+// Matcher::SearchByProjection / SearchBySim3 / SearchFuseCandidates (include/ygz/Algorithm/Matcher.h): nothing in the reference; ORB-SLAM2's
+// ORBmatcher::SearchByProjection(pKF, Scw, ...), SearchBySim3 and Fuse(pKF, Scw, ...) as gathers on the host around one device call each
+// (ygz_hip_search_by_projection, ygz_slam_amd/csrc/proj.hip).  A problem has one point per source (a map point, or a feature of the source
+// keyframe), so the device's indices are the caller's; what a method skips becomes pt_skip, what it excludes as a target becomes kp_taken.
+// Error conventions of the other surfaces: a failed call logs and returns 0, only a missing device throws.
+#include "ygz/Basic.h"
+#include "ygz/Algorithm/Matcher.h"
+#include "ygz/hip/Runtime.h"
+#include "ygz_hip.h"
+#include <algorithm>
+#include <cstring>
+
+namespace ygz {
+
+namespace {
+// ORBmatcher::TH_LOW / TH_HIGH.  Not _options.th_low / th_high: those follow the reference's configuration (65 / 100 by default) and belong to
+// its BoW searches
+const int kThLow = 50, kThHigh = 100;
+
+bool good(const MapPoint *mp) { return mp && !mp->_bad; }
+
+struct Problem {
+    vector<double> kp_px, pw, dmax, normal;
+    vector<int32_t> kp_level;
+    vector<uint8_t> kp_desc, kp_taken, pt_desc, skip;
+    bool with_normal = false;
+    double S[8];
+
+    void keypoints(const Frame *kf)
+    {
+        const size_t n = kf->_features.size();
+        kp_px.resize(2 * n); kp_level.resize(n); kp_desc.assign(32 * n, 0); kp_taken.assign(n, 0);
+        for (size_t i = 0; i < n; ++i) {
+            const Feature *f = kf->_features[i];
+            kp_px[2 * i] = f->_pixel[0]; kp_px[2 * i + 1] = f->_pixel[1];
+            kp_level[i] = std::max(f->_level, 0);
+            if (f->_desc.data && f->_desc.rows * f->_desc.cols >= 32) memcpy(&kp_desc[32 * i], f->_desc.data, 32);
+            else kp_taken[i] = 1;                                     // no descriptor: never a candidate
+        }
+    }
+    // one more point: a skipped one (skip set, or no usable observation) carries zeros
+    void point(const MapPoint *mp, bool skip_it)
+    {
+        Matcher::PointAttr a;
+        const bool use = !skip_it && Matcher::PointAttributes(mp, a);
+        const size_t i = skip.size();
+        skip.push_back(use ? 0 : 1);
+        pw.resize(3 * (i + 1), 0.0); normal.resize(3 * (i + 1), 0.0); pt_desc.resize(32 * (i + 1), 0); dmax.push_back(use ? a.dmax : 1.0);
+        if (!use) return;
+        for (int k = 0; k < 3; ++k) { pw[3 * i + k] = mp->_pos_world[k]; normal[3 * i + k] = a.normal[k]; }
+        memcpy(&pt_desc[32 * i], a.desc, 32);
+    }
+    ygz_proj_problem view() const
+    {
+        ygz_proj_problem b;
+        b.kp_px = kp_px.data(); b.kp_level = kp_level.data(); b.kp_desc = kp_desc.data(); b.kp_taken = kp_taken.data();
+        b.n_kp = (int)kp_level.size();
+        b.pw = pw.data(); b.pt_desc = pt_desc.data(); b.pt_dmax = dmax.data(); b.pt_normal = with_normal ? normal.data() : nullptr;
+        b.pt_skip = skip.data(); b.n_pt = (int)skip.size();
+        for (int k = 0; k < 8; ++k) b.S[k] = S[k];
+        return b;
+    }
+};
+
+bool camera_K4(double K4[4])
+{
+    if (Frame::GetCamera() == nullptr) return false;
+    const Matrix3d K = Frame::GetCamera()->GetCameraMatrix();
+    K4[0] = K(0, 0); K4[1] = K(1, 1); K4[2] = K(0, 2); K4[3] = K(1, 2);
+    return true;
+}
+
+// (R, t / s, 1) of S: the target camera in the units of the points' world (ORB-SLAM2: tcw = Scw.col(3) / scw)
+void unscaled(const Sim3 &S, double out[8]) { Sim3(S.R, S.t / S.s, 1.0).to8(out); }
+}
+
+bool Matcher::PointAttributes(const MapPoint *mp, PointAttr &out)
+{
+    if (!mp) return false;
+    const Feature *ref = nullptr;
+    Vector3d sum(0, 0, 0);
+    int n = 0;
+    for (const auto &ob : mp->_obs) {                                   // key order
+        const Feature *f = ob.second;
+        if (!f || !f->_frame) continue;
+        if (!ref) ref = f;
+        const Vector3d ray = mp->_pos_world - f->_frame->GetCamCenter();
+        sum += ray / ray.norm();
+        ++n;
+    }
+    if (!ref) return false;
+    const Mat &dd = mp->_distinctive_desc;
+    const Mat &d = (dd.data && dd.rows * dd.cols * (int)dd.elemSize() == 32) ? dd : ref->_desc;
+    if (!d.data || d.rows * d.cols * (int)d.elemSize() < 32) return false;
+    memcpy(out.desc, d.data, 32);
+    out.dmax = (mp->_pos_world - ref->_frame->GetCamCenter()).norm() * (double)(1 << std::max(ref->_level, 0));
+    out.normal = sum / (double)n;
+    return true;
+}
+
+int Matcher::SearchByProjection(Frame *kf, const Sim3 &Scw, const vector<MapPoint *> &points, vector<MapPoint *> &matched, float th)
+{
+    double K4[4];
+    if (!kf || kf->_features.empty() || points.empty() || !camera_K4(K4)) return 0;
+    matched.resize(kf->_features.size(), nullptr);
+    Problem pb;
+    pb.with_normal = true;
+    pb.keypoints(kf);
+    std::set<const MapPoint *> have;
+    for (size_t i = 0; i < matched.size(); ++i)
+        if (matched[i]) { pb.kp_taken[i] = 1; have.insert(matched[i]); }
+    for (const MapPoint *mp : points) pb.point(mp, !good(mp) || have.count(mp) > 0);
+    unscaled(Scw, pb.S);
+    ygz_proj_params prm;
+    ygz_hip_default_proj_params(&prm);
+    prm.th = th; prm.th_dist = kThLow; prm.claim = 1;
+    const ygz_proj_problem b = pb.view();
+    vector<int32_t> m(points.size(), -1);
+    if (!hip::check(ygz_hip_search_by_projection(hip::Runtime::Get().ctx(), 1, &b, K4, &prm, m.data(), nullptr, nullptr, nullptr), "search_by_projection"))
+        return 0;
+    int found = 0;
+    for (size_t i = 0; i < points.size(); ++i)
+        if (m[i] >= 0) { matched[m[i]] = points[i]; ++found; }
+    return found;
+}
+
+int Matcher::SearchBySim3(Frame *kf1, Frame *kf2, vector<MapPoint *> &matches12, const Sim3 &S12, float th)
+{
+    double K4[4];
+    if (!kf1 || !kf2 || kf1->_features.empty() || kf2->_features.empty() || !camera_K4(K4)) return 0;
+    const size_t n1 = kf1->_features.size(), n2 = kf2->_features.size();
+    matches12.resize(n1, nullptr);
+    std::set<const MapPoint *> have2;
+    for (const MapPoint *mp : matches12) if (mp) have2.insert(mp);
+    Problem a, b;                                                    // a: kf1's points into kf2; b: kf2's points into kf1
+    a.keypoints(kf2); b.keypoints(kf1);
+    for (size_t j = 0; j < n2; ++j) if (!good(kf2->_features[j]->_mappoint)) a.kp_taken[j] = 1;       // a pair needs a map point on both sides
+    for (size_t i = 0; i < n1; ++i) if (!good(kf1->_features[i]->_mappoint)) b.kp_taken[i] = 1;
+    for (size_t i = 0; i < n1; ++i) { const MapPoint *mp = kf1->_features[i]->_mappoint; a.point(mp, !good(mp) || matches12[i] != nullptr); }
+    for (size_t j = 0; j < n2; ++j) { const MapPoint *mp = kf2->_features[j]->_mappoint; b.point(mp, !good(mp) || have2.count(mp) > 0); }
+    (S12.inverse() * kf1->_TCW).to8(a.S);
+    (S12 * kf2->_TCW).to8(b.S);
+    ygz_proj_params prm;
+    ygz_hip_default_proj_params(&prm);
+    prm.th = th; prm.th_dist = kThHigh; prm.claim = 0;
+    const ygz_proj_problem pbs[2] = { a.view(), b.view() };
+    vector<int32_t> m(n1 + n2, -1);
+    if (!hip::check(ygz_hip_search_by_projection(hip::Runtime::Get().ctx(), 2, pbs, K4, &prm, m.data(), nullptr, nullptr, nullptr), "search_by_sim3"))
+        return 0;
+    int found = 0;
+    for (size_t i = 0; i < n1; ++i) {
+        const int j = m[i];
+        if (j < 0 || m[n1 + (size_t)j] != (int)i) continue;           // both directions agree
+        matches12[i] = kf2->_features[j]->_mappoint;
+        ++found;
+    }
+    return found;
+}
+
+int Matcher::SearchFuseCandidates(const vector<Frame *> &kfs, const vector<Sim3> &Scw, const vector<MapPoint *> &points, float th,
+                                  vector<vector<int>> &feature_of_point)
+{
+    double K4[4];
+    feature_of_point.assign(kfs.size(), vector<int>(points.size(), -1));
+    if (kfs.empty() || kfs.size() != Scw.size() || points.empty() || points.size() > YGZ_PROJ_MAX_POINTS || !camera_K4(K4)) return 0;
+    ygz_proj_params prm;
+    ygz_hip_default_proj_params(&prm);
+    prm.th = th; prm.th_dist = kThLow; prm.claim = 0;
+    // as many keyframes per call as the call holds (problems and points)
+    const size_t per_call = std::min<size_t>(YGZ_PROJ_MAX_PROBLEMS, YGZ_PROJ_MAX_POINTS / points.size());
+    int found = 0;
+    for (size_t k0 = 0; k0 < kfs.size(); k0 += per_call) {
+        const size_t k1 = std::min(kfs.size(), k0 + per_call);
+        vector<Problem> pbs;
+        vector<size_t> owner;
+        for (size_t k = k0; k < k1; ++k) {
+            Frame *kf = kfs[k];
+            if (!kf || kf->_features.empty()) continue;
+            pbs.emplace_back();
+            Problem &pb = pbs.back();
+            pb.with_normal = true;
+            pb.keypoints(kf);
+            for (const MapPoint *mp : points) pb.point(mp, !good(mp) || mp->_obs.count(kf->_keyframe_id) > 0);
+            unscaled(Scw[k], pb.S);
+            owner.push_back(k);
+        }
+        if (pbs.empty()) continue;
+        vector<ygz_proj_problem> views;
+        for (const Problem &pb : pbs) views.push_back(pb.view());
+        vector<int32_t> m(pbs.size() * points.size(), -1);
+        if (!hip::check(ygz_hip_search_by_projection(hip::Runtime::Get().ctx(), (int)views.size(), views.data(), K4, &prm, m.data(), nullptr, nullptr,
+                                                     nullptr), "search_fuse_candidates"))
+            return 0;
+        for (size_t q = 0; q < pbs.size(); ++q)
+            for (size_t i = 0; i < points.size(); ++i) {
+                const int j = m[q * points.size() + i];
+                feature_of_point[owner[q]][i] = j;
+                if (j >= 0) ++found;
+            }
+    }
+    return found;
+}
+
+}  // namespace ygz
