@@ -4,8 +4,12 @@
 // covisibility-group consistency) and LoopClosing::ComputeSim3 (SearchByBoW per candidate, then Sim3 RANSAC and the 7-dof refinement of every
 // candidate in one device call, ygz_hip_sim3_ransac) with its second half, SearchLoopMapPoints: the accepted candidate's pairs widened by
 // Matcher::SearchBySim3, then the map points of the loop keyframe's neighbourhood pulled in by Matcher::SearchByProjection, and the "enough
-// matches in total" decision.  It detects only: no pose, map point, feature, observation or connection changes
-// (ygz_slam_amd/host/ygz_loop.cpp; the integration is in INTEGRATION.md).
+// matches in total" decision.  Those three detect only: no pose, map point, feature, observation or connection changes
+// (ygz_slam_amd/host/ygz_loop.cpp).  CorrectLoop is the correcting half of ORB-SLAM2's LoopClosing::CorrectLoop: the Sim3 of the accepted loop
+// is propagated to the current keyframe's neighbourhood, a Sim3 pose graph over the keyframes (Optimizer::OptimizeEssentialGraph's edges) is
+// optimised in one device call (ygz_hip_pose_graph_optimize), and the keyframe poses and map points are rewritten from the result
+// (ygz_slam_amd/host/ygz_correct.cpp).  Fusing duplicated map points, covisibility updates and a global BA are not part of it.  The
+// integration is in INTEGRATION.md.
 #ifndef YGZ_LOOP_CLOSING_H_
 #define YGZ_LOOP_CLOSING_H_
 
@@ -42,6 +46,7 @@ public:
         int _min_total_matches = 40;            // matches of the current keyframe SearchLoopMapPoints needs to accept the loop
         float _sim3_search_th = 7.5f;           // SearchBySim3's window, level-0 pixels
         float _projection_search_th = 10.0f;    // SearchByProjection's
+        int _min_essential_weight = 100;        // CorrectLoop: connected pairs with at least this weight get an edge (ORB-SLAM2's minFeat)
     } _option;
 
     struct Stats
@@ -57,6 +62,28 @@ public:
         int sim3_added = 0;                     // last SearchLoopMapPoints: pairs SearchBySim3 added to the refined inliers
         int projection_added = 0;               // matches SearchByProjection added from the loop map points
         int total_matches = 0;                  // features of the current keyframe with a loop map point
+        // the last CorrectLoop
+        int correct_vertices = 0;               // keyframes in the pose graph
+        int correct_tree_edges = 0;             // one per keyframe with a connected keyframe of smaller id
+        int correct_covisibility_edges = 0;     // connected pairs of weight >= _min_essential_weight without a tree edge
+        int correct_loop_edges = 0;             // 1
+        vector<unsigned long> correct_left_out; // keyframes given that have no edge: untouched
+        int correct_points_moved = 0;
+        struct PoseGraphResult                  // ygz_pgo_result's fields
+        {
+            int status = 0, lm_iterations = 0, n_solves = 0, cg_iterations_total = 0, cg_capped = 0;
+            double cost_initial = 0, cost_final = 0, lambda = 0;
+        } pose_graph;
+    };
+
+    // the pose graph of the last CorrectLoop that reached the solver, as it was handed over and as it came back
+    struct PoseGraph
+    {
+        vector<unsigned long> keyframe_ids;     // per vertex, ascending
+        vector<double> S, S_out;                // [N][8] qx qy qz qw tx ty tz s, world -> camera
+        vector<uint8_t> fixed;                  // [N]
+        vector<int32_t> edges;                  // [E][2] vertex indices (i, j)
+        vector<double> M;                       // [E][8] ~ S_j o S_i^-1
     };
 
     // kf: a keyframe of the map with its covisibility (_connected_keyframe_weights); true when some loop candidate is consistent enough
@@ -69,6 +96,24 @@ public:
     // (keyframes in _keyframe_id order, features in index order, each point once) are the loop map points, SearchByProjection(current, S_cw,
     // loop points, ..., 10) pulls them in; true when the matches reach _min_total_matches.  Changes nothing in the map.
     bool SearchLoopMapPoints();
+    // valid once after a ComputeSim3() that returned true (SearchLoopMapPoints is not needed); otherwise false and nothing changes, a second
+    // call for the same loop included.  Ties go by _keyframe_id, never by address.
+    //  vertices: the keyframes given that are not bad, by id; one without an edge is left out and untouched (Stats::correct_left_out)
+    //  estimate: the current keyframe GetCorrectedPose(); each keyframe connected to it (but the matched one) Sim3(T_iw T_wc) o S_cw; the
+    //            others Sim3(T_iw)
+    //  edges (i, j) with M = Sim3(T_jw T_iw^-1) of the poses before the correction; a pair is connected with the larger of the two weights
+    //            the keyframes hold for each other: per keyframe i its connected keyframe j of smaller id with the largest weight (ties: the
+    //            smaller id) -- no fallback to the previous id; then every connected pair of weight >= _min_essential_weight without such an
+    //            edge, i the larger id; last the loop edge current -> matched with M = Sim3(T_mw) o S_cw^-1
+    //  fixed:    the matched keyframe; _fix_scale is passed on
+    //  one ygz_hip_pose_graph_optimize call; on an error or status failed: false, the map untouched
+    //  poses:    T_iw <- (R, t / s) of every vertex but the fixed one
+    //  points:   keyframes by id, features by index, each good point once: its reference keyframe r is that of the _obs entry with the lowest
+    //            key that has a feature whose frame is a vertex (Matcher::PointAttributes' rule); P <- S_rw^-1 (T_rw P) with the new S_rw and
+    //            the old T_rw, unless S_rw did not change; a point without such an entry stays
+    bool CorrectLoop(const vector<Frame *> &keyframes);
+    bool CorrectLoop();                     // every keyframe registered in Memory
+    const PoseGraph &GetPoseGraph() const { return _pose_graph; }
 
     Frame *GetMatchedKeyframe() const { return _matched; }
     const Sim3 &GetSim3() const { return _S12; }                      // loop keyframe's camera -> current keyframe's camera
@@ -90,6 +135,8 @@ private:
     Sim3 _S12, _Scw;
     vector<pair<MapPoint *, MapPoint *>> _matches;
     vector<MapPoint *> _current_matched, _loop_points;
+    bool _correctable = false;                                        // an accepted loop that no CorrectLoop has used yet
+    PoseGraph _pose_graph;
     Stats _stats;
 };
 

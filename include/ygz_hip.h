@@ -48,7 +48,9 @@ extern "C" {
  * Still 6: the loop detection's Sim3 RANSAC added (ygz_sim3_params, ygz_sim3_result, ygz_hip_default_sim3_params, ygz_hip_sim3_ransac,
  * ygz_hip_sim3_hypotheses) -- no existing argument list changed.
  * Still 6: the projection-guided descriptor search added (ygz_proj_problem, ygz_proj_params, ygz_hip_default_proj_params,
- * ygz_hip_search_by_projection, ygz_hip_projection_candidates) -- no existing argument list changed. */
+ * ygz_hip_search_by_projection, ygz_hip_projection_candidates) -- no existing argument list changed.
+ * Still 6: the Sim3 pose-graph optimiser added (ygz_pgo_params, ygz_pgo_result, ygz_hip_default_pgo_params, ygz_hip_pose_graph_optimize,
+ * ygz_hip_pgo_linearize) -- no existing argument list changed. */
 #define YGZ_HIP_ABI_VERSION 6
 
 typedef struct ygz_hip_ctx ygz_hip_ctx;
@@ -790,6 +792,48 @@ int  ygz_hip_search_by_projection(ygz_hip_ctx *ctx, int n_problems, const ygz_pr
  * each may be NULL */
 int  ygz_hip_projection_candidates(ygz_hip_ctx *ctx, const ygz_proj_problem *problem, const double K4[4], const ygz_proj_params *params,
                                    int32_t *cand_idx, int32_t *cand_dist, int32_t *n_cand, int32_t *pred_level);
+
+/* ---- loop correction: Sim3 pose-graph optimisation -- nothing in the reference; ORB-SLAM2's Optimizer::OptimizeEssentialGraph.  N vertices
+ * S [N][8] (qx qy qz qw tx ty tz s, world -> camera i), E edges (i, j) = edges [E][2] with a measurement M [E][8] ~ S_j o S_i^-1, fixed [N]
+ * (non-zero: the vertex is not moved).  Minimises the sum over the edges of |lift(M o S_i o S_j^-1)|^2 (identity information) by
+ * Levenberg-Marquardt with g2o's rules; every step is solved by block-Jacobi preconditioned conjugate gradients on (J^T J + lambda I) d = b
+ * without assembling J^T J; the update is S_i <- Delta(d_i) o S_i with the Delta of the Sim3 refinement, lift is its inverse.  One resident
+ * workgroup runs the whole loop.  The arithmetic is that of tests/pgo_ref.c: every output is bit-identical to it. */
+#define YGZ_PGO_MAX_VERTICES 4096
+#define YGZ_PGO_MAX_EDGES    32768
+#define YGZ_PGO_FAILED         0          /* the residual is undefined at the input (a rotation error of 180 degrees, a non-finite value): S_out = S */
+#define YGZ_PGO_CONVERGED      1          /* an accepted step lowered the cost by at most min_rel_decrease times the cost */
+#define YGZ_PGO_MAX_ITERATIONS 2          /* max_iterations ran */
+#define YGZ_PGO_STALLED        3          /* max_trials rejected steps in a row, a step that left the cost unchanged, or lambda overflowed */
+typedef struct {
+    int32_t max_iterations;               /* 20: LM iterations (ORB-SLAM2's optimize(20)), in [1, 1000] */
+    int32_t max_trials;                   /* 10: trials of lambda per iteration, in [1, 100] */
+    int32_t cg_max_iterations;            /* 0: min(7 free vertices, 2048); else the cap itself, up to 65536 */
+    int32_t fix_scale;                    /* 0; 1: no vertex changes its scale (6-dof) */
+    double  cg_tol;                       /* 1e-8: CG stops at r^T z <= cg_tol^2 r0^T z0; in (0, 1) */
+    double  min_rel_decrease;             /* 1e-9: in [0, 1) */
+} ygz_pgo_params;
+typedef struct {
+    double  cost_initial, cost_final;     /* the sum of squared residuals at S and at S_out */
+    double  lambda;                       /* the final damping */
+    int32_t status;                       /* YGZ_PGO_* */
+    int32_t lm_iterations;
+    int32_t n_solves;                     /* CG solves (trials whose preconditioner could be factored) */
+    int32_t cg_iterations_total;
+    int32_t cg_capped;                    /* solves that ended at the cap (not an error: the iterate is used) */
+    int32_t pad;
+} ygz_pgo_result;
+void ygz_hip_default_pgo_params(ygz_pgo_params *p);
+/* the whole optimisation: params NULL: defaults; S_out [N][8].  One upload, one launch, one copy back and one wait.  Checked in this order,
+ * all before the device is touched: YGZ_E_INVALID for a null array or result; YGZ_E_CAPACITY above YGZ_PGO_MAX_VERTICES vertices or
+ * YGZ_PGO_MAX_EDGES edges; YGZ_E_INVALID for N < 2, E < 1, no free vertex, an edge with i = j or an index out of range, a free vertex
+ * without an edge, a scale <= 0 or a non-finite value in S or M, a parameter out of its range; last, YGZ_E_INVALID for a null context. */
+int  ygz_hip_pose_graph_optimize(ygz_hip_ctx *ctx, int n_vertices, const double *S, const uint8_t *fixed, int n_edges, const int32_t *edges,
+                                 const double *M, const ygz_pgo_params *params, double *S_out, ygz_pgo_result *result);
+/* stage for tests: the linearisation at S -- residuals [E][7], Ji and Jj [E][49] (dr / dd_i and dr / dd_j, row-major), cost [1]; each may
+ * be NULL.  The same checks.  Returns YGZ_E_STATE when the residual is undefined at S (the outputs are zero for such an edge). */
+int  ygz_hip_pgo_linearize(ygz_hip_ctx *ctx, int n_vertices, const double *S, const uint8_t *fixed, int n_edges, const int32_t *edges,
+                           const double *M, const ygz_pgo_params *params, double *residuals, double *Ji, double *Jj, double *cost);
 
 #ifdef __cplusplus
 }

@@ -250,6 +250,54 @@ def proj_problems(problems):
     return arr, keep
 
 
+class PgoParams(C.Structure):
+    """ygz_pgo_params (include/ygz_hip.h)"""
+    _fields_ = [("max_iterations", C.c_int32), ("max_trials", C.c_int32), ("cg_max_iterations", C.c_int32), ("fix_scale", C.c_int32),
+                ("cg_tol", C.c_double), ("min_rel_decrease", C.c_double)]
+
+
+class PgoResult(C.Structure):
+    """ygz_pgo_result; `lambda_` is the header's `lambda`"""
+    _fields_ = [("cost_initial", C.c_double), ("cost_final", C.c_double), ("lambda_", C.c_double), ("status", C.c_int32),
+                ("lm_iterations", C.c_int32), ("n_solves", C.c_int32), ("cg_iterations_total", C.c_int32), ("cg_capped", C.c_int32),
+                ("pad", C.c_int32)]
+
+    def to_dict(self):
+        return dict((k, getattr(self, k)) for k, _ in self._fields_ if k != "pad")
+
+
+def default_pgo_params():
+    p = PgoParams()
+    load().ygz_hip_default_pgo_params(C.byref(p))
+    return p
+
+
+def _pgo_params(**kw):
+    p = default_pgo_params()
+    for k, v in kw.items():
+        if v is not None:
+            setattr(p, k, v)
+    return p
+
+
+def pgo_arrays(S, fixed, edges, M):
+    """the four arrays of a pose graph in the ABI's types: S [N][8], fixed [N] uint8, edges [E][2] int32, M [E][8]"""
+    S = np.ascontiguousarray(S, np.float64).reshape(-1, 8)
+    M = np.ascontiguousarray(M, np.float64).reshape(-1, 8)
+    fixed = np.ascontiguousarray(fixed, np.uint8).reshape(-1)
+    edges = np.ascontiguousarray(edges, np.int32).reshape(-1, 2)
+    if len(S) != len(fixed) or len(edges) != len(M):
+        raise ValueError("S / fixed or edges / M differ in length")
+    return S, fixed, edges, M
+
+
+def pgo_argtypes(lib):
+    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    lib.ygz_hip_pose_graph_optimize.argtypes = [C.c_void_p, C.c_int, dp, C.POINTER(C.c_uint8), C.c_int, ip, dp, C.POINTER(PgoParams), dp,
+                                                C.POINTER(PgoResult)]
+    lib.ygz_hip_pgo_linearize.argtypes = [C.c_void_p, C.c_int, dp, C.POINTER(C.c_uint8), C.c_int, ip, dp, C.POINTER(PgoParams), dp, dp, dp, dp]
+
+
 # every symbol include/ygz_hip.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
     "ygz_hip_default_params", "ygz_hip_create", "ygz_hip_destroy", "ygz_hip_synchronize", "ygz_hip_join", "ygz_hip_set_overlap", "ygz_hip_error_string",
@@ -276,6 +324,7 @@ ABI_SYMBOLS = [
     "ygz_hip_default_pnp_params", "ygz_hip_pnp_sample_sets", "ygz_hip_pnp_ransac", "ygz_hip_pnp_hypotheses",
     "ygz_hip_default_sim3_params", "ygz_hip_sim3_ransac", "ygz_hip_sim3_hypotheses",
     "ygz_hip_default_proj_params", "ygz_hip_search_by_projection", "ygz_hip_projection_candidates",
+    "ygz_hip_default_pgo_params", "ygz_hip_pose_graph_optimize", "ygz_hip_pgo_linearize",
 ]
 INIT_SYMBOLS = ["ygz_hip_default_init_params", "ygz_hip_initialize", "ygz_hip_init_sample_sets", "ygz_hip_init_hypotheses", "ygz_hip_init_reconstruct"]
 INIT_NONE, INIT_H, INIT_F = 0, 1, 2
@@ -285,6 +334,9 @@ SIM3_SYMBOLS = ["ygz_hip_default_sim3_params", "ygz_hip_sim3_ransac", "ygz_hip_s
 SIM3_MAX_ITER, SIM3_MAX_PROBLEMS = 1024, 64
 PROJ_SYMBOLS = ["ygz_hip_default_proj_params", "ygz_hip_search_by_projection", "ygz_hip_projection_candidates"]
 PROJ_MAX_PROBLEMS, PROJ_TOPK, PROJ_MAX_POINTS = 64, 8, 65536
+PGO_SYMBOLS = ["ygz_hip_default_pgo_params", "ygz_hip_pose_graph_optimize", "ygz_hip_pgo_linearize"]
+PGO_MAX_VERTICES, PGO_MAX_EDGES = 4096, 32768
+PGO_FAILED, PGO_CONVERGED, PGO_MAX_ITERATIONS, PGO_STALLED = 0, 1, 2, 3
 
 SUMMARY_FIELDS = 32
 
@@ -1190,6 +1242,34 @@ class HipContext:
                                                          _p(pred, C.c_int32)), "projection_candidates")
         del keep
         return dict(cand_idx=ci[:n], cand_dist=cd[:n], n_cand=nc[:n], pred_level=pred[:n])
+
+    # ---- loop correction (Sim3 pose-graph optimisation)
+
+    def pose_graph_optimize(self, S, fixed, edges, M, **params):
+        """the whole optimisation in one call (ygz_hip_pose_graph_optimize): dict(S [N][8], and the fields of ygz_pgo_result).  params: the
+        fields of ygz_pgo_params"""
+        S, fixed, edges, M = pgo_arrays(S, fixed, edges, M)
+        prm, res, out = _pgo_params(**params), PgoResult(), np.zeros_like(S)
+        pgo_argtypes(self.lib)
+        self._chk(self.lib.ygz_hip_pose_graph_optimize(self._ctx, len(S), _p(S, C.c_double), _p(fixed, C.c_uint8), len(edges), _p(edges, C.c_int32),
+                                                       _p(M, C.c_double), C.byref(prm), _p(out, C.c_double), C.byref(res)), "pose_graph_optimize")
+        d = res.to_dict()
+        d["S"] = out
+        return d
+
+    def pgo_linearize(self, S, fixed, edges, M, **params):
+        """the linearisation at S (ygz_hip_pgo_linearize): dict(ok, res [E][7], Ji, Jj [E][7][7], cost); ok is False when the residual is
+        undefined at S"""
+        S, fixed, edges, M = pgo_arrays(S, fixed, edges, M)
+        E = len(edges)
+        prm = _pgo_params(**params)
+        res, Ji, Jj, cost = np.zeros((E, 7)), np.zeros((E, 7, 7)), np.zeros((E, 7, 7)), np.zeros(1)
+        pgo_argtypes(self.lib)
+        rc = self.lib.ygz_hip_pgo_linearize(self._ctx, len(S), _p(S, C.c_double), _p(fixed, C.c_uint8), E, _p(edges, C.c_int32), _p(M, C.c_double),
+                                            C.byref(prm), _p(res, C.c_double), _p(Ji, C.c_double), _p(Jj, C.c_double), _p(cost, C.c_double))
+        if rc != E_STATE:
+            self._chk(rc, "pgo_linearize")
+        return dict(ok=rc == OK, res=res, Ji=Ji, Jj=Jj, cost=float(cost[0]))
 
     # ---- BoW
     def vocab_load(self, blob):

@@ -170,6 +170,7 @@ bool LoopClosing::DetectLoop(Frame *kf, const vector<Frame *> &keyframes)
 bool LoopClosing::ComputeSim3()
 {
     _matched = nullptr;
+    _correctable = false;
     _S12 = Sim3(); _Scw = Sim3();
     _matches.clear();
     _stats.bow_pairs.clear(); _stats.ransac_inliers.clear(); _stats.refined_inliers.clear();
@@ -249,6 +250,7 @@ bool LoopClosing::ComputeSim3()
     for (size_t k = 0; k < best->pairs.size(); ++k)
         if (mask[best->first + k] & 2) _matches.push_back(make_pair(best->pairs[k].first->_mappoint, best->pairs[k].second->_mappoint));
     _last_loop_kf_id = kf->_keyframe_id;
+    _correctable = true;
     return true;
 }
 
