@@ -8,8 +8,12 @@
 // (ygz_slam_amd/host/ygz_loop.cpp).  CorrectLoop is the correcting half of ORB-SLAM2's LoopClosing::CorrectLoop: the Sim3 of the accepted loop
 // is propagated to the current keyframe's neighbourhood, a Sim3 pose graph over the keyframes (Optimizer::OptimizeEssentialGraph's edges) is
 // optimised in one device call (ygz_hip_pose_graph_optimize), and the keyframe poses and map points are rewritten from the result
-// (ygz_slam_amd/host/ygz_correct.cpp).  Fusing duplicated map points, covisibility updates and a global BA are not part of it.  The
-// integration is in INTEGRATION.md.
+// (ygz_slam_amd/host/ygz_correct.cpp).  FuseLoop is the rest of ORB-SLAM2's CorrectLoop up to, but not including, the global BA: the
+// duplicated map points of the revisited region are fused into the old ones (the current keyframe's matches, then Matcher::
+// SearchFuseCandidates over the corrected neighbourhood), the surviving points' distinctive descriptors are recomputed
+// (Matcher::ComputeDistinctiveDescriptors, ygz_hip_distinctive_descriptors) and the covisibility of every keyframe it touched is recounted
+// (UpdateCovisibility, ygz_hip_covisibility) -- ygz_slam_amd/host/ygz_fuse.cpp.  The new connections are not fed back into the pose graph
+// and no global BA follows.  The integration is in INTEGRATION.md.
 #ifndef YGZ_LOOP_CLOSING_H_
 #define YGZ_LOOP_CLOSING_H_
 
@@ -47,6 +51,7 @@ public:
         float _sim3_search_th = 7.5f;           // SearchBySim3's window, level-0 pixels
         float _projection_search_th = 10.0f;    // SearchByProjection's
         int _min_essential_weight = 100;        // CorrectLoop: connected pairs with at least this weight get an edge (ORB-SLAM2's minFeat)
+        float _fuse_search_th = 4.0f;           // FuseLoop: SearchFuseCandidates' window, level-0 pixels (ORB-SLAM2's SearchAndFuse)
     } _option;
 
     struct Stats
@@ -74,7 +79,21 @@ public:
             int status = 0, lm_iterations = 0, n_solves = 0, cg_iterations_total = 0, cg_capped = 0;
             double cost_initial = 0, cost_final = 0, lambda = 0;
         } pose_graph;
+        // the last FuseLoop
+        int fuse_current_replaced = 0;          // step 1: points of the current keyframe replaced by their loop map point
+        int fuse_current_added = 0;             // step 1: loop map points given to a feature without a good point
+        int fuse_targets = 0;                   // keyframes SearchFuseCandidates looked into
+        int fuse_hits = 0;                      // its (keyframe, point) hits
+        int fuse_replaced = 0;                  // step 3: points replaced
+        int fuse_added = 0;                     // step 3: observations added
+        int fuse_conflicts = 0;                 // matches and hits skipped: the loop point is already observed there, or is bad, or the feature holds another loop point
+        int fuse_descriptors = 0;               // points whose _distinctive_desc was set
+        int fuse_rows = 0;                      // keyframes whose covisibility was rewritten
     };
+
+    // one action of FuseLoop: feature `feature` of keyframe `keyframe_id` now observes loop map point `loop_point_id`; `replaced_point_id`
+    // is the point it held before (now bad), -1 when it held none
+    struct FusedPair { unsigned long keyframe_id; int feature; unsigned long loop_point_id; long replaced_point_id; };
 
     // the pose graph of the last CorrectLoop that reached the solver, as it was handed over and as it came back
     struct PoseGraph
@@ -115,6 +134,35 @@ public:
     bool CorrectLoop();                     // every keyframe registered in Memory
     const PoseGraph &GetPoseGraph() const { return _pose_graph; }
 
+    // ORB-SLAM2's MapPoint::Replace on this data model; pure host code.  Nothing happens when the two are equal or either is null.  For each
+    // (id, f) of from->_obs in key order: when into->_obs has no entry for id, f->_mappoint = into and into->_obs[id] = f; otherwise
+    // f->_mappoint = nullptr.  into's _cnt_found and _cnt_visible grow by from's; from->_bad = true and from->_obs is cleared.  Nothing is deleted.
+    static void ReplaceMapPoint(MapPoint *from, MapPoint *into);
+    // recounts the covisibility of `rows` on the device (ygz_hip_covisibility, in chunks of rows when rows x K is above its cell cap).  The
+    // universe is the keyframes given that are not bad, once each, by id; the points are the good map points of their features, each once; a
+    // point's list is its _obs keys that belong to the universe.  Each row keyframe of the universe is rewritten by Frame::UpdateConnections'
+    // rules: nothing changes when it shares nothing; _connected_keyframe_weights holds every non-zero count; _cov_keyframes / _cov_weights the
+    // counts >= 15, heaviest first, equal weights by the smaller id; when no count reaches 15 the single largest (the smaller id of equals),
+    // and that keyframe gets AddConnection.  Returns the rows rewritten.
+    int UpdateCovisibility(const vector<Frame *> &rows, const vector<Frame *> &keyframes);
+    // valid once, after a CorrectLoop that returned true for a loop on which SearchLoopMapPoints() ran before that correction (afterwards the
+    // revisit run's camera frames are rescaled and SearchLoopMapPoints can no longer run); in every other case false and nothing changes, a
+    // second call for the same loop included.  Poses and point positions are never touched.
+    //  1. current keyframe: for each feature i with GetCurrentMatchedPoints()[i] = L, L good, in index order: L already observed by the
+    //     current keyframe -> a conflict; the feature's point q good and q != L -> ReplaceMapPoint(q, L); no good point -> the observation is added
+    //  2. targets: the current keyframe and the keyframes connected to it (the larger of the two weights, as CorrectLoop) that are among the
+    //     keyframes given, not bad, not the matched keyframe and not connected to it, by id; one SearchFuseCandidates(targets, Sim3(T_kw),
+    //     GetLoopMapPoints(), _fuse_search_th) with the corrected poses at scale 1
+    //  3. hits: keyframes by id, points by index, each re-checked against the map as it is now: L bad or already observed by k -> a conflict;
+    //     the feature's point q null or bad -> the observation is added; q = L -> nothing; q itself a loop map point -> a conflict (left to local
+    //     mapping); otherwise ReplaceMapPoint(q, L)
+    //  4. Matcher::ComputeDistinctiveDescriptors over every loop map point that gained an observation, one device call
+    //  5. UpdateCovisibility(touched, keyframes): the keyframes in which some feature's _mappoint changed and those that observe a point
+    //     that gained an observation, by id
+    bool FuseLoop(const vector<Frame *> &keyframes);
+    bool FuseLoop();                        // every keyframe registered in Memory
+    const vector<FusedPair> &GetFusedPairs() const { return _fused; }   // every action of the last FuseLoop, in order
+
     Frame *GetMatchedKeyframe() const { return _matched; }
     const Sim3 &GetSim3() const { return _S12; }                      // loop keyframe's camera -> current keyframe's camera
     const Sim3 &GetCorrectedPose() const { return _Scw; }             // S12 * T_2w
@@ -136,6 +184,9 @@ private:
     vector<pair<MapPoint *, MapPoint *>> _matches;
     vector<MapPoint *> _current_matched, _loop_points;
     bool _correctable = false;                                        // an accepted loop that no CorrectLoop has used yet
+    bool _searched = false;                                           // SearchLoopMapPoints ran for that loop, before its correction
+    bool _fusable = false;                                            // a corrected loop with such a search that no FuseLoop has used yet
+    vector<FusedPair> _fused;
     PoseGraph _pose_graph;
     Stats _stats;
 };

@@ -71,6 +71,12 @@ public:
     // (keyframe, point) hits.
     int SearchFuseCandidates(const vector<Frame *> &kfs, const vector<Sim3> &Scw, const vector<MapPoint *> &points, float th,
                              vector<vector<int>> &feature_of_point);
+    // ORB-SLAM2's MapPoint::ComputeDistinctiveDescriptors for many points in one device call (ygz_hip_distinctive_descriptors, DESIGN.md
+    // section 14; the reference ships MapPoint::ComputeDistinctiveDesc commented out).  Per good point the observations are the _obs entries
+    // in key order whose feature is non-null and holds a continuous 32-byte _desc; _distinctive_desc becomes a 1 x 32 CV_8UC1 copy of the
+    // one with the smallest median distance to the others (the first of equals).  Points with no such observation, or with more than 256,
+    // keep _distinctive_desc as it is.  Returns the number of points set.
+    int ComputeDistinctiveDescriptors(const vector<MapPoint *> &points);
     SE3 GetTCR() const { return _TCR_esti; }
 private:
     SparseImgAlign *_align;

@@ -50,7 +50,8 @@ extern "C" {
  * Still 6: the projection-guided descriptor search added (ygz_proj_problem, ygz_proj_params, ygz_hip_default_proj_params,
  * ygz_hip_search_by_projection, ygz_hip_projection_candidates) -- no existing argument list changed.
  * Still 6: the Sim3 pose-graph optimiser added (ygz_pgo_params, ygz_pgo_result, ygz_hip_default_pgo_params, ygz_hip_pose_graph_optimize,
- * ygz_hip_pgo_linearize) -- no existing argument list changed. */
+ * ygz_hip_pgo_linearize) -- no existing argument list changed.
+ * Still 6: the map upkeep of loop fusion added (ygz_hip_distinctive_descriptors, ygz_hip_covisibility) -- no existing argument list changed. */
 #define YGZ_HIP_ABI_VERSION 6
 
 typedef struct ygz_hip_ctx ygz_hip_ctx;
@@ -834,6 +835,32 @@ int  ygz_hip_pose_graph_optimize(ygz_hip_ctx *ctx, int n_vertices, const double 
  * be NULL.  The same checks.  Returns YGZ_E_STATE when the residual is undefined at S (the outputs are zero for such an edge). */
 int  ygz_hip_pgo_linearize(ygz_hip_ctx *ctx, int n_vertices, const double *S, const uint8_t *fixed, int n_edges, const int32_t *edges,
                            const double *M, const ygz_pgo_params *params, double *residuals, double *Ji, double *Jj, double *cost);
+
+/* ---- map upkeep after a loop correction -- nothing in the reference (MapPoint::ComputeDistinctiveDesc is shipped commented out, the
+ * covisibility weights exist only as Frame::UpdateConnections); ORB-SLAM2's MapPoint::ComputeDistinctiveDescriptors and the counting of
+ * KeyFrame::UpdateConnections, for many points at once.  The observations of point p are rows offsets[p] .. offsets[p+1]-1 of the per-
+ * observation array, in the caller's order.  Every output is an integer and bit-identical to tests/map_ref.c. */
+#define YGZ_MAP_MAX_OBS_PER_POINT 256     /* observations of one point (descriptors) */
+#define YGZ_MAP_MAX_OBS           1048576 /* observations per call */
+#define YGZ_MAP_MAX_KEYFRAMES     4096    /* K */
+#define YGZ_COVIS_MAX_CELLS       4194304 /* n_rows x K */
+/* per point with n observations desc [n_obs][32]: d(i, j) the 256-bit Hamming distance, d(i, i) = 0; the median of observation i is element
+ * (n - 1) / 2 of its distance row sorted ascending, the self distance included; best [n_points] is the smallest i with the smallest median,
+ * median [n_points] (or NULL) that value, out_desc [n_points][32] (or NULL) that observation's bytes; n = 0 gives -1, -1 and zeros.  One
+ * upload, one launch, one copy back and one wait.  Checked in this order, all before the device is touched: YGZ_E_INVALID for a null offsets,
+ * desc or best, n_points < 1, offsets[0] != 0 or a decreasing offset; YGZ_E_CAPACITY for a point with more than YGZ_MAP_MAX_OBS_PER_POINT
+ * observations or more than YGZ_MAP_MAX_OBS in the call; last, YGZ_E_INVALID for a null context. */
+int  ygz_hip_distinctive_descriptors(ygz_hip_ctx *ctx, int n_points, const int32_t *offsets, const uint8_t *desc, int32_t *best,
+                                     int32_t *median, uint8_t *out_desc);
+/* kf [n_obs] holds keyframe indices in [0, n_keyframes), strictly ascending within a point; rows [n_rows] distinct keyframe indices in any
+ * order.  weights [n_rows][n_keyframes]: weights[r][b] for b != rows[r] is the number of points whose list holds both rows[r] and b,
+ * weights[r][rows[r]] the number of points whose list holds rows[r].  One upload, the clear and the launch, one copy back and one wait.
+ * Checked in this order, all before the device is touched: YGZ_E_INVALID for a null array; YGZ_E_CAPACITY for n_keyframes above
+ * YGZ_MAP_MAX_KEYFRAMES; YGZ_E_INVALID for n_keyframes < 1 or n_rows < 1; YGZ_E_CAPACITY for n_rows x n_keyframes above YGZ_COVIS_MAX_CELLS;
+ * YGZ_E_INVALID for n_points < 1, offsets[0] != 0 or a decreasing offset; YGZ_E_CAPACITY for more than YGZ_MAP_MAX_OBS observations;
+ * YGZ_E_INVALID for an index out of range, a list that is not strictly ascending or a repeated row; last, for a null context. */
+int  ygz_hip_covisibility(ygz_hip_ctx *ctx, int n_points, const int32_t *offsets, const int32_t *kf, int n_keyframes, int n_rows,
+                          const int32_t *rows, int32_t *weights);
 
 #ifdef __cplusplus
 }

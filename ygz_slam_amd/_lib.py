@@ -298,6 +298,12 @@ def pgo_argtypes(lib):
     lib.ygz_hip_pgo_linearize.argtypes = [C.c_void_p, C.c_int, dp, C.POINTER(C.c_uint8), C.c_int, ip, dp, C.POINTER(PgoParams), dp, dp, dp, dp]
 
 
+def map_argtypes(lib):
+    ip, bp = C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
+    lib.ygz_hip_distinctive_descriptors.argtypes = [C.c_void_p, C.c_int, ip, bp, ip, ip, bp]
+    lib.ygz_hip_covisibility.argtypes = [C.c_void_p, C.c_int, ip, ip, C.c_int, C.c_int, ip, ip]
+
+
 # every symbol include/ygz_hip.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
     "ygz_hip_default_params", "ygz_hip_create", "ygz_hip_destroy", "ygz_hip_synchronize", "ygz_hip_join", "ygz_hip_set_overlap", "ygz_hip_error_string",
@@ -325,6 +331,7 @@ ABI_SYMBOLS = [
     "ygz_hip_default_sim3_params", "ygz_hip_sim3_ransac", "ygz_hip_sim3_hypotheses",
     "ygz_hip_default_proj_params", "ygz_hip_search_by_projection", "ygz_hip_projection_candidates",
     "ygz_hip_default_pgo_params", "ygz_hip_pose_graph_optimize", "ygz_hip_pgo_linearize",
+    "ygz_hip_distinctive_descriptors", "ygz_hip_covisibility",
 ]
 INIT_SYMBOLS = ["ygz_hip_default_init_params", "ygz_hip_initialize", "ygz_hip_init_sample_sets", "ygz_hip_init_hypotheses", "ygz_hip_init_reconstruct"]
 INIT_NONE, INIT_H, INIT_F = 0, 1, 2
@@ -337,6 +344,8 @@ PROJ_MAX_PROBLEMS, PROJ_TOPK, PROJ_MAX_POINTS = 64, 8, 65536
 PGO_SYMBOLS = ["ygz_hip_default_pgo_params", "ygz_hip_pose_graph_optimize", "ygz_hip_pgo_linearize"]
 PGO_MAX_VERTICES, PGO_MAX_EDGES = 4096, 32768
 PGO_FAILED, PGO_CONVERGED, PGO_MAX_ITERATIONS, PGO_STALLED = 0, 1, 2, 3
+MAP_SYMBOLS = ["ygz_hip_distinctive_descriptors", "ygz_hip_covisibility"]
+MAP_MAX_OBS_PER_POINT, MAP_MAX_OBS, MAP_MAX_KEYFRAMES, COVIS_MAX_CELLS = 256, 1048576, 4096, 4194304
 
 SUMMARY_FIELDS = 32
 
@@ -1270,6 +1279,39 @@ class HipContext:
         if rc != E_STATE:
             self._chk(rc, "pgo_linearize")
         return dict(ok=rc == OK, res=res, Ji=Ji, Jj=Jj, cost=float(cost[0]))
+
+    # ---- map upkeep after a loop correction
+
+    def distinctive_descriptors(self, offsets, desc):
+        """ORB-SLAM2's ComputeDistinctiveDescriptors for a batch of points (ygz_hip_distinctive_descriptors): offsets [P + 1], desc
+        [n_obs][32]; dict(best [P], median [P], desc [P][32])"""
+        off = np.ascontiguousarray(offsets, np.int32).reshape(-1)
+        d = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        P = len(off) - 1
+        if P < 1 or int(off[-1]) != len(d):
+            raise ValueError("offsets do not describe desc")
+        d = d if len(d) else np.zeros((1, 32), np.uint8)
+        best, med, out = np.full(P, -2, np.int32), np.full(P, -2, np.int32), np.full((P, 32), 0xAA, np.uint8)
+        map_argtypes(self.lib)
+        self._chk(self.lib.ygz_hip_distinctive_descriptors(self._ctx, P, _p(off, C.c_int32), _p(d, C.c_uint8), _p(best, C.c_int32),
+                                                           _p(med, C.c_int32), _p(out, C.c_uint8)), "distinctive_descriptors")
+        return dict(best=best, median=med, desc=out)
+
+    def covisibility(self, offsets, kf, n_keyframes, rows):
+        """shared-point counts (ygz_hip_covisibility): offsets [P + 1], kf [n_obs] ascending within a point, rows [R] distinct keyframe
+        indices; weights [R][n_keyframes]"""
+        off = np.ascontiguousarray(offsets, np.int32).reshape(-1)
+        k = np.ascontiguousarray(kf, np.int32).reshape(-1)
+        r = np.ascontiguousarray(rows, np.int32).reshape(-1)
+        P = len(off) - 1
+        if P < 1 or int(off[-1]) != len(k):
+            raise ValueError("offsets do not describe kf")
+        k = k if len(k) else np.zeros(1, np.int32)
+        w = np.full((max(len(r), 1), max(int(n_keyframes), 1)), -2, np.int32)
+        map_argtypes(self.lib)
+        self._chk(self.lib.ygz_hip_covisibility(self._ctx, P, _p(off, C.c_int32), _p(k, C.c_int32), int(n_keyframes), len(r), _p(r, C.c_int32),
+                                                _p(w, C.c_int32)), "covisibility")
+        return w
 
     # ---- BoW
     def vocab_load(self, blob):

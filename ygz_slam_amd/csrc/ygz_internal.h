@@ -10,7 +10,7 @@
 // the tracker's working images: every level inside a reflect-101 frame of KLT_B pixels (klt.hip; written by the pyramid kernels, image.hip)
 #define KLT_B      24          // >= window + 1, multiple of 4
 #define KLT_PW(w)  (((w) + 2 * KLT_B + 3) & ~3)      // framed row pitch, 4-byte aligned for any level width
-#define YGZ_N_SCRATCH  32
+#define YGZ_N_SCRATCH  40
 
 struct ygz_hip_ctx {
     ygz_hip_params prm;

@@ -1,7 +1,8 @@
 // ygz::LoopClosing::CorrectLoop (include/ygz/Algorithm/LoopClosing.h): nothing in the reference, whose loop closing is empty.  The correcting
 // half of ORB-SLAM2's LoopClosing::CorrectLoop with Optimizer::OptimizeEssentialGraph's graph: the accepted Sim3 propagated to the current
 // keyframe's neighbourhood, one ygz_hip_pose_graph_optimize call (ygz_slam_amd/csrc/pgo.hip), poses and map points rewritten from its result.
-// Every choice ORB-SLAM2 leaves to set iteration over pointers goes by keyframe id here.  No fusion, no covisibility update, no global BA.
+// Every choice ORB-SLAM2 leaves to set iteration over pointers goes by keyframe id here.  Fusion and the covisibility update are FuseLoop
+// (ygz_fuse.cpp); no global BA.
 // Error conventions of the other surfaces: a failed call logs and returns false, only a missing device throws.
 #include "ygz/Algorithm/LoopClosing.h"
 #include "ygz/hip/Runtime.h"
@@ -172,6 +173,8 @@ bool LoopClosing::CorrectLoop(const vector<Frame *> &keyframes)
             ++_stats.correct_points_moved;
         }
     _correctable = false;
+    _fusable = _searched;                                             // FuseLoop needs the loop map points of before this correction
+    _searched = false;
     return true;
 }
 

@@ -70,6 +70,7 @@ bool LoopClosing::DetectLoop(Frame *kf, const vector<Frame *> &keyframes)
     _enough_consistent.clear();
     _acc_score.clear();
     _current = nullptr;
+    _searched = _fusable = false;
     if (!kf || Frame::_vocab == nullptr) {
         LOG(ERROR) << "LoopClosing::DetectLoop: no keyframe or no vocabulary" << endl;
         return false;
@@ -171,6 +172,7 @@ bool LoopClosing::ComputeSim3()
 {
     _matched = nullptr;
     _correctable = false;
+    _searched = _fusable = false;
     _S12 = Sim3(); _Scw = Sim3();
     _matches.clear();
     _stats.bow_pairs.clear(); _stats.ransac_inliers.clear(); _stats.refined_inliers.clear();
@@ -260,6 +262,7 @@ bool LoopClosing::SearchLoopMapPoints()
 {
     _current_matched.clear();
     _loop_points.clear();
+    _searched = _fusable = false;                                    // FuseLoop works on this call's vectors
     _stats.sim3_added = _stats.projection_added = _stats.total_matches = 0;
     Frame *kf = _current;
     if (!kf || !_matched || _matches.empty()) return false;
@@ -289,6 +292,7 @@ bool LoopClosing::SearchLoopMapPoints()
     _stats.projection_added = _matcher.SearchByProjection(kf, _Scw, _loop_points, _current_matched, _option._projection_search_th);
     // 5. enough matches in total
     for (const MapPoint *mp : _current_matched) if (mp) ++_stats.total_matches;
+    _searched = _correctable;                                         // after the correction the revisit run's camera frames are rescaled
     return _stats.total_matches >= _option._min_total_matches;
 }
 
