@@ -181,13 +181,30 @@ int ygz_kcopy(ygz_hip_ctx *ctx, void *dst, const void *src, size_t bytes, int ki
 
 int ygz_join(ygz_hip_ctx *ctx, unsigned skip_mask)
 {
+    if (ctx->head_aside) skip_mask &= ~(1u << YGZ_AUX_SPARSE);      // whoever ends the trailing LK's privilege also waits for the head beside it
     for (int i = 0; i < 3; ++i)
         if (ctx->aux_pending[i] && !((skip_mask >> i) & 1u)) {
             YGZ_HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join[i], 0)); ctx->aux_pending[i] = false;
             if (i == YGZ_AUX_MATCH) ctx->match_aux_reads_track = false;
+            if (i == YGZ_AUX_SPARSE) ctx->head_aside = false;
         }
+    ctx->klt_tail = false;                          // what the caller enqueues on the main stream next comes behind the LK launch
     return YGZ_OK;
 }
+
+// build_pyramid / track_klt_prepare / detect: a pending BA linearisation reads no image and writes no keypoint, so it is never waited for.  On
+// the main stream they wait for the other side streams (and thereby end a trailing LK's privilege: they come behind it anyway); aside, the
+// head's stream waits for the matcher's stream (direct projection reads the images, the matcher the descriptors) and the main stream is left alone.
+int ygz_head_join(ygz_hip_ctx *ctx)
+{
+    if (!ctx->head_aside) return ygz_join(ctx, 1u << YGZ_AUX_BA);
+    if (ctx->aux_pending[YGZ_AUX_MATCH]) YGZ_HIPCHK(ctx, hipStreamWaitEvent(ctx->aux[YGZ_AUX_SPARSE], ctx->ev_join[YGZ_AUX_MATCH], 0));
+    return YGZ_OK;
+}
+
+// YGZ_KLT_ASIDE=0: the next step's head never runs beside a trailing LK launch (one set of LK working images, the schedule before this existed)
+static bool env_on(const char *name, bool dflt) { const char *e = getenv(name); return e ? e[0] != '0' : dflt; }
+static bool klt_aside_enabled() { static const bool on = env_on("YGZ_KLT_ASIDE", true); return on; }
 
 int ygz_ensure_levels(ygz_hip_ctx *ctx, int n_levels)
 {
@@ -285,10 +302,13 @@ void ygz_hip_destroy(ygz_hip_ctx *ctx)
     if (ctx->ev_xctx) (void)hipEventDestroy(ctx->ev_xctx);
     if (ctx->ev_mark) (void)hipEventDestroy(ctx->ev_mark);
     if (ctx->ev_prep) (void)hipEventDestroy(ctx->ev_prep);
+    if (ctx->ev_pre_klt) (void)hipEventDestroy(ctx->ev_pre_klt);
     for (int L = 0; L < YGZ_MAX_LEVELS; ++L) {
         if (ctx->lvl[L]) (void)hipFree(ctx->lvl[L]);
         if (ctx->deriv[L]) (void)hipFree(ctx->deriv[L]);
         if (ctx->klt_pad[L]) (void)hipFree(ctx->klt_pad[L]);
+        if (ctx->deriv_alt[L]) (void)hipFree(ctx->deriv_alt[L]);
+        if (ctx->klt_pad_alt[L]) (void)hipFree(ctx->klt_pad_alt[L]);
         if (L == 0 && ctx->klt_slots) (void)hipFree(ctx->klt_slots);
         if (ctx->dbg_score[L]) (void)hipFree(ctx->dbg_score[L]);
         if (ctx->dbg_nms[L]) (void)hipFree(ctx->dbg_nms[L]);
@@ -323,6 +343,8 @@ int ygz_hip_set_overlap(ygz_hip_ctx *ctx, int enable)
         }
     }
     ctx->overlap = enable ? 1 : 0;
+    if (enable && klt_aside_enabled() && !ctx->ev_pre_klt) YGZ_HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_pre_klt, hipEventDisableTiming));
+    ctx->klt_aside = enable && klt_aside_enabled();
     return YGZ_OK;
 }
 
@@ -387,6 +409,7 @@ int ygz_hip_abi_version(void) { return YGZ_HIP_ABI_VERSION; }
 int ygz_hip_get_stream(ygz_hip_ctx *ctx, void **stream)
 {
     if (!ctx || !stream) return YGZ_E_INVALID;
+    YgzDeviceGuard dg_(ctx);                                  // what the caller enqueues on the stream comes behind a head that ran aside
     *stream = (void *)ctx->stream;
     return YGZ_OK;
 }
@@ -544,13 +567,57 @@ int ygz_hip_upload_gray(ygz_hip_ctx *ctx, int slot, const uint8_t *gray, int str
     return YGZ_OK;
 }
 
+// The flip of the LK working images (see ygz_internal.h): brings the other set up to the levels the current one has, orders the head's stream
+// behind everything the main stream held before the trailing LK launch, and makes the other set the current one.  When the device has no room
+// for the second set nothing is flipped and the caller goes on as without a trailing LK (one set, behind LK on the main stream): the levels that
+// were allocated stay (each with its zero frame) and the next attempt asks for the missing ones only.
+static int klt_flip_sets(ygz_hip_ctx *ctx)
+{
+    hipStream_t hs = ctx->aux[YGZ_AUX_SPARSE];
+    for (int L = 0; L < YGZ_MAX_LEVELS; ++L) {
+        const size_t psz = (size_t)KLT_PW(ctx->lw[L]) * (ctx->lh[L] + 2 * KLT_B);
+        if (ctx->klt_pad[L] && !ctx->klt_pad_alt[L] && hipMalloc((void **)&ctx->klt_pad_alt[L], (size_t)ctx->prm.max_frames * psz + 64) != hipSuccess) {
+            ctx->klt_pad_alt[L] = nullptr; (void)hipGetLastError(); return YGZ_OK;
+        }
+        if (ctx->deriv[L] && !ctx->deriv_alt[L]) {
+            if (hipMalloc((void **)&ctx->deriv_alt[L], (size_t)ctx->prm.max_frames * psz * 4 + 64) != hipSuccess) {
+                ctx->deriv_alt[L] = nullptr; (void)hipGetLastError(); return YGZ_OK;
+            }
+            YGZ_HIPCHK(ctx, hipMemsetAsync(ctx->deriv_alt[L], 0, (size_t)ctx->prm.max_frames * psz * 4 + 64, hs));   // the zero frame
+        }
+    }
+    YGZ_HIPCHK(ctx, hipStreamWaitEvent(hs, ctx->ev_pre_klt, 0));
+    for (int L = 0; L < YGZ_MAX_LEVELS; ++L) {
+        uint8_t *p = ctx->klt_pad[L]; ctx->klt_pad[L] = ctx->klt_pad_alt[L]; ctx->klt_pad_alt[L] = p;
+        int16_t *d = ctx->deriv[L]; ctx->deriv[L] = ctx->deriv_alt[L]; ctx->deriv_alt[L] = d;
+    }
+    ctx->klt_set ^= 1;
+    for (uint8_t &pl : ctx->pad_levels) pl = 0;               // this set holds no slot's current images yet
+    ctx->klt_prep_valid = false;
+    ctx->head_aside = true;
+    (void)hipEventRecord(ctx->ev_join[YGZ_AUX_SPARSE], hs); ctx->aux_pending[YGZ_AUX_SPARSE] = true;
+    return YGZ_OK;
+}
+
 int ygz_hip_build_pyramid(ygz_hip_ctx *ctx, int slot_begin, int n_slots, int from_bgr)
 {
-    YgzDeviceGuard dg_(ctx);
+    YgzDeviceGuard dg_(ctx, YGZ_HEAD_CALL);
     if (!ctx || slot_begin < 0 || n_slots < 1 || slot_begin + n_slots > ctx->prm.max_frames) return YGZ_E_INVALID;
     if (from_bgr && !ctx->bgr) return YGZ_E_STATE;
-    { int rj = ygz_join(ctx, 1u << YGZ_AUX_BA); if (rj != YGZ_OK) return rj; }      // a pending BA linearisation reads no image
-    if (ctx->klt_prep_pending) { YGZ_HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_prep, 0)); ctx->klt_prep_pending = false; }   // ... but LK working images being built do
+    // LK is still at the tail of the main stream and this call rebuilds every slot its pair table names: the images go to the other set, and
+    // this call and the rest of the head run beside that launch (it got its pointers by value).  A partial rebuild, or no trailing LK: as before,
+    // on the main stream (behind LK) into the current set.
+    if (ctx->klt_aside && ctx->klt_tail && !ctx->head_aside && ctx->klt_pad[0] && ctx->n_klt_slots > 0 && (int)ctx->klt_slots_host.size() == ctx->n_klt_slots) {
+        bool all = true;
+        for (int s : ctx->klt_slots_host) if (s < slot_begin || s >= slot_begin + n_slots) all = false;
+        if (all) { const int rf = klt_flip_sets(ctx); if (rf != YGZ_OK) return rf; }
+    }
+    YgzHeadScope head(ctx);
+    { int rj = ygz_head_join(ctx); if (rj != YGZ_OK) return rj; }
+    if (ctx->klt_prep_pending) {                               // LK working images being built read the levels
+        YGZ_HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_prep, 0));
+        if (!ctx->head_aside) ctx->klt_prep_pending = false;   // (aside: the main stream has not waited)
+    }
     int rc = ygz_launch_gray_pyramid(ctx, slot_begin, n_slots, from_bgr, ctx->n_levels_alloc);
     if (rc != YGZ_OK) return rc;
     for (int s = slot_begin; s < slot_begin + n_slots; ++s) ctx->pyr_valid[s] = 1;

@@ -694,9 +694,10 @@ extern "C" {
 
 int ygz_hip_detect(ygz_hip_ctx *ctx, int slot_begin, int n_slots, const uint8_t *occupied)
 {
-    YgzDeviceGuard dg_(ctx);
-    if (ctx) { int rj_ = ygz_join(ctx, 1u << YGZ_AUX_BA); if (rj_ != YGZ_OK) return rj_; }
+    YgzDeviceGuard dg_(ctx, YGZ_HEAD_CALL);
     if (!ctx || slot_begin < 0 || n_slots < 1 || slot_begin + n_slots > ctx->prm.max_frames) return YGZ_E_INVALID;
+    YgzHeadScope head(ctx);                                   // beside a trailing LK launch when the pyramid was built there (ygz_hip_build_pyramid)
+    { int rj_ = ygz_head_join(ctx); if (rj_ != YGZ_OK) return rj_; }
     for (int s = slot_begin; s < slot_begin + n_slots; ++s) if (!ctx->pyr_valid[s]) return YGZ_E_STATE;
     const size_t Cn = (size_t)ctx->cells;
     if (occupied) {                                           // through the page-locked arena: the caller's array may be pageable and short-lived
@@ -713,6 +714,7 @@ int ygz_hip_keypoint_count(ygz_hip_ctx *ctx, int slot, int *n)
 {
     YgzDeviceGuard dg_(ctx);
     if (!ctx || !n || slot < 0 || slot >= ctx->prm.max_frames) return YGZ_E_INVALID;
+    { int rj_ = ygz_join(ctx); if (rj_ != YGZ_OK) return rj_; }      // the extractor may have run on a side stream
     YGZ_HIPCHK(ctx, hipMemcpyAsync(n, ctx->n_kp + slot, 4, hipMemcpyDeviceToHost, ctx->stream));
     YGZ_HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return YGZ_OK;
@@ -787,6 +789,7 @@ int ygz_hip_get_fast_maps(ygz_hip_ctx *ctx, int slot, int level, uint8_t *score,
     YgzDeviceGuard dg_(ctx);
     if (!ctx || slot < 0 || slot >= ctx->prm.max_frames || level < 0 || level >= ctx->prm.pyramid_levels) return YGZ_E_INVALID;
     if (!ctx->prm.debug_maps) return YGZ_E_STATE;
+    { int rj_ = ygz_join(ctx); if (rj_ != YGZ_OK) return rj_; }
     const size_t npix = (size_t)ctx->lw[level] * ctx->lh[level];
     if (score) YGZ_HIPCHK(ctx, hipMemcpyAsync(score, ctx->dbg_score[level] + slot * npix, npix, hipMemcpyDeviceToHost, ctx->stream));
     if (nms) YGZ_HIPCHK(ctx, hipMemcpyAsync(nms, ctx->dbg_nms[level] + slot * npix, npix, hipMemcpyDeviceToHost, ctx->stream));

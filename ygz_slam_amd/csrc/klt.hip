@@ -616,7 +616,17 @@ __global__ __launch_bounds__(256) void k_klt3(KltArgs A)
 }
 
 static int launch_klt_impl(ygz_hip_ctx *ctx, int n_pairs, const ygz_klt_params *prm, bool prep_only);
-int ygz_launch_klt(ygz_hip_ctx *ctx, int n_pairs, const ygz_klt_params *prm) { return launch_klt_impl(ctx, n_pairs, prm, false); }
+// LK stays on the main stream.  With ctx->klt_aside it is marked as the stream's tail: until another entry point than the three of the head is called, a
+// ygz_hip_build_pyramid of the whole pair table may start the next head beside it (ctx.hip), ordered behind ev_pre_klt.
+int ygz_launch_klt(ygz_hip_ctx *ctx, int n_pairs, const ygz_klt_params *prm)
+{
+    // a head that ran aside wrote the images this launch reads; LK neither reads nor writes what the matcher's stream or a BA build works on
+    if (ctx->head_aside) { const int rj = ygz_join(ctx, (1u << YGZ_AUX_BA) | (1u << YGZ_AUX_MATCH)); if (rj != YGZ_OK) return rj; }
+    ctx->klt_tail = false;
+    const int rc = launch_klt_impl(ctx, n_pairs, prm, false);
+    if (rc == YGZ_OK && ctx->klt_aside) ctx->klt_tail = true;
+    return rc;
+}
 // the tracker's working images (reflect-framed copies + Scharr images of the distinct slots of the pair table) ahead of the LK launch:
 // they depend only on the pyramids, so a pipeline can build them before it forks its side-stream stages
 int ygz_klt_prepare_early(ygz_hip_ctx *ctx)
@@ -674,6 +684,7 @@ static int launch_klt_impl(ygz_hip_ctx *ctx, int n_pairs, const ygz_klt_params *
     ctx->klt_prep_valid = false;
     if (prep_only) return YGZ_OK;
     if (ctx->klt_prep_pending) { YGZ_HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_prep, 0)); ctx->klt_prep_pending = false; }
+    if (ctx->klt_aside) YGZ_HIPCHK(ctx, hipEventRecord(ctx->ev_pre_klt, ctx->stream));     // working images done, LK not yet enqueued
     A.max_level = max_level; A.win = prm->win; A.cells = ctx->cells; A.n_pairs = n_pairs;
     A.max_count = prm->max_iter < 0 ? 0 : (prm->max_iter > 100 ? 100 : prm->max_iter);
     const double eps = prm->eps < 0 ? 0 : (prm->eps > 10 ? 10 : prm->eps);

@@ -255,10 +255,11 @@ int ygz_hip_track_klt(ygz_hip_ctx *ctx, const ygz_klt_params *prm)
 // ygz_hip_track_klt then starts with the LK kernel itself.  Without it ygz_hip_track_klt builds them first; same results.
 int ygz_hip_track_klt_prepare(ygz_hip_ctx *ctx)
 {
-    YgzDeviceGuard dg_(ctx);
+    YgzDeviceGuard dg_(ctx, YGZ_HEAD_CALL);
     if (!ctx) return YGZ_E_INVALID;
     if (ctx->n_pairs < 1 || !ctx->trk_alloc) return YGZ_E_STATE;
     if (!ctx->ev_prep) YGZ_HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_prep, hipEventDisableTiming));
+    YgzHeadScope head(ctx);                                  // behind the pyramid kernels, wherever they ran
     YgzAuxScope aux(ctx, YGZ_AUX_BA);                        // idle at this point of a step: the BA build is issued after the extractor
     const int rc = ygz_klt_prepare_early(ctx);
     if (rc != YGZ_OK) return rc;

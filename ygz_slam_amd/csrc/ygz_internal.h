@@ -33,6 +33,19 @@ struct ygz_hip_ctx {
     // Scharr derivative levels for KLT (int16 x2 per pixel), allocated on first KLT call
     int16_t *deriv[YGZ_MAX_LEVELS] = {nullptr};
     uint8_t *klt_pad[YGZ_MAX_LEVELS] = {nullptr};       // reflect-101 framed copies of the levels (KLT working images)
+    // The second set of LK working images (allocated at the first flip, i.e. only with overlap enabled).  deriv / klt_pad always point at the set
+    // that holds the CURRENT images, and every piece of bookkeeping (pad_levels, klt_prep_valid, klt_prep_levels) describes that set alone.  The
+    // other set is either what an LK launch at the tail of the main stream is still reading (klt_tail && head_aside) or garbage.  The only flip is
+    // in ygz_hip_build_pyramid, which then rewrites every slot of the pair table and marks every other slot's framed copies as missing -- so no
+    // per-set copy of the bookkeeping is needed.  klt_set names the current set (it is not a step counter: it changes only at a flip).
+    int16_t *deriv_alt[YGZ_MAX_LEVELS] = {nullptr};
+    uint8_t *klt_pad_alt[YGZ_MAX_LEVELS] = {nullptr};
+    int  klt_set = 0;
+    bool klt_aside = false;                  // overlap enabled and YGZ_KLT_ASIDE != 0: the next step's extraction may run beside a trailing LK launch
+    bool klt_tail = false;                   // the LK kernel is the last thing enqueued on the main stream (cleared by every ygz_join and by every entry point that is not one of the three head calls: YgzDeviceGuard)
+    bool head_aside = false;                 // build_pyramid / track_klt_prepare / detect run on the sparse-alignment side stream, beside that LK launch
+                                             // (which reads the OTHER set); implies aux_pending[YGZ_AUX_SPARSE]; ended by the join of that stream
+    hipEvent_t ev_pre_klt = nullptr;         // the main stream right before the trailing LK launch: what the head aside is ordered behind
     int32_t *klt_slots = nullptr; int n_klt_slots = 0, n_klt_refs = 0;   // distinct slots of the pair table: [0, n_klt_slots) all, then the reference slots
     std::vector<int32_t> klt_slots_host;    // the first n_klt_slots entries of klt_slots
     std::vector<uint8_t> pad_levels;        // per slot: the framed copies of levels [0, pad_levels) match the slot's pyramid (written by the pyramid kernels or by k_klt_pad)
@@ -159,12 +172,32 @@ static inline int ygz_div_up(int a, int b) { return (a + b - 1) / b; }
 
 // Every entry point that may allocate or launch makes the context's device current for its duration and restores the
 // caller's device afterwards (a process may hold contexts on several GPUs, and torch may have switched device since create).
+// It is also the ONE place that ends the privileges of a trailing LK launch: only ygz_hip_build_pyramid, ygz_hip_track_klt_prepare and
+// ygz_hip_detect (YGZ_HEAD_CALL) know that a head may run on a side stream; every other entry point first has the main stream wait for such a head
+// and takes the tail mark away, so whatever it enqueues on the main stream is ordered behind the pyramids and keypoints, and a later
+// ygz_hip_build_pyramid is ordered behind it -- as when everything ran on the main stream.
+// side streams (indices of ctx->aux, bits of a skip mask)
+#define YGZ_AUX_SPARSE 0
+#define YGZ_AUX_BA     1
+#define YGZ_AUX_MATCH  2
+int ygz_join(ygz_hip_ctx *ctx, unsigned skip_mask);
+enum YgzHeadCall { YGZ_HEAD_CALL };
 struct YgzDeviceGuard {
     int prev = -1; bool switched = false;
-    explicit YgzDeviceGuard(const ygz_hip_ctx *c)
+    void enter(const ygz_hip_ctx *c)
     {
         if (!c) return;
         if (hipGetDevice(&prev) == hipSuccess && prev != c->device) switched = (hipSetDevice(c->device) == hipSuccess);
+    }
+    explicit YgzDeviceGuard(const ygz_hip_ctx *c) { enter(c); }                  // entry points that enqueue nothing
+    YgzDeviceGuard(ygz_hip_ctx *c, YgzHeadCall) { enter(c); }
+    explicit YgzDeviceGuard(ygz_hip_ctx *c)
+    {
+        enter(c);
+        if (!c) return;
+        // the head's stream alone: what else is pending stays pending for the entry point's own join
+        if (c->head_aside) (void)ygz_join(c, (1u << YGZ_AUX_BA) | (1u << YGZ_AUX_MATCH));
+        c->klt_tail = false;
     }
     ~YgzDeviceGuard() { if (switched) (void)hipSetDevice(prev); }
     YgzDeviceGuard(const YgzDeviceGuard &) = delete;
@@ -223,9 +256,6 @@ void ygz_kf_store_free(ygz_hip_ctx *ctx);   // window.hip
 int ygz_join(ygz_hip_ctx *ctx, unsigned skip_mask = 0);   // main stream waits for every pending side-stream stage (bit i of
                                                           // skip_mask: leave side stream i pending -- for entry points that do not
                                                           // touch what that stage reads or writes)
-#define YGZ_AUX_SPARSE 0
-#define YGZ_AUX_BA     1
-#define YGZ_AUX_MATCH  2
 
 // RAII: run the enclosed launches on side stream `idx` (sparse-align 0, BA 1, matcher 2) when overlap is enabled.
 // The side stream first waits for everything already enqueued on the main stream (fork), and the main stream waits
@@ -246,6 +276,22 @@ struct YgzAuxScope {
         c->stream = saved; c->aux_pending[idx] = true;
     }
 };
+// RAII for the three calls of a step's head: while ctx->head_aside their launches go to the sparse-alignment side stream (in order behind one
+// another there); the main stream waits for them at the next ygz_join of that stream (ygz_hip_track_reload in a step).
+struct YgzHeadScope {
+    ygz_hip_ctx *c; hipStream_t saved; bool active;
+    explicit YgzHeadScope(ygz_hip_ctx *ctx) : c(ctx), saved(ctx->stream), active(ctx->head_aside)
+    {
+        if (active) ctx->stream = ctx->aux[YGZ_AUX_SPARSE];
+    }
+    ~YgzHeadScope()
+    {
+        if (!active) return;
+        (void)hipEventRecord(c->ev_join[YGZ_AUX_SPARSE], c->aux[YGZ_AUX_SPARSE]);
+        c->stream = saved; c->aux_pending[YGZ_AUX_SPARSE] = true;
+    }
+};
+int ygz_head_join(ygz_hip_ctx *ctx);                        // what a call of the head waits for, on the stream it runs on (ctx.hip)
 int ygz_ensure_levels(ygz_hip_ctx *ctx, int n_levels);      // allocates image levels up to n_levels
 
 // launchers implemented in the kernel translation units
