@@ -8,12 +8,15 @@
 // (ygz_slam_amd/host/ygz_loop.cpp).  CorrectLoop is the correcting half of ORB-SLAM2's LoopClosing::CorrectLoop: the Sim3 of the accepted loop
 // is propagated to the current keyframe's neighbourhood, a Sim3 pose graph over the keyframes (Optimizer::OptimizeEssentialGraph's edges) is
 // optimised in one device call (ygz_hip_pose_graph_optimize), and the keyframe poses and map points are rewritten from the result
-// (ygz_slam_amd/host/ygz_correct.cpp).  FuseLoop is the rest of ORB-SLAM2's CorrectLoop up to, but not including, the global BA: the
+// (ygz_slam_amd/host/ygz_correct.cpp).  FuseLoop is the rest of ORB-SLAM2's CorrectLoop up to its global BA: the
 // duplicated map points of the revisited region are fused into the old ones (the current keyframe's matches, then Matcher::
 // SearchFuseCandidates over the corrected neighbourhood), the surviving points' distinctive descriptors are recomputed
 // (Matcher::ComputeDistinctiveDescriptors, ygz_hip_distinctive_descriptors) and the covisibility of every keyframe it touched is recounted
-// (UpdateCovisibility, ygz_hip_covisibility) -- ygz_slam_amd/host/ygz_fuse.cpp.  The new connections are not fed back into the pose graph
-// and no global BA follows.  The integration is in INTEGRATION.md.
+// (UpdateCovisibility, ygz_hip_covisibility) -- ygz_slam_amd/host/ygz_fuse.cpp.  The new connections are not fed back into the pose
+// graph.  GlobalBundleAdjustment is what ORB-SLAM2's CorrectLoop ends with, RunGlobalBundleAdjustment, as a synchronous
+// call: every keyframe pose and every map point with two observations or more against all of their observations in one device call
+// (ygz_hip_global_ba: Levenberg-Marquardt, the points marginalised, conjugate gradients on the camera system) --
+// ygz_slam_amd/host/ygz_gba.cpp.  It needs no loop state and may be called at any time.  The integration is in INTEGRATION.md.
 #ifndef YGZ_LOOP_CLOSING_H_
 #define YGZ_LOOP_CLOSING_H_
 
@@ -52,6 +55,8 @@ public:
         float _projection_search_th = 10.0f;    // SearchByProjection's
         int _min_essential_weight = 100;        // CorrectLoop: connected pairs with at least this weight get an edge (ORB-SLAM2's minFeat)
         float _fuse_search_th = 4.0f;           // FuseLoop: SearchFuseCandidates' window, level-0 pixels (ORB-SLAM2's SearchAndFuse)
+        int _gba_iterations = 10;               // GlobalBundleAdjustment: LM iterations (ORB-SLAM2's RunGlobalBundleAdjustment)
+        double _gba_huber_delta = 5.991;        // its Huber width in pixels (sqrt of ORB-SLAM2's thHuber2D squared: g2o's setDelta); <= 0: no kernel
     } _option;
 
     struct Stats
@@ -89,6 +94,16 @@ public:
         int fuse_conflicts = 0;                 // matches and hits skipped: the loop point is already observed there, or is bad, or the feature holds another loop point
         int fuse_descriptors = 0;               // points whose _distinctive_desc was set
         int fuse_rows = 0;                      // keyframes whose covisibility was rewritten
+        // the last GlobalBundleAdjustment
+        int gba_poses = 0;                      // keyframes in the problem (the one with the smallest id is fixed)
+        int gba_points = 0;                     // map points in it
+        int gba_edges = 0;                      // observations
+        int gba_points_left_out = 0;            // good map points with fewer than 2 observations among the poses: untouched
+        struct GlobalBAResult                   // ygz_gba_result's fields
+        {
+            int status = 0, lm_iterations = 0, n_solves = 0, cg_iterations_total = 0, cg_capped = 0;
+            double cost_initial = 0, cost_final = 0, lambda = 0;
+        } global_ba;
     };
 
     // one action of FuseLoop: feature `feature` of keyframe `keyframe_id` now observes loop map point `loop_point_id`; `replaced_point_id`
@@ -103,6 +118,20 @@ public:
         vector<uint8_t> fixed;                  // [N]
         vector<int32_t> edges;                  // [E][2] vertex indices (i, j)
         vector<double> M;                       // [E][8] ~ S_j o S_i^-1
+    };
+
+    // the problem of the last GlobalBundleAdjustment that reached the solver, as it was handed over and as it came back
+    struct BundleProblem
+    {
+        vector<unsigned long> keyframe_ids;     // per pose, ascending
+        vector<unsigned long> point_ids;        // per point, in the order of rule 2
+        vector<double> poses, poses_out;        // [N][7] qx qy qz qw tx ty tz, world -> camera
+        vector<uint8_t> fixed;                  // [N]
+        vector<double> points, points_out;      // [L][3]
+        vector<int32_t> edge_pose, edge_point;  // [E]
+        vector<double> obs;                     // [E][2]
+        double K4[4] = { 0, 0, 0, 0 };          // fx fy cx cy
+        double huber_delta = 0;
     };
 
     // kf: a keyframe of the map with its covisibility (_connected_keyframe_weights); true when some loop candidate is consistent enough
@@ -163,6 +192,19 @@ public:
     bool FuseLoop();                        // every keyframe registered in Memory
     const vector<FusedPair> &GetFusedPairs() const { return _fused; }   // every action of the last FuseLoop, in order
 
+    // callable at any time, no loop state needed.  Ties go by _keyframe_id, never by address.
+    //  1. poses: the keyframes given that are not bad, once each, by id; the one with the smallest id is fixed (ORB-SLAM2's keyframe 0)
+    //  2. points: the good map points of their features, keyframes by id, features by index, each point once; a point's edges are its _obs
+    //     entries in key order whose feature is non-null and whose frame is a pose; the pixel is Feature::_pixel, the camera Frame::GetCamera()
+    //  3. a point with fewer than 2 such edges is left out and untouched (Stats::gba_points_left_out)
+    //  4. a free pose left without any edge: false, nothing changed
+    //  5. one ygz_hip_global_ba call with _gba_iterations and _gba_huber_delta; on an error or status failed: false, the map untouched
+    //  6. _TCW of every free pose and _pos_world of every included point are rewritten from the result; the fixed keyframe keeps its bits
+    //  7. nothing else changes: no observation, no _bad flag, no covisibility, no outlier removal
+    bool GlobalBundleAdjustment(const vector<Frame *> &keyframes);
+    bool GlobalBundleAdjustment();          // every keyframe registered in Memory
+    const BundleProblem &GetBundleProblem() const { return _bundle; }
+
     Frame *GetMatchedKeyframe() const { return _matched; }
     const Sim3 &GetSim3() const { return _S12; }                      // loop keyframe's camera -> current keyframe's camera
     const Sim3 &GetCorrectedPose() const { return _Scw; }             // S12 * T_2w
@@ -188,6 +230,7 @@ private:
     bool _fusable = false;                                            // a corrected loop with such a search that no FuseLoop has used yet
     vector<FusedPair> _fused;
     PoseGraph _pose_graph;
+    BundleProblem _bundle;
     Stats _stats;
 };
 

@@ -51,7 +51,9 @@ extern "C" {
  * ygz_hip_search_by_projection, ygz_hip_projection_candidates) -- no existing argument list changed.
  * Still 6: the Sim3 pose-graph optimiser added (ygz_pgo_params, ygz_pgo_result, ygz_hip_default_pgo_params, ygz_hip_pose_graph_optimize,
  * ygz_hip_pgo_linearize) -- no existing argument list changed.
- * Still 6: the map upkeep of loop fusion added (ygz_hip_distinctive_descriptors, ygz_hip_covisibility) -- no existing argument list changed. */
+ * Still 6: the map upkeep of loop fusion added (ygz_hip_distinctive_descriptors, ygz_hip_covisibility) -- no existing argument list changed.
+ * Still 6: the global bundle adjustment added (ygz_gba_params, ygz_gba_result, ygz_hip_default_gba_params, ygz_hip_global_ba,
+ * ygz_hip_gba_linearize) -- no existing argument list changed. */
 #define YGZ_HIP_ABI_VERSION 6
 
 typedef struct ygz_hip_ctx ygz_hip_ctx;
@@ -861,6 +863,57 @@ int  ygz_hip_distinctive_descriptors(ygz_hip_ctx *ctx, int n_points, const int32
  * YGZ_E_INVALID for an index out of range, a list that is not strictly ascending or a repeated row; last, for a null context. */
 int  ygz_hip_covisibility(ygz_hip_ctx *ctx, int n_points, const int32_t *offsets, const int32_t *kf, int n_keyframes, int n_rows,
                           const int32_t *rows, int32_t *weights);
+
+/* ---- global bundle adjustment after a loop closing -- nothing in the reference; ORB-SLAM2's Optimizer::GlobalBundleAdjustemnt.  N poses
+ * [N][7] (qx qy qz qw tx ty tz, world -> camera), fixed [N] (non-zero: the pose is not moved), L points [L][3], E edges: edge e observes point
+ * edge_point[e] from pose edge_pose[e] at the pixel obs[e]; a (point, pose) pair may appear more than once, and each edge counts.  One
+ * pinhole camera K4 = fx fy cx cy.  Minimises the sum over the edges of rho(|obs - K (R X + t) / z|^2), identity information, rho g2o's Huber
+ * kernel of width huber_delta (5.991 in ORB-SLAM2; <= 0: no kernel), by Levenberg-Marquardt with g2o's rules.  Every step marginalises the
+ * points and solves the reduced camera system by preconditioned conjugate gradients without forming it (the preconditioner: every pose's
+ * 6x6 diagonal block of that system); the update is T <- Delta(d) o T with q_Delta = normalise(omega / 2, 1), X <- X + d.  Many workgroups,
+ * one short kernel per phase; the host queues CG iterations in batches and reads one small record back per batch.  The arithmetic is that
+ * of tests/gba_ref.c: every output is bit-identical to it, whatever cg_batch is. */
+#define YGZ_GBA_MAX_POSES  4096
+#define YGZ_GBA_MAX_POINTS 1048576
+#define YGZ_GBA_MAX_EDGES  4194304
+#define YGZ_GBA_FAILED         0          /* at the input a point is not in front of one of its cameras, or a value is not finite: outputs = inputs */
+#define YGZ_GBA_CONVERGED      1          /* the values of YGZ_PGO_*, with their meanings */
+#define YGZ_GBA_MAX_ITERATIONS 2
+#define YGZ_GBA_STALLED        3
+typedef struct {
+    int32_t max_iterations;               /* 10: LM iterations (the nIterations of ORB-SLAM2's RunGlobalBundleAdjustment), in [1, 1000] */
+    int32_t max_trials;                   /* 10: trials of lambda per iteration, in [1, 100] */
+    int32_t cg_max_iterations;            /* 0: min(6 free poses, 1024); else the cap itself, up to 65536 */
+    int32_t cg_batch;                     /* 0: 8; CG iterations queued between two read-backs of the control record, up to 1024; no output depends on it */
+    double  cg_tol;                       /* 1e-8: CG stops at r^T z <= cg_tol^2 r0^T z0; in (0, 1) */
+    double  min_rel_decrease;             /* 1e-9: in [0, 1) */
+} ygz_gba_params;
+typedef struct {
+    double  cost_initial, cost_final;     /* the robust cost at the input and at the output */
+    double  lambda;                       /* the final damping */
+    int32_t status;                       /* YGZ_GBA_* */
+    int32_t lm_iterations;
+    int32_t n_solves;                     /* CG solves (trials whose blocks could all be factored) */
+    int32_t cg_iterations_total;
+    int32_t cg_capped;                    /* solves that ended at the cap (not an error: the iterate is used) */
+    int32_t pad;
+} ygz_gba_result;
+void ygz_hip_default_gba_params(ygz_gba_params *p);
+/* the whole optimisation: params NULL: defaults; poses_out [N][7], points_out [L][3].  Checked in this order, all before the device is
+ * touched: YGZ_E_INVALID for a null array, output or result; YGZ_E_CAPACITY, by the counts alone, above YGZ_GBA_MAX_POSES poses,
+ * YGZ_GBA_MAX_POINTS points or YGZ_GBA_MAX_EDGES edges; YGZ_E_INVALID for N < 2, L < 1 or E < 1, a parameter out of its range, a non-finite
+ * K4 or huber_delta or a focal length <= 0, an index out of range, a non-finite observation, pose or point, a zero quaternion, a free pose
+ * without an edge, no free pose, a point with fewer than 2 edges; last, YGZ_E_INVALID for a null context. */
+int  ygz_hip_global_ba(ygz_hip_ctx *ctx, int n_poses, const double *poses, const uint8_t *fixed, int n_points, const double *points, int n_edges,
+                       const int32_t *edge_pose, const int32_t *edge_point, const double *obs, const double K4[4], double huber_delta,
+                       const ygz_gba_params *params, double *poses_out, double *points_out, ygz_gba_result *result);
+/* stage for tests: the linearisation at the input -- residuals [E][2], weights [E] (rho'), Jp [E][12] (dr / d(omega, t), 2x6 row-major), Jl
+ * [E][6] (dr / dX, 2x3), Hpp [N][21] and Hll [L][6] (upper triangles row by row; rows of fixed poses are zero), bp [N][6], bl [L][3], cost
+ * [1]; each may be NULL.  The same checks (without the outputs).  Returns YGZ_E_STATE when a residual is undefined (zeros for such an edge). */
+int  ygz_hip_gba_linearize(ygz_hip_ctx *ctx, int n_poses, const double *poses, const uint8_t *fixed, int n_points, const double *points,
+                           int n_edges, const int32_t *edge_pose, const int32_t *edge_point, const double *obs, const double K4[4],
+                           double huber_delta, const ygz_gba_params *params, double *residuals, double *weights, double *Jp, double *Jl,
+                           double *Hpp, double *bp, double *Hll, double *bl, double *cost);
 
 #ifdef __cplusplus
 }

@@ -298,6 +298,57 @@ def pgo_argtypes(lib):
     lib.ygz_hip_pgo_linearize.argtypes = [C.c_void_p, C.c_int, dp, C.POINTER(C.c_uint8), C.c_int, ip, dp, C.POINTER(PgoParams), dp, dp, dp, dp]
 
 
+class GbaParams(C.Structure):
+    """ygz_gba_params (include/ygz_hip.h)"""
+    _fields_ = [("max_iterations", C.c_int32), ("max_trials", C.c_int32), ("cg_max_iterations", C.c_int32), ("cg_batch", C.c_int32),
+                ("cg_tol", C.c_double), ("min_rel_decrease", C.c_double)]
+
+
+class GbaResult(C.Structure):
+    """ygz_gba_result; `lambda_` is the header's `lambda`"""
+    _fields_ = [("cost_initial", C.c_double), ("cost_final", C.c_double), ("lambda_", C.c_double), ("status", C.c_int32),
+                ("lm_iterations", C.c_int32), ("n_solves", C.c_int32), ("cg_iterations_total", C.c_int32), ("cg_capped", C.c_int32),
+                ("pad", C.c_int32)]
+
+    def to_dict(self):
+        return dict((k, getattr(self, k)) for k, _ in self._fields_ if k != "pad")
+
+
+def default_gba_params():
+    p = GbaParams()
+    load().ygz_hip_default_gba_params(C.byref(p))
+    return p
+
+
+def _gba_params(**kw):
+    p = default_gba_params()
+    for k, v in kw.items():
+        if v is not None:
+            setattr(p, k, v)
+    return p
+
+
+def gba_arrays(poses, fixed, points, edge_pose, edge_point, obs):
+    """the six arrays of a bundle-adjustment problem in the ABI's types: poses [N][7], fixed [N] uint8, points [L][3], edge_pose and
+    edge_point [E] int32, obs [E][2]"""
+    poses = np.ascontiguousarray(poses, np.float64).reshape(-1, 7)
+    points = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+    obs = np.ascontiguousarray(obs, np.float64).reshape(-1, 2)
+    fixed = np.ascontiguousarray(fixed, np.uint8).reshape(-1)
+    edge_pose = np.ascontiguousarray(edge_pose, np.int32).reshape(-1)
+    edge_point = np.ascontiguousarray(edge_point, np.int32).reshape(-1)
+    if len(poses) != len(fixed) or not len(edge_pose) == len(edge_point) == len(obs):
+        raise ValueError("poses / fixed or edge_pose / edge_point / obs differ in length")
+    return poses, fixed, points, edge_pose, edge_point, obs
+
+
+def gba_argtypes(lib):
+    dp, ip, bp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
+    problem = [C.c_void_p, C.c_int, dp, bp, C.c_int, dp, C.c_int, ip, ip, dp, dp, C.c_double, C.POINTER(GbaParams)]
+    lib.ygz_hip_global_ba.argtypes = problem + [dp, dp, C.POINTER(GbaResult)]
+    lib.ygz_hip_gba_linearize.argtypes = problem + [dp] * 9
+
+
 def map_argtypes(lib):
     ip, bp = C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
     lib.ygz_hip_distinctive_descriptors.argtypes = [C.c_void_p, C.c_int, ip, bp, ip, ip, bp]
@@ -332,6 +383,7 @@ ABI_SYMBOLS = [
     "ygz_hip_default_proj_params", "ygz_hip_search_by_projection", "ygz_hip_projection_candidates",
     "ygz_hip_default_pgo_params", "ygz_hip_pose_graph_optimize", "ygz_hip_pgo_linearize",
     "ygz_hip_distinctive_descriptors", "ygz_hip_covisibility",
+    "ygz_hip_default_gba_params", "ygz_hip_global_ba", "ygz_hip_gba_linearize",
 ]
 INIT_SYMBOLS = ["ygz_hip_default_init_params", "ygz_hip_initialize", "ygz_hip_init_sample_sets", "ygz_hip_init_hypotheses", "ygz_hip_init_reconstruct"]
 INIT_NONE, INIT_H, INIT_F = 0, 1, 2
@@ -346,6 +398,11 @@ PGO_MAX_VERTICES, PGO_MAX_EDGES = 4096, 32768
 PGO_FAILED, PGO_CONVERGED, PGO_MAX_ITERATIONS, PGO_STALLED = 0, 1, 2, 3
 MAP_SYMBOLS = ["ygz_hip_distinctive_descriptors", "ygz_hip_covisibility"]
 MAP_MAX_OBS_PER_POINT, MAP_MAX_OBS, MAP_MAX_KEYFRAMES, COVIS_MAX_CELLS = 256, 1048576, 4096, 4194304
+
+GBA_SYMBOLS = ["ygz_hip_default_gba_params", "ygz_hip_global_ba", "ygz_hip_gba_linearize"]
+GBA_MAX_POSES, GBA_MAX_POINTS, GBA_MAX_EDGES = 4096, 1048576, 4194304
+GBA_FAILED, GBA_CONVERGED, GBA_MAX_ITERATIONS, GBA_STALLED = 0, 1, 2, 3
+GBA_HUBER = 5.991
 
 SUMMARY_FIELDS = 32
 
@@ -1279,6 +1336,41 @@ class HipContext:
         if rc != E_STATE:
             self._chk(rc, "pgo_linearize")
         return dict(ok=rc == OK, res=res, Ji=Ji, Jj=Jj, cost=float(cost[0]))
+
+    # ---- global bundle adjustment after a loop closing
+
+    def global_ba(self, poses, fixed, points, edge_pose, edge_point, obs, K4, huber_delta=GBA_HUBER, **params):
+        """the whole optimisation in one call (ygz_hip_global_ba): dict(poses [N][7], points [L][3], and the fields of ygz_gba_result).
+        params: the fields of ygz_gba_params; cg_batch is the number of CG iterations queued per read-back (no output depends on it)"""
+        poses, fixed, points, ep, el, obs = gba_arrays(poses, fixed, points, edge_pose, edge_point, obs)
+        K = np.ascontiguousarray(K4, np.float64).reshape(4)
+        prm, res, po, xo = _gba_params(**params), GbaResult(), np.zeros_like(poses), np.zeros_like(points)
+        gba_argtypes(self.lib)
+        self._chk(self.lib.ygz_hip_global_ba(self._ctx, len(poses), _p(poses, C.c_double), _p(fixed, C.c_uint8), len(points), _p(points, C.c_double),
+                                             len(ep), _p(ep, C.c_int32), _p(el, C.c_int32), _p(obs, C.c_double), _p(K, C.c_double), float(huber_delta),
+                                             C.byref(prm), _p(po, C.c_double), _p(xo, C.c_double), C.byref(res)), "global_ba")
+        d = res.to_dict()
+        d["poses"], d["points"] = po, xo
+        return d
+
+    def gba_linearize(self, poses, fixed, points, edge_pose, edge_point, obs, K4, huber_delta=GBA_HUBER, **params):
+        """the linearisation at the input (ygz_hip_gba_linearize): dict(ok, res [E][2], w [E], Jp [E][2][6], Jl [E][2][3], Hpp [N][21], bp
+        [N][6], Hll [L][6], bl [L][3], cost); ok is False when a residual is undefined"""
+        poses, fixed, points, ep, el, obs = gba_arrays(poses, fixed, points, edge_pose, edge_point, obs)
+        K = np.ascontiguousarray(K4, np.float64).reshape(4)
+        N, L, E = len(poses), len(points), len(ep)
+        prm = _gba_params(**params)
+        o = dict(res=np.zeros((E, 2)), w=np.zeros(E), Jp=np.zeros((E, 2, 6)), Jl=np.zeros((E, 2, 3)), Hpp=np.zeros((N, 21)), bp=np.zeros((N, 6)),
+                 Hll=np.zeros((L, 6)), bl=np.zeros((L, 3)))
+        cost = np.zeros(1)
+        gba_argtypes(self.lib)
+        rc = self.lib.ygz_hip_gba_linearize(self._ctx, N, _p(poses, C.c_double), _p(fixed, C.c_uint8), L, _p(points, C.c_double), E, _p(ep, C.c_int32),
+                                            _p(el, C.c_int32), _p(obs, C.c_double), _p(K, C.c_double), float(huber_delta), C.byref(prm),
+                                            *[_p(o[k], C.c_double) for k in ("res", "w", "Jp", "Jl", "Hpp", "bp", "Hll", "bl")], _p(cost, C.c_double))
+        if rc != E_STATE:
+            self._chk(rc, "gba_linearize")
+        o.update(ok=rc == OK, cost=float(cost[0]))
+        return o
 
     # ---- map upkeep after a loop correction
 

@@ -2,7 +2,7 @@
 // half of ORB-SLAM2's LoopClosing::CorrectLoop with Optimizer::OptimizeEssentialGraph's graph: the accepted Sim3 propagated to the current
 // keyframe's neighbourhood, one ygz_hip_pose_graph_optimize call (ygz_slam_amd/csrc/pgo.hip), poses and map points rewritten from its result.
 // Every choice ORB-SLAM2 leaves to set iteration over pointers goes by keyframe id here.  Fusion and the covisibility update are FuseLoop
-// (ygz_fuse.cpp); no global BA.
+// (ygz_fuse.cpp), the global BA GlobalBundleAdjustment (ygz_gba.cpp).
 // Error conventions of the other surfaces: a failed call logs and returns false, only a missing device throws.
 #include "ygz/Algorithm/LoopClosing.h"
 #include "ygz/hip/Runtime.h"

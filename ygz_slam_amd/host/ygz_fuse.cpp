@@ -1,5 +1,5 @@
 // ygz::LoopClosing::FuseLoop / ReplaceMapPoint / UpdateCovisibility and Matcher::ComputeDistinctiveDescriptors (include/ygz/Algorithm/
-// LoopClosing.h, Matcher.h): nothing in the reference.  The rest of ORB-SLAM2's LoopClosing::CorrectLoop up to the global BA: the current
+// LoopClosing.h, Matcher.h): nothing in the reference.  The rest of ORB-SLAM2's LoopClosing::CorrectLoop up to the global BA (ygz_gba.cpp): the current
 // keyframe's loop matches and the hits of Matcher::SearchFuseCandidates over the corrected neighbourhood are acted on (MapPoint::Replace /
 // AddObservation on this data model), then the two pieces of map upkeep that forces run on the device, one call each:
 // ygz_hip_distinctive_descriptors and ygz_hip_covisibility (ygz_slam_amd/csrc/map.hip).  Every order ORB-SLAM2 leaves to set iteration over
