@@ -17,6 +17,8 @@
 // call: every keyframe pose and every map point with two observations or more against all of their observations in one device call
 // (ygz_hip_global_ba: Levenberg-Marquardt, the points marginalised, conjugate gradients on the camera system) --
 // ygz_slam_amd/host/ygz_gba.cpp.  It needs no loop state and may be called at any time.  The integration is in INTEGRATION.md.
+// SetKeyFrameDatabase is optional: with a ygz::KeyFrameDatabase attached DetectLoop takes its BoW scores and common-word counts from one device
+// query instead of one host walk per keyframe; every result is the same bit for bit (ygz/Algorithm/KeyFrameDatabase.h).
 #ifndef YGZ_LOOP_CLOSING_H_
 #define YGZ_LOOP_CLOSING_H_
 
@@ -27,6 +29,8 @@
 
 namespace ygz
 {
+
+class KeyFrameDatabase;
 
 // ygz::Sim3 is defined in ygz/Basic/Sim3.h (Matcher.h names it too) and exposed here as before:
 //   struct Sim3 { SO3 R; Vector3d t; double s; Sim3(); Sim3(R, t, s); explicit Sim3(const SE3 &);
@@ -134,6 +138,14 @@ public:
         double huber_delta = 0;
     };
 
+    // Optional, null by default: where DetectLoop computes, never what.  With a database attached the scores of step 2 and the common-word
+    // counts and scores of step 3 come from ONE KeyFrameDatabase::Query of kf->_bow_vec for every keyframe the database holds, and from the host
+    // functions, as without it, for every other keyframe (and for all of them when the query fails).  Every filter stays where it is and sees
+    // the same numbers, so every return value, Stats field and later stage is identical with, without, or with a partly filled database --
+    // provided the database holds each keyframe's current _bow_vec (it stores the vector as of Add).  Not owned; it outlives its use here.
+    void SetKeyFrameDatabase(KeyFrameDatabase *db) { _kfdb = db; }
+    KeyFrameDatabase *GetKeyFrameDatabase() const { return _kfdb; }
+
     // kf: a keyframe of the map with its covisibility (_connected_keyframe_weights); true when some loop candidate is consistent enough
     bool DetectLoop(Frame *kf, const vector<Frame *> &keyframes);
     bool DetectLoop(Frame *kf);             // every keyframe registered in Memory
@@ -221,6 +233,7 @@ private:
     Frame *_current = nullptr;
     unsigned long _last_loop_kf_id = 0;
     Matcher _matcher;
+    KeyFrameDatabase *_kfdb = nullptr;
     Frame *_matched = nullptr;
     Sim3 _S12, _Scw;
     vector<pair<MapPoint *, MapPoint *>> _matches;

@@ -2,6 +2,8 @@
 // src/Module/VisualOdometry.cpp:101-104 ("try relocalization"), in the manner of ORB-SLAM2's Tracking::Relocalization -- BoW keyframe
 // retrieval, Matcher::SearchByBoW against each candidate, P3P RANSAC of all candidates in one device call (ygz_hip_pnp_ransac), then
 // ba::OptimizeCurrentPoseOnly on the inliers (ygz_slam_amd/host/ygz_reloc.cpp; the integration is in INTEGRATION.md).
+// SetKeyFrameDatabase is optional: with a ygz::KeyFrameDatabase attached the retrieval's BoW scores come from one device query instead of one
+// host walk per keyframe; every result is the same bit for bit (ygz/Algorithm/KeyFrameDatabase.h).
 #ifndef YGZ_RELOCALIZER_H_
 #define YGZ_RELOCALIZER_H_
 
@@ -11,6 +13,8 @@
 
 namespace ygz
 {
+
+class KeyFrameDatabase;
 
 class Relocalizer
 {
@@ -39,10 +43,19 @@ public:
     bool Relocalize(Frame *current, const vector<Frame *> &keyframes);
     bool Relocalize(Frame *current);        // every keyframe registered in Memory
 
+    // Optional, null by default: where Relocalize computes, never what.  With a database attached the BoW scores of the retrieval come from ONE
+    // KeyFrameDatabase::Query of the frame's BoW vector for every keyframe the database holds, and from Vocabulary::score, as without it, for
+    // every other keyframe (and for all of them when the query fails).  Every filter stays where it is and sees the same numbers: the outcome,
+    // the pose and the Stats are identical with, without, or with a partly filled database -- provided the database holds each keyframe's
+    // current _bow_vec (it stores the vector as of Add).  Not owned; it outlives its use here.
+    void SetKeyFrameDatabase(KeyFrameDatabase *db) { _kfdb = db; }
+    KeyFrameDatabase *GetKeyFrameDatabase() const { return _kfdb; }
+
     Frame *GetMatchedKeyframe() const { return _matched; }
     const Stats &GetStats() const { return _stats; }
 
 private:
+    KeyFrameDatabase *_kfdb = nullptr;
     FeatureDetector _detector;
     Matcher _matcher;
     Frame *_matched = nullptr;

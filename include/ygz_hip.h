@@ -53,7 +53,9 @@ extern "C" {
  * ygz_hip_pgo_linearize) -- no existing argument list changed.
  * Still 6: the map upkeep of loop fusion added (ygz_hip_distinctive_descriptors, ygz_hip_covisibility) -- no existing argument list changed.
  * Still 6: the global bundle adjustment added (ygz_gba_params, ygz_gba_result, ygz_hip_default_gba_params, ygz_hip_global_ba,
- * ygz_hip_gba_linearize) -- no existing argument list changed. */
+ * ygz_hip_gba_linearize) -- no existing argument list changed.
+ * Still 6: the keyframe database added (ygz_kfdb, ygz_hip_kfdb_create, ygz_hip_kfdb_destroy, ygz_hip_kfdb_add, ygz_hip_kfdb_erase,
+ * ygz_hip_kfdb_clear, ygz_hip_kfdb_info, ygz_hip_kfdb_query) -- no existing argument list changed. */
 #define YGZ_HIP_ABI_VERSION 6
 
 typedef struct ygz_hip_ctx ygz_hip_ctx;
@@ -914,6 +916,39 @@ int  ygz_hip_gba_linearize(ygz_hip_ctx *ctx, int n_poses, const double *poses, c
                            int n_edges, const int32_t *edge_pose, const int32_t *edge_point, const double *obs, const double K4[4],
                            double huber_delta, const ygz_gba_params *params, double *residuals, double *weights, double *Jp, double *Jl,
                            double *Hpp, double *bp, double *Hll, double *bl, double *cost);
+
+/* ---- keyframe database: place-recognition queries -- nothing in the reference (its relocalisation and loop detection are stubs); ORB-SLAM2's
+ * KeyFrameDatabase over DBoW3's L1 scoring.  The BoW vectors of the keyframes live in HBM; one launch gives, for up to YGZ_KFDB_MAX_QUERIES
+ * query vectors, the common-word count and the L1 score against every stored row.
+ *  - a vector is n pairs (word, weight): words >= 0 and strictly ascending, weights finite and > 0;
+ *  - add appends a row and returns its entry id 0, 1, 2, ...; ids are never reused; n = 0 is a legal row; one upload;
+ *  - erase marks a row dead (erasing a dead row is YGZ_OK and changes nothing); clear empties the database and restarts the ids at 0;
+ *  - device memory grows geometrically with a device-to-device copy: add never fails for lack of room below the caps;
+ *  - query, for every query q and every entry e < n_entries, at [q][e]: a dead entry gives common = -1 and score = 0; otherwise common is the
+ *    number of words the two vectors share and score = -s / 2, where s starts at 0.0 and receives s += fabs(v - w) - fabs(v) - fabs(w) (v the
+ *    query's weight, w the row's) for each shared word in ascending word order, one addition after the other: DBoW3::L1Scoring::score.  One
+ *    upload of the queries, one launch on the context's stream, one copy back and one wait.
+ * Every output is bit-identical to tests/kfdb_ref.c.  Checked in this order, all before the device is touched:
+ * YGZ_E_INVALID for a null array or output (the arrays of an add with n = 0 may be null); YGZ_E_CAPACITY, by the counts alone, for a vector above
+ * YGZ_KFDB_MAX_WORDS words, an add to a database that ever held YGZ_KFDB_MAX_ENTRIES rows since its last clear, more than YGZ_KFDB_MAX_QUERIES
+ * queries; YGZ_E_INVALID for n < 0, n_queries < 1, q_offsets[0] != 0 or a decreasing offset, a negative or non-ascending word, a weight that
+ * is not finite and > 0, an erase of an id never given, a query on a database without rows; last, YGZ_E_INVALID for a null db or ctx.  The
+ * database belongs to its context, is used by one thread at a time like it, and is destroyed before it. */
+#define YGZ_KFDB_MAX_ENTRIES 4096   /* rows ever added to one database (= YGZ_MAP_MAX_KEYFRAMES) */
+#define YGZ_KFDB_MAX_WORDS   8192   /* words of one vector, stored or queried */
+#define YGZ_KFDB_MAX_QUERIES 64     /* queries per call */
+typedef struct ygz_kfdb ygz_kfdb;
+int  ygz_hip_kfdb_create (ygz_hip_ctx *ctx, ygz_kfdb **db);
+void ygz_hip_kfdb_destroy(ygz_kfdb *db);
+int  ygz_hip_kfdb_add    (ygz_kfdb *db, const int32_t *word, const double *weight, int n, int32_t *entry);
+int  ygz_hip_kfdb_erase  (ygz_kfdb *db, int32_t entry);
+int  ygz_hip_kfdb_clear  (ygz_kfdb *db);
+/* each output may be NULL; n_entries: ids given since the last clear; n_alive: those not erased; n_words: the words of all of them, dead rows
+ * included (their memory comes back with clear) */
+int  ygz_hip_kfdb_info   (const ygz_kfdb *db, int32_t *n_entries, int32_t *n_alive, int64_t *n_words);
+/* q_offsets [n_queries + 1]: query q is q_word / q_weight [q_offsets[q] .. q_offsets[q + 1]); common and score [n_queries][n_entries] */
+int  ygz_hip_kfdb_query  (ygz_kfdb *db, int n_queries, const int32_t *q_offsets, const int32_t *q_word, const double *q_weight,
+                          int32_t *common, double *score);
 
 #ifdef __cplusplus
 }

@@ -349,6 +349,27 @@ def gba_argtypes(lib):
     lib.ygz_hip_gba_linearize.argtypes = problem + [dp] * 9
 
 
+def kfdb_argtypes(lib):
+    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    lib.ygz_hip_kfdb_create.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+    lib.ygz_hip_kfdb_destroy.argtypes = [C.c_void_p]
+    lib.ygz_hip_kfdb_destroy.restype = None
+    lib.ygz_hip_kfdb_add.argtypes = [C.c_void_p, ip, dp, C.c_int, ip]
+    lib.ygz_hip_kfdb_erase.argtypes = [C.c_void_p, C.c_int32]
+    lib.ygz_hip_kfdb_clear.argtypes = [C.c_void_p]
+    lib.ygz_hip_kfdb_info.argtypes = [C.c_void_p, ip, ip, C.POINTER(C.c_int64)]
+    lib.ygz_hip_kfdb_query.argtypes = [C.c_void_p, C.c_int, ip, ip, dp, ip, dp]
+
+
+def kfdb_pack(vectors):
+    """a list of (word, weight) pairs as the ABI's q_offsets [n + 1], q_word and q_weight (arrays of at least one element)"""
+    off = np.zeros(len(vectors) + 1, np.int32)
+    off[1:] = np.cumsum([len(w) for w, _ in vectors])
+    word = np.ascontiguousarray(np.concatenate([np.asarray(w, np.int32).reshape(-1) for w, _ in vectors] + [np.zeros(1, np.int32)]))
+    weight = np.ascontiguousarray(np.concatenate([np.asarray(v, np.float64).reshape(-1) for _, v in vectors] + [np.zeros(1)]))
+    return off, word, weight
+
+
 def map_argtypes(lib):
     ip, bp = C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
     lib.ygz_hip_distinctive_descriptors.argtypes = [C.c_void_p, C.c_int, ip, bp, ip, ip, bp]
@@ -384,6 +405,7 @@ ABI_SYMBOLS = [
     "ygz_hip_default_pgo_params", "ygz_hip_pose_graph_optimize", "ygz_hip_pgo_linearize",
     "ygz_hip_distinctive_descriptors", "ygz_hip_covisibility",
     "ygz_hip_default_gba_params", "ygz_hip_global_ba", "ygz_hip_gba_linearize",
+    "ygz_hip_kfdb_create", "ygz_hip_kfdb_destroy", "ygz_hip_kfdb_add", "ygz_hip_kfdb_erase", "ygz_hip_kfdb_clear", "ygz_hip_kfdb_info", "ygz_hip_kfdb_query",
 ]
 INIT_SYMBOLS = ["ygz_hip_default_init_params", "ygz_hip_initialize", "ygz_hip_init_sample_sets", "ygz_hip_init_hypotheses", "ygz_hip_init_reconstruct"]
 INIT_NONE, INIT_H, INIT_F = 0, 1, 2
@@ -403,6 +425,10 @@ GBA_SYMBOLS = ["ygz_hip_default_gba_params", "ygz_hip_global_ba", "ygz_hip_gba_l
 GBA_MAX_POSES, GBA_MAX_POINTS, GBA_MAX_EDGES = 4096, 1048576, 4194304
 GBA_FAILED, GBA_CONVERGED, GBA_MAX_ITERATIONS, GBA_STALLED = 0, 1, 2, 3
 GBA_HUBER = 5.991
+
+KFDB_SYMBOLS = ["ygz_hip_kfdb_create", "ygz_hip_kfdb_destroy", "ygz_hip_kfdb_add", "ygz_hip_kfdb_erase", "ygz_hip_kfdb_clear", "ygz_hip_kfdb_info",
+                "ygz_hip_kfdb_query"]
+KFDB_MAX_ENTRIES, KFDB_MAX_WORDS, KFDB_MAX_QUERIES = 4096, 8192, 64
 
 SUMMARY_FIELDS = 32
 
@@ -1631,3 +1657,57 @@ class HipContext:
                                                d("chi2_edge"), d("chi2")), "ba_download")
         o["chi2"] = float(o["chi2"][0])
         return o
+
+
+class KeyframeDatabase:
+    """One ygz_kfdb on a context (ygz_hip_kfdb_*): BoW vectors resident in HBM, common words and L1 scores of up to KFDB_MAX_QUERIES queries
+    against every row in one launch.  Close it before its context."""
+
+    def __init__(self, ctx):
+        self.lib = ctx.lib
+        kfdb_argtypes(self.lib)
+        self._ctx = ctx
+        self._db = C.c_void_p()
+        ctx._chk(self.lib.ygz_hip_kfdb_create(ctx._ctx, C.byref(self._db)), "kfdb_create")
+
+    def close(self):
+        if self._db:
+            self.lib.ygz_hip_kfdb_destroy(self._db)
+        self._db = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add(self, word, weight):
+        word = np.ascontiguousarray(word, np.int32).reshape(-1)
+        weight = np.ascontiguousarray(weight, np.float64).reshape(-1)
+        if len(word) != len(weight):
+            raise ValueError("word / weight differ in length")
+        entry = C.c_int32(-1)
+        self._ctx._chk(self.lib.ygz_hip_kfdb_add(self._db, _p(word, C.c_int32) if len(word) else None, _p(weight, C.c_double) if len(word) else None,
+                                                 len(word), C.byref(entry)), "kfdb_add")
+        return entry.value
+
+    def erase(self, entry):
+        self._ctx._chk(self.lib.ygz_hip_kfdb_erase(self._db, int(entry)), "kfdb_erase")
+
+    def clear(self):
+        self._ctx._chk(self.lib.ygz_hip_kfdb_clear(self._db), "kfdb_clear")
+
+    def info(self):
+        """(n_entries, n_alive, n_words)"""
+        e, a, w = C.c_int32(), C.c_int32(), C.c_int64()
+        self._ctx._chk(self.lib.ygz_hip_kfdb_info(self._db, C.byref(e), C.byref(a), C.byref(w)), "kfdb_info")
+        return e.value, a.value, w.value
+
+    def query(self, vectors):
+        """vectors: a list of (word, weight); returns common [n_queries][n_entries] int32 and score [n_queries][n_entries] float64"""
+        off, word, weight = kfdb_pack(vectors)
+        n = self.info()[0]
+        common, score = np.zeros((len(vectors), n), np.int32), np.zeros((len(vectors), n), np.float64)
+        self._ctx._chk(self.lib.ygz_hip_kfdb_query(self._db, len(vectors), _p(off, C.c_int32), _p(word, C.c_int32), _p(weight, C.c_double),
+                                                   _p(common, C.c_int32), _p(score, C.c_double)), "kfdb_query")
+        return common, score

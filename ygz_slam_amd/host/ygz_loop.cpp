@@ -3,6 +3,7 @@
 // with every tie broken by keyframe id; the geometric check of all candidates is one ygz_hip_sim3_ransac call (ygz_slam_amd/csrc/sim3.hip).
 // Error conventions of the other surfaces: a failed call logs and returns false, only a missing device throws.
 #include "ygz/Algorithm/LoopClosing.h"
+#include "ygz/Algorithm/KeyFrameDatabase.h"
 #include "ygz/hip/Runtime.h"
 #include "ygz_hip.h"
 #include <algorithm>
@@ -81,12 +82,28 @@ bool LoopClosing::DetectLoop(Frame *kf, const vector<Frame *> &keyframes)
         _consistent_groups.clear();
         return false;
     }
+    // an attached database answers steps 2 and 3 for the keyframes it holds with one device query: the same numbers (KeyFrameDatabase.h)
+    map<const Frame *, KeyFrameDatabase::Hit> db_hit;
+    vector<KeyFrameDatabase::Hit> hits;
+    const bool from_db = _kfdb && Frame::_vocab->scoring_ == 0 && _kfdb->Query(kf->_bow_vec, hits);
+    for (const KeyFrameDatabase::Hit &h : hits) db_hit[h.kf] = h;
+    // held and scored by the query: a keyframe that is not among the hits shares no word, and Vocabulary::score returns -0.0 / 2 for it
+    auto db_answer = [&](Frame *k, int &common, double &score) {
+        if (!from_db || !_kfdb->Has(k)) return false;
+        auto it = db_hit.find(k);
+        common = it != db_hit.end() ? it->second.common : 0;
+        score = it != db_hit.end() ? it->second.score : -0.0 / 2.0;
+        return true;
+    };
     // 2. minScore: the lowest score against the connected keyframes (1 without any)
     double min_score = 1.0;
     for (const auto &c : kf->_connected_keyframe_weights) {
         Frame *n = c.first;
         if (!n || n->_bad || n == kf || !ensure_bow(n)) continue;
-        min_score = std::min(min_score, Frame::_vocab->score(kf->_bow_vec, n->_bow_vec));
+        int cn = 0;
+        double sn = 0;
+        if (!db_answer(n, cn, sn)) sn = Frame::_vocab->score(kf->_bow_vec, n->_bow_vec);
+        min_score = std::min(min_score, sn);
     }
     _stats.min_score = min_score;
 
@@ -96,7 +113,9 @@ bool LoopClosing::DetectLoop(Frame *kf, const vector<Frame *> &keyframes)
     for (Frame *k : keyframes) {
         if (!k || k == kf || k->_bad || kf->_connected_keyframe_weights.count(k)) continue;
         if (!ensure_bow(k)) continue;
-        const int c = common_words(kf->_bow_vec, k->_bow_vec);
+        int c = 0;
+        double sk = 0;
+        if (!db_answer(k, c, sk)) c = common_words(kf->_bow_vec, k->_bow_vec);
         if (c <= 0) continue;
         sharing.push_back(make_pair(k, c));
         max_common = std::max(max_common, c);
@@ -105,7 +124,9 @@ bool LoopClosing::DetectLoop(Frame *kf, const vector<Frame *> &keyframes)
     const double min_common = _option._min_common_words_ratio * max_common;
     for (const auto &s : sharing) {
         if (!(s.second > min_common)) continue;
-        const double si = Frame::_vocab->score(kf->_bow_vec, s.first->_bow_vec);
+        int cs = 0;
+        double si = 0;
+        if (!db_answer(s.first, cs, si)) si = Frame::_vocab->score(kf->_bow_vec, s.first->_bow_vec);
         if (si >= min_score) passed[s.first] = si;
     }
 

@@ -3,6 +3,7 @@
 // are the existing GPU paths; the P3P RANSAC of every candidate keyframe is one ygz_hip_pnp_ransac call (ygz_slam_amd/csrc/pnp.hip).
 // Error conventions of the other surfaces: a failed call logs and returns false, only a missing device throws.
 #include "ygz/Algorithm/Relocalizer.h"
+#include "ygz/Algorithm/KeyFrameDatabase.h"
 #include "ygz/Algorithm/BA.h"
 #include "ygz/hip/Runtime.h"
 #include "ygz_hip.h"
@@ -62,12 +63,21 @@ bool Relocalizer::Relocalize(Frame *current, const vector<Frame *> &keyframes)
     if (detected.empty() || current->_bow_vec.empty()) return finish(false);
 
     // 3. candidates by BoW score: >= _min_score_ratio of the best and > 0, best first, ties by keyframe id
+    // (an attached database answers for the keyframes it holds with one device query: the same numbers, KeyFrameDatabase.h)
+    map<const Frame *, double> db_score;
+    vector<KeyFrameDatabase::Hit> hits;
+    const bool from_db = _kfdb && Frame::_vocab->scoring_ == 0 && _kfdb->Query(current->_bow_vec, hits);
+    for (const KeyFrameDatabase::Hit &h : hits) db_score[h.kf] = h.score;
     vector<Candidate> cands;
     for (Frame *kf : keyframes) {
         if (!kf || kf->_bad || kf == current) continue;
         Candidate c;
         c.kf = kf;
-        c.score = Frame::_vocab->score(current->_bow_vec, kf->_bow_vec);
+        if (from_db && _kfdb->Has(kf)) {
+            auto it = db_score.find(kf);
+            c.score = it != db_score.end() ? it->second : -0.0 / 2.0;             // no shared word: what Vocabulary::score returns
+        } else
+            c.score = Frame::_vocab->score(current->_bow_vec, kf->_bow_vec);
         if (c.score > 0) cands.push_back(std::move(c));
     }
     std::sort(cands.begin(), cands.end(), [](const Candidate &a, const Candidate &b) {
