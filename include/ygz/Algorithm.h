@@ -8,6 +8,7 @@
 #include "ygz/Algorithm/BA.h"
 #include "ygz/Algorithm/Initializer.h"
 #include "ygz/Algorithm/KeyFrameDatabase.h"
+#include "ygz/Algorithm/KeyFrameCulling.h"
 #include "ygz/Algorithm/Relocalizer.h"
 #include "ygz/Algorithm/LoopClosing.h"
 #endif

@@ -55,7 +55,9 @@ extern "C" {
  * Still 6: the global bundle adjustment added (ygz_gba_params, ygz_gba_result, ygz_hip_default_gba_params, ygz_hip_global_ba,
  * ygz_hip_gba_linearize) -- no existing argument list changed.
  * Still 6: the keyframe database added (ygz_kfdb, ygz_hip_kfdb_create, ygz_hip_kfdb_destroy, ygz_hip_kfdb_add, ygz_hip_kfdb_erase,
- * ygz_hip_kfdb_clear, ygz_hip_kfdb_info, ygz_hip_kfdb_query) -- no existing argument list changed. */
+ * ygz_hip_kfdb_clear, ygz_hip_kfdb_info, ygz_hip_kfdb_query) -- no existing argument list changed.
+ * Still 6: keyframe culling added (ygz_cull_params, ygz_hip_default_cull_params, ygz_hip_keyframe_redundancy, ygz_hip_cull_keyframes) -- no
+ * existing argument list changed. */
 #define YGZ_HIP_ABI_VERSION 6
 
 typedef struct ygz_hip_ctx ygz_hip_ctx;
@@ -949,6 +951,45 @@ int  ygz_hip_kfdb_info   (const ygz_kfdb *db, int32_t *n_entries, int32_t *n_ali
 /* q_offsets [n_queries + 1]: query q is q_word / q_weight [q_offsets[q] .. q_offsets[q + 1]); common and score [n_queries][n_entries] */
 int  ygz_hip_kfdb_query  (ygz_kfdb *db, int n_queries, const int32_t *q_offsets, const int32_t *q_word, const double *q_weight,
                           int32_t *common, double *score);
+
+/* ---- keyframe culling -- the reference has the stage written and switched off (LocalMapping::KeyFrameCulling, LocalMapping.cpp:579-618, its
+ * call at :327 commented out); ORB-SLAM2's LocalMapping::KeyFrameCulling.  The input is ygz_hip_covisibility's point-major CSR plus one array:
+ * kf [n_obs] keyframe indices in [0, n_keyframes), strictly ascending within a point, level [n_obs] the pyramid level of the observing
+ * feature, in [0, 15].  The state is removed [K] (all 0), live [p] (the length of p's list) and dead [p] (all 0).  Under a state
+ *  - tracked(a) is the number of points with dead = 0 whose list holds a;
+ *  - redundant(a) the number of those for which at least th_obs entries b of the list have b != a, removed[b] = 0 and (level_slack < 0 or
+ *    level_b <= level_a + level_slack): the reference's `_obs.size() > th_obs` followed by `nobs >= th_obs`.
+ * The walk visits the candidates in the caller's order.  Candidate c is culled exactly when (double)redundant > ratio * (double)tracked (one
+ * multiplication, one comparison: never when tracked is 0).  A cull sets removed[c] = 1 and takes one `live` from every point of c; a point
+ * whose live falls below min_obs gets dead = 1 and never counts again.  A point is never dead before a removal has touched it.  Every output is
+ * an integer and bit-identical to tests/cull_ref.c. */
+#define YGZ_CULL_MAX_KEYFRAMES 4096       /* K and n_cand (= YGZ_MAP_MAX_KEYFRAMES) */
+typedef struct {
+    int32_t th_obs;                       /* 3 (LocalMapping.cpp:591): observers that make a point redundant, in [1, 256] */
+    int32_t level_slack;                  /* -1: no scale test (the reference's rule); >= 0: ORB-SLAM2's scaleLevel_b <= scaleLevel_a + slack (it uses 1); in [-1, 15] */
+    int32_t min_obs;                      /* 2: a point needs this many live observations to stay in the map, in [0, 256] */
+    int32_t pad;
+    double  ratio;                        /* 0.9 (LocalMapping.cpp:615), in [0, 1] */
+} ygz_cull_params;
+void ygz_hip_default_cull_params(ygz_cull_params *p);
+/* the counts of every keyframe on the initial state: tracked and redundant [n_keyframes].  params NULL: defaults.  Many workgroups that reduce
+ * in LDS before they touch a global counter; one upload, the clear and the launch, one copy back and one wait.  Checked in this order, all before
+ * the device is touched: YGZ_E_INVALID for a null array; YGZ_E_CAPACITY for n_keyframes above YGZ_CULL_MAX_KEYFRAMES; YGZ_E_INVALID for th_obs
+ * outside [1, 256], min_obs outside [0, 256], level_slack outside [-1, 15], a ratio that is not finite or outside [0, 1], n_points < 1,
+ * n_keyframes < 1, offsets[0] != 0 or a decreasing offset; YGZ_E_CAPACITY for a point with more than YGZ_MAP_MAX_OBS_PER_POINT observations or
+ * more than YGZ_MAP_MAX_OBS in the call; YGZ_E_INVALID for an index out of range, a list that is not strictly ascending or a level outside
+ * [0, 15]; last, for a null context. */
+int  ygz_hip_keyframe_redundancy(ygz_hip_ctx *ctx, int n_points, const int32_t *offsets, const int32_t *kf, const int32_t *level, int n_keyframes,
+                                 const ygz_cull_params *params, int32_t *tracked, int32_t *redundant);
+/* the whole walk over cand [n_cand], distinct keyframe indices: culled [n_cand] (0 / 1), tracked and redundant [n_cand] the counts each
+ * decision was made on, point_dead [n_points] (or NULL) the dead flags of the final state.  The entry point builds the keyframe-major index of
+ * the candidates' observations beside the upload; one resident workgroup steps through the candidates and strides over a candidate's
+ * observations, however many.  One upload, one launch, one copy back and one wait.  The checks of ygz_hip_keyframe_redundancy, with n_cand
+ * beside n_keyframes (YGZ_E_CAPACITY above YGZ_CULL_MAX_KEYFRAMES, YGZ_E_INVALID below 1) and, before the null context, YGZ_E_INVALID for a
+ * candidate out of range or repeated. */
+int  ygz_hip_cull_keyframes(ygz_hip_ctx *ctx, int n_points, const int32_t *offsets, const int32_t *kf, const int32_t *level, int n_keyframes,
+                            int n_cand, const int32_t *cand, const ygz_cull_params *params, int32_t *culled, int32_t *tracked,
+                            int32_t *redundant, uint8_t *point_dead);
 
 #ifdef __cplusplus
 }

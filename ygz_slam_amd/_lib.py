@@ -376,6 +376,45 @@ def map_argtypes(lib):
     lib.ygz_hip_covisibility.argtypes = [C.c_void_p, C.c_int, ip, ip, C.c_int, C.c_int, ip, ip]
 
 
+class CullParams(C.Structure):
+    """ygz_cull_params (include/ygz_hip.h)"""
+    _fields_ = [("th_obs", C.c_int32), ("level_slack", C.c_int32), ("min_obs", C.c_int32), ("pad", C.c_int32), ("ratio", C.c_double)]
+
+
+def default_cull_params():
+    p = CullParams()
+    load().ygz_hip_default_cull_params(C.byref(p))
+    return p
+
+
+def _cull_params(**kw):
+    p = default_cull_params()
+    for k, v in kw.items():
+        if v is not None:
+            setattr(p, k, v)
+    return p
+
+
+def cull_argtypes(lib):
+    ip, bp, pp = C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(CullParams)
+    lib.ygz_hip_default_cull_params.argtypes = [pp]
+    lib.ygz_hip_default_cull_params.restype = None
+    lib.ygz_hip_keyframe_redundancy.argtypes = [C.c_void_p, C.c_int, ip, ip, ip, C.c_int, pp, ip, ip]
+    lib.ygz_hip_cull_keyframes.argtypes = [C.c_void_p, C.c_int, ip, ip, ip, C.c_int, C.c_int, ip, pp, ip, ip, ip, bp]
+
+
+def cull_arrays(offsets, kf, level):
+    """the three arrays of the observation lists in the ABI's types (kf and level of at least one element)"""
+    off = np.ascontiguousarray(offsets, np.int32).reshape(-1)
+    k = np.ascontiguousarray(kf, np.int32).reshape(-1)
+    l = np.ascontiguousarray(level, np.int32).reshape(-1)
+    if len(off) < 2 or int(off[-1]) != len(k) or len(k) != len(l):
+        raise ValueError("offsets do not describe kf and level")
+    if not len(k):
+        k, l = np.zeros(1, np.int32), np.zeros(1, np.int32)
+    return off, k, l
+
+
 # every symbol include/ygz_hip.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
     "ygz_hip_default_params", "ygz_hip_create", "ygz_hip_destroy", "ygz_hip_synchronize", "ygz_hip_join", "ygz_hip_set_overlap", "ygz_hip_error_string",
@@ -406,6 +445,7 @@ ABI_SYMBOLS = [
     "ygz_hip_distinctive_descriptors", "ygz_hip_covisibility",
     "ygz_hip_default_gba_params", "ygz_hip_global_ba", "ygz_hip_gba_linearize",
     "ygz_hip_kfdb_create", "ygz_hip_kfdb_destroy", "ygz_hip_kfdb_add", "ygz_hip_kfdb_erase", "ygz_hip_kfdb_clear", "ygz_hip_kfdb_info", "ygz_hip_kfdb_query",
+    "ygz_hip_default_cull_params", "ygz_hip_keyframe_redundancy", "ygz_hip_cull_keyframes",
 ]
 INIT_SYMBOLS = ["ygz_hip_default_init_params", "ygz_hip_initialize", "ygz_hip_init_sample_sets", "ygz_hip_init_hypotheses", "ygz_hip_init_reconstruct"]
 INIT_NONE, INIT_H, INIT_F = 0, 1, 2
@@ -429,6 +469,9 @@ GBA_HUBER = 5.991
 KFDB_SYMBOLS = ["ygz_hip_kfdb_create", "ygz_hip_kfdb_destroy", "ygz_hip_kfdb_add", "ygz_hip_kfdb_erase", "ygz_hip_kfdb_clear", "ygz_hip_kfdb_info",
                 "ygz_hip_kfdb_query"]
 KFDB_MAX_ENTRIES, KFDB_MAX_WORDS, KFDB_MAX_QUERIES = 4096, 8192, 64
+
+CULL_SYMBOLS = ["ygz_hip_default_cull_params", "ygz_hip_keyframe_redundancy", "ygz_hip_cull_keyframes"]
+CULL_MAX_KEYFRAMES = 4096
 
 SUMMARY_FIELDS = 32
 
@@ -1430,6 +1473,36 @@ class HipContext:
         self._chk(self.lib.ygz_hip_covisibility(self._ctx, P, _p(off, C.c_int32), _p(k, C.c_int32), int(n_keyframes), len(r), _p(r, C.c_int32),
                                                 _p(w, C.c_int32)), "covisibility")
         return w
+
+    # ---- keyframe culling
+
+    def keyframe_redundancy(self, offsets, kf, level, n_keyframes, **params):
+        """the culling counts of every keyframe (ygz_hip_keyframe_redundancy): offsets [P + 1], kf [n_obs] ascending within a point, level
+        [n_obs]; params: the fields of ygz_cull_params; dict(tracked [K], redundant [K])"""
+        off, k, l = cull_arrays(offsets, kf, level)
+        K = int(n_keyframes)
+        prm = _cull_params(**params)
+        t, r = np.full(max(K, 1), -2, np.int32), np.full(max(K, 1), -2, np.int32)
+        cull_argtypes(self.lib)
+        self._chk(self.lib.ygz_hip_keyframe_redundancy(self._ctx, len(off) - 1, _p(off, C.c_int32), _p(k, C.c_int32), _p(l, C.c_int32), K,
+                                                       C.byref(prm), _p(t, C.c_int32), _p(r, C.c_int32)), "keyframe_redundancy")
+        return dict(tracked=t, redundant=r)
+
+    def cull_keyframes(self, offsets, kf, level, n_keyframes, cand, **params):
+        """ORB-SLAM2's culling walk over the candidates in the order given (ygz_hip_cull_keyframes); dict(culled, tracked, redundant
+        [n_cand], point_dead [P] uint8)"""
+        off, k, l = cull_arrays(offsets, kf, level)
+        c = np.ascontiguousarray(cand, np.int32).reshape(-1)
+        n, P = len(c), len(off) - 1
+        prm = _cull_params(**params)
+        o = dict(culled=np.full(max(n, 1), -2, np.int32), tracked=np.full(max(n, 1), -2, np.int32), redundant=np.full(max(n, 1), -2, np.int32),
+                 point_dead=np.full(P, 0xAA, np.uint8))
+        c = c if n else np.zeros(1, np.int32)
+        cull_argtypes(self.lib)
+        self._chk(self.lib.ygz_hip_cull_keyframes(self._ctx, P, _p(off, C.c_int32), _p(k, C.c_int32), _p(l, C.c_int32), int(n_keyframes), n,
+                                                  _p(c, C.c_int32), C.byref(prm), _p(o["culled"], C.c_int32), _p(o["tracked"], C.c_int32),
+                                                  _p(o["redundant"], C.c_int32), _p(o["point_dead"], C.c_uint8)), "cull_keyframes")
+        return o
 
     # ---- BoW
     def vocab_load(self, blob):
