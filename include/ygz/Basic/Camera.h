@@ -26,6 +26,21 @@ public:
     inline float cx() const { return _cx; }
     inline float cy() const { return _cy; }
     inline float focal() const { return _f; }
+    // the lens coefficients of camera.k1, k2, p1, p2 (0 when the configuration has none)
+    inline float k1() const { return _k1; }
+    inline float k2() const { return _k2; }
+    inline float p1() const { return _p1; }
+    inline float p2() const { return _p2; }
+    inline bool HasDistortion() const { return _k1 != 0 || _k2 != 0 || _p1 != 0 || _p2 != 0; }
+    // Brown-Conrady on normalised coordinates, k3 = 0: the model Frame::InitFrame undistorts level 0 with (ygz_hip_set_undistortion, the order and
+    // parentheses of tests/undist_ref.c).  Not the reference's UndistortPoint, whose tangential terms are not Brown-Conrady's
+    inline Vector2d DistortPoint(const Vector2d &p) const
+    {
+        const double k1 = _k1, k2 = _k2, p1 = _p1, p2 = _p2, x = p[0], y = p[1];
+        const double x2 = x * x, y2 = y * y, r2 = x2 + y2, xy2 = 2.0 * (x * y);
+        const double kr = 1.0 + ((0.0 * r2 + k2) * r2 + k1) * r2;
+        return Vector2d((x * kr + p1 * xy2) + p2 * (r2 + 2.0 * x2), (y * kr + p1 * (r2 + 2.0 * y2)) + p2 * xy2);
+    }
     inline Matrix3d GetCameraMatrix() const                     // Camera.h:28-34
     { Matrix3d m; m(0, 0) = _fx; m(0, 2) = _cx; m(1, 1) = _fy; m(1, 2) = _cy; m(2, 2) = 1; return m; }
 protected:

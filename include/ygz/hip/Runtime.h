@@ -19,6 +19,9 @@ public:
     ygz_hip_ctx *ctx();                 // throws std::runtime_error if no usable gfx950 device (no CPU fallback)
     int cells();
     int Resident(Frame *f);             // HBM slot of f (uploads / rebuilds the pyramid if it was evicted)
+    // image (CV_8UC3 BGR or CV_8UC1) into slot + its pyramid; through the lens undistortion (ygz_hip_build_pyramid_undistorted, the map set once per
+    // camera) when Frame's camera -- or, without one, the configuration -- has a non-zero k1, k2, p1 or p2; otherwise exactly the calls made before
+    bool UploadColor(int slot, const cv::Mat &image);
     void Release(Frame *f);
     void RegisterLevels(Frame *f);
     bool FindLevel(const uint8_t *data, Frame **f, int *level);

@@ -57,7 +57,9 @@ extern "C" {
  * Still 6: the keyframe database added (ygz_kfdb, ygz_hip_kfdb_create, ygz_hip_kfdb_destroy, ygz_hip_kfdb_add, ygz_hip_kfdb_erase,
  * ygz_hip_kfdb_clear, ygz_hip_kfdb_info, ygz_hip_kfdb_query) -- no existing argument list changed.
  * Still 6: keyframe culling added (ygz_cull_params, ygz_hip_default_cull_params, ygz_hip_keyframe_redundancy, ygz_hip_cull_keyframes) -- no
- * existing argument list changed. */
+ * existing argument list changed.
+ * Still 6: lens undistortion added (ygz_undistort_params, ygz_hip_default_undistort_params, ygz_hip_set_undistortion, ygz_hip_undistort_map,
+ * ygz_hip_build_pyramid_undistorted) -- no existing argument list changed. */
 #define YGZ_HIP_ABI_VERSION 6
 
 typedef struct ygz_hip_ctx ygz_hip_ctx;
@@ -133,6 +135,34 @@ int  ygz_hip_download_level(ygz_hip_ctx *ctx, int slot, int level, uint8_t *dst 
  * dst [h + 48][w + 48]; YGZ_E_STATE when the slot has no current framed copy of the level.  (Test / debugging aid.) */
 int  ygz_hip_download_framed_level(ygz_hip_ctx *ctx, int slot, int level, uint8_t *dst);
 int  ygz_hip_level_size(const ygz_hip_ctx *ctx, int level, int *w, int *h);
+
+/* ---- A0: lens undistortion in front of the pyramid -- the reference reads camera.k1, k2, p1, p2 (Basic/Camera.h) and never uses them; every
+ * kernel behind level 0 assumes an ideal pinhole picture.  The model is OpenCV's: initUndistortRectifyMap with R = I, then remap with
+ * INTER_LINEAR in its 5-bit fixed point and a constant border.  For output pixel (u, v) of the context's camera (its float intrinsics as
+ * doubles, _d below), in FP64 without contraction:
+ *   x = (u - cx_d) / fx_d, y = (v - cy_d) / fy_d; x2 = x x, y2 = y y, r2 = x2 + y2, xy2 = 2 (x y); kr = 1 + ((k3 r2 + k2) r2 + k1) r2;
+ *   xd = (x kr + p1 xy2) + p2 (r2 + 2 x2); yd = (y kr + p1 (r2 + 2 y2)) + p2 xy2; mx = fx xd + cx, my = fy yd + cy.
+ * Outside -- !(mx > -2 && mx < w + 1 && my > -2 && my < h + 1), NaN included -- the pixel is border_value and both map entries INT32_MIN.
+ * Otherwise qx = (int32) rint(32 mx) (half to even), sx = qx >> 5, ax = qx & 31, the same for y, the four taps (sy, sx) .. (sy + 1, sx + 1)
+ * with border_value outside the picture, and out = ((32-ax)(32-ay) t00 + ax (32-ay) t01 + (32-ax) ay t10 + ax ay t11 + 512) >> 10.  A BGR
+ * picture is converted per tap with the gray formula of ygz_hip_build_pyramid.  The map and the image are bit-identical to tests/undist_ref.c
+ * (DESIGN.md section 18); parity with OpenCV itself is unpinned. */
+typedef struct {
+    double k1, k2, p1, p2, k3;          /* Brown-Conrady coefficients of the camera that took the picture */
+    double fx, fy, cx, cy;              /* its intrinsics (the output camera is the context's ygz_hip_params) */
+    int    border_value;                /* gray value of what the picture does not cover, in [0, 255] */
+} ygz_undistort_params;
+/* zero coefficients, the context's intrinsics, border 0.  YGZ_E_INVALID for a null argument */
+int  ygz_hip_default_undistort_params(const ygz_hip_ctx *ctx, ygz_undistort_params *p);
+/* builds the map of the context's size (one launch, synchronous); p == NULL drops it.  YGZ_E_INVALID for a field that is not finite, fx or
+ * fy <= 0, border_value outside [0, 255]; last, for a null context */
+int  ygz_hip_set_undistortion(ygz_hip_ctx *ctx, const ygz_undistort_params *p);
+/* the map, qx and qy [h][w] (test aid; synchronises).  YGZ_E_STATE without a map */
+int  ygz_hip_undistort_map(ygz_hip_ctx *ctx, int32_t *qx, int32_t *qy);
+/* ygz_hip_build_pyramid with level 0 = the undistorted gray of the uploaded picture (from_bgr: of the BGR upload, else of the gray upload, which
+ * is first copied aside on the same stream).  One call: the remap, the pyramid and the tracker's framed copies follow one another on one
+ * stream, also beside a trailing LK launch.  YGZ_E_STATE without a map.  ygz_hip_build_pyramid itself never undistorts. */
+int  ygz_hip_build_pyramid_undistorted(ygz_hip_ctx *ctx, int slot_begin, int n_slots, int from_bgr);
 
 /* ---- A2-A7: extractor -- replaces FeatureDetector::Detect
  *      (src/Algorithm/FeatureDetector.cpp:345-444: fast_corner_detect_10 + fast_corner_score_10

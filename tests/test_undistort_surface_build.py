@@ -1,0 +1,104 @@
+"""The lens-undistortion surface without a device: tests/cpp/undist_surface.cpp, written against include/ygz only, compiles and links with
+-Wl,--no-undefined; PinholeCamera declares DistortPoint and the coefficients; the C ABI symbols are bound by the loader and exported; every
+invalid call comes back YGZ_E_INVALID with a null context (the context is checked last, so a valid call with a null context is refused too);
+ygz_undistort_params has the size and the fields of the restatement's struct; the new sources read no environment variable."""
+import ctypes
+import os
+import re
+import subprocess
+
+from conftest import ROOT
+
+import undist_ref as ur
+
+PKG = os.path.join(ROOT, "ygz_slam_amd")
+
+
+def build_program(out_dir):
+    """compile tests/cpp/undist_surface.cpp into a program in out_dir (also used by tests/test_gpu_undistort_surface.py)"""
+    exe = os.path.join(out_dir, "undist_surface")
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-Wall", "-I", os.path.join(ROOT, "include"),
+                           os.path.join(ROOT, "tests", "cpp", "undist_surface.cpp"), "-o", exe, "-L", PKG, "-lygz_host", "-lygz_hip",
+                           "-Wl,--no-undefined", "-Wl,-rpath," + PKG])
+    return exe
+
+
+def test_program_compiles_and_links(tmp_path):
+    assert os.path.exists(os.path.join(PKG, "libygz_host.so")), "libygz_host.so is not built (run __graft_entry__.build())"
+    exe = build_program(str(tmp_path))
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)          # no arguments: the usage line, no device touched
+    assert r.returncode == 2 and "usage" in r.stderr
+
+
+def test_public_surface():
+    cam = open(os.path.join(ROOT, "include", "ygz", "Basic", "Camera.h")).read()
+    for decl in [r"Vector2d\s+DistortPoint\s*\(\s*const\s+Vector2d\s*&", r"float\s+k1\s*\(\s*\)\s*const", r"float\s+k2\s*\(\s*\)\s*const",
+                 r"float\s+p1\s*\(\s*\)\s*const", r"float\s+p2\s*\(\s*\)\s*const", r"bool\s+HasDistortion\s*\(\s*\)\s*const"]:
+        assert re.search(decl, cam), decl
+    rt = open(os.path.join(ROOT, "include", "ygz", "hip", "Runtime.h")).read()
+    assert re.search(r"bool\s+UploadColor\s*\(\s*int\s+slot\s*,\s*const\s+cv::Mat\s*&", rt)
+    host = open(os.path.join(PKG, "host", "ygz_host.cpp")).read()
+    # one place makes the undistorting call, for InitFrame and for the re-upload from _color; the re-upload from the mirror stays plain
+    assert host.count("ygz_hip_build_pyramid_undistorted(") == 1 and host.count("ygz_hip_set_undistortion(") == 1
+    assert host.count("UploadColor(slot, ") == 2
+    assert re.search(r"upload_gray\(c, slot, f->_pyramid\[0\]\.data[^\n]*ygz_hip_build_pyramid\(c, slot, 1, 0\)", host)
+    hip = open(os.path.join(PKG, "csrc", "undistort.hip")).read()
+    code = re.sub(r"//[^\n]*", "", hip)
+    for word in ["getenv", "atomic", "hipLaunchCooperativeKernel", "cooperative_groups", "__threadfence"]:
+        assert word not in code, word
+    new_host = host[host.index("bool Runtime::UploadColor"):host.index("// HBM slot of a frame")]
+    assert "getenv" not in new_host and "getenv" not in open(os.path.join(ROOT, "tests", "cpp", "undist_surface.cpp")).read()
+    ctx = open(os.path.join(PKG, "csrc", "ctx.hip")).read()
+    # one body behind both pyramid calls
+    assert ctx.count("build_pyramid_body(ctx, slot_begin, n_slots, from_bgr, ") == 2 and ctx.count("klt_flip_sets(ctx)") == 1
+
+
+def test_symbols_are_bound_and_exported(hip_lib):
+    lib = hip_lib.load()
+    assert hip_lib.UNDISTORT_SYMBOLS == ["ygz_hip_default_undistort_params", "ygz_hip_set_undistortion", "ygz_hip_undistort_map",
+                                         "ygz_hip_build_pyramid_undistorted"]
+    for s in hip_lib.UNDISTORT_SYMBOLS:
+        assert s in hip_lib.ABI_SYMBOLS and hasattr(lib, s), s
+    hdr = open(os.path.join(ROOT, "include", "ygz_hip.h")).read()
+    assert re.search(r"Still 6: lens undistortion added", hdr) and hip_lib.ABI_VERSION == 6 == lib.ygz_hip_abi_version()
+    for s in hip_lib.UNDISTORT_SYMBOLS:
+        assert re.search(r"\bint\s+%s\s*\(" % s, hdr), s
+    # the struct: the header's fields in the header's order, the restatement's layout
+    body = re.search(r"typedef struct \{([^}]*)\} ygz_undistort_params;", hdr).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    names = [n.strip() for decl in body.split(";") if decl.strip() for n in re.sub(r"^\s*(double|int)\s+", "", decl.strip()).split(",")]
+    assert names == [n for n, _ in hip_lib.UndistortParams._fields_] == [n for n, _ in ur.Params._fields_]
+    assert ctypes.sizeof(hip_lib.UndistortParams) == ctypes.sizeof(ur.Params) == ur.lib().ur_params_size() == 80
+    for (n, t), (rn, rtype) in zip(hip_lib.UndistortParams._fields_, ur.Params._fields_):
+        assert getattr(hip_lib.UndistortParams, n).offset == getattr(ur.Params, rn).offset and ctypes.sizeof(t) == ctypes.sizeof(rtype), n
+    assert hip_lib.UNDISTORT_OUTSIDE == ur.OUTSIDE == -2 ** 31
+
+
+def test_every_call_is_refused_with_a_null_context(hip_lib):
+    lib = hip_lib.load()
+    hip_lib.undistort_argtypes(lib)
+    INV = hip_lib.E_INVALID
+    good = dict(k1=0.1, k2=-0.2, p1=0.001, p2=-0.002, k3=0.3, fx=500.0, fy=501.0, cx=320.0, cy=240.0, border_value=0)
+
+    def set_(**kw):
+        v = dict(good, **kw)
+        p = hip_lib.UndistortParams(*[v[n] for n, _ in hip_lib.UndistortParams._fields_])
+        return lib.ygz_hip_set_undistortion(None, ctypes.byref(p))
+    assert set_() == INV and set_(border_value=255) == INV                      # valid: only the context is missing
+    assert lib.ygz_hip_set_undistortion(None, None) == INV                       # dropping the map of no context
+    for name in ("k1", "k2", "p1", "p2", "k3", "fx", "fy", "cx", "cy"):
+        for bad in (float("nan"), float("inf"), -float("inf")):
+            assert set_(**{name: bad}) == INV, (name, bad)
+    for bad in (dict(fx=0.0), dict(fy=0.0), dict(fx=-500.0), dict(fy=-1e-300), dict(border_value=-1), dict(border_value=256)):
+        assert set_(**bad) == INV, bad
+    p = hip_lib.UndistortParams(*[1.0] * 9, 77)
+    assert lib.ygz_hip_default_undistort_params(None, ctypes.byref(p)) == INV
+    assert (p.k1, p.fx, p.border_value) == (0.0, 0.0, 0)                         # zeroed all the same
+    assert lib.ygz_hip_default_undistort_params(None, None) == INV
+    import numpy as np
+    q = np.zeros(4, np.int32)
+    ip = q.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+    assert lib.ygz_hip_undistort_map(None, ip, ip) == INV and lib.ygz_hip_undistort_map(None, None, None) == INV
+    for args in ((0, 1, 0), (0, 1, 1), (-1, 1, 0), (0, 0, 0)):
+        assert lib.ygz_hip_build_pyramid_undistorted(None, *args) == INV
+        assert lib.ygz_hip_build_pyramid(None, *args) == INV

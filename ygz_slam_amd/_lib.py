@@ -415,6 +415,20 @@ def cull_arrays(offsets, kf, level):
     return off, k, l
 
 
+class UndistortParams(C.Structure):
+    """ygz_undistort_params (include/ygz_hip.h)"""
+    _fields_ = [("k1", C.c_double), ("k2", C.c_double), ("p1", C.c_double), ("p2", C.c_double), ("k3", C.c_double),
+                ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("border_value", C.c_int)]
+
+
+def undistort_argtypes(lib):
+    ip, pp = C.POINTER(C.c_int32), C.POINTER(UndistortParams)
+    lib.ygz_hip_default_undistort_params.argtypes = [C.c_void_p, pp]
+    lib.ygz_hip_set_undistortion.argtypes = [C.c_void_p, pp]
+    lib.ygz_hip_undistort_map.argtypes = [C.c_void_p, ip, ip]
+    lib.ygz_hip_build_pyramid_undistorted.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+
+
 # every symbol include/ygz_hip.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
     "ygz_hip_default_params", "ygz_hip_create", "ygz_hip_destroy", "ygz_hip_synchronize", "ygz_hip_join", "ygz_hip_set_overlap", "ygz_hip_error_string",
@@ -446,6 +460,7 @@ ABI_SYMBOLS = [
     "ygz_hip_default_gba_params", "ygz_hip_global_ba", "ygz_hip_gba_linearize",
     "ygz_hip_kfdb_create", "ygz_hip_kfdb_destroy", "ygz_hip_kfdb_add", "ygz_hip_kfdb_erase", "ygz_hip_kfdb_clear", "ygz_hip_kfdb_info", "ygz_hip_kfdb_query",
     "ygz_hip_default_cull_params", "ygz_hip_keyframe_redundancy", "ygz_hip_cull_keyframes",
+    "ygz_hip_default_undistort_params", "ygz_hip_set_undistortion", "ygz_hip_undistort_map", "ygz_hip_build_pyramid_undistorted",
 ]
 INIT_SYMBOLS = ["ygz_hip_default_init_params", "ygz_hip_initialize", "ygz_hip_init_sample_sets", "ygz_hip_init_hypotheses", "ygz_hip_init_reconstruct"]
 INIT_NONE, INIT_H, INIT_F = 0, 1, 2
@@ -472,6 +487,9 @@ KFDB_MAX_ENTRIES, KFDB_MAX_WORDS, KFDB_MAX_QUERIES = 4096, 8192, 64
 
 CULL_SYMBOLS = ["ygz_hip_default_cull_params", "ygz_hip_keyframe_redundancy", "ygz_hip_cull_keyframes"]
 CULL_MAX_KEYFRAMES = 4096
+
+UNDISTORT_SYMBOLS = ["ygz_hip_default_undistort_params", "ygz_hip_set_undistortion", "ygz_hip_undistort_map", "ygz_hip_build_pyramid_undistorted"]
+UNDISTORT_OUTSIDE = -2 ** 31
 
 SUMMARY_FIELDS = 32
 
@@ -551,10 +569,13 @@ class HipContext:
     """One ygz_hip_ctx: owns HBM frame slots on one GPU and one HIP stream."""
 
     def __init__(self, width=640, height=480, levels=3, max_frames=8, device=0, debug_maps=False, stream=None,
-                 fast_threshold=15, cell_size=10, nms_tie_suppress=0):
+                 fast_threshold=15, cell_size=10, nms_tie_suppress=0, intrinsics=None):
+        """intrinsics: (fx, fy, cx, cy) of the context's camera, or None for the defaults of ygz_hip_default_params"""
         self.lib = load()
         p = Params()
         self.lib.ygz_hip_default_params(C.byref(p))
+        if intrinsics is not None:
+            p.fx, p.fy, p.cx, p.cy = [float(v) for v in intrinsics]
         p.image_width, p.image_height, p.pyramid_levels = width, height, levels
         p.max_frames, p.debug_maps = max_frames, int(debug_maps)
         p.fast_threshold, p.cell_size, p.nms_tie_suppress = fast_threshold, cell_size, nms_tie_suppress
@@ -778,6 +799,36 @@ class HipContext:
 
     def build_pyramid(self, slot_begin=0, n_slots=1, from_bgr=False):
         self._chk(self.lib.ygz_hip_build_pyramid(self._ctx, slot_begin, n_slots, int(from_bgr)), "build_pyramid")
+
+    # ---- lens undistortion
+    def default_undistort_params(self):
+        p = UndistortParams()
+        undistort_argtypes(self.lib)
+        self._chk(self.lib.ygz_hip_default_undistort_params(self._ctx, C.byref(p)), "default_undistort_params")
+        return p
+
+    def set_undistortion(self, drop=False, **fields):
+        """builds the map from the defaults (the context's camera, no distortion, border 0) with the given fields of ygz_undistort_params
+        replaced; drop=True removes it"""
+        undistort_argtypes(self.lib)
+        if drop:
+            self._chk(self.lib.ygz_hip_set_undistortion(self._ctx, None), "set_undistortion")
+            return None
+        p = self.default_undistort_params()
+        for k, v in fields.items():
+            setattr(p, k, v)
+        self._chk(self.lib.ygz_hip_set_undistortion(self._ctx, C.byref(p)), "set_undistortion")
+        return p
+
+    def undistort_map(self):
+        """(qx, qy) [h, w] int32: source positions in 1/32 pixel, UNDISTORT_OUTSIDE in both where the picture has nothing"""
+        undistort_argtypes(self.lib)
+        qx, qy = np.empty((self.height, self.width), np.int32), np.empty((self.height, self.width), np.int32)
+        self._chk(self.lib.ygz_hip_undistort_map(self._ctx, _p(qx, C.c_int32), _p(qy, C.c_int32)), "undistort_map")
+        return qx, qy
+
+    def build_pyramid_undistorted(self, slot_begin=0, n_slots=1, from_bgr=False):
+        self._chk(self.lib.ygz_hip_build_pyramid_undistorted(self._ctx, slot_begin, n_slots, int(from_bgr)), "build_pyramid_undistorted")
 
     def level_size(self, level):
         w, h = C.c_int(0), C.c_int(0)

@@ -297,6 +297,7 @@ void ygz_hip_destroy(ygz_hip_ctx *ctx)
     ygz_hip_ba_free_all(ctx);
     ygz_hip_vocab_free(ctx);
     ygz_kf_store_free(ctx);
+    ygz_undistort_free(ctx);
     if (ctx->stage) (void)hipHostFree(ctx->stage);
     if (ctx->depth_img) (void)hipFree(ctx->depth_img);
     if (ctx->ev_xctx) (void)hipEventDestroy(ctx->ev_xctx);
@@ -494,7 +495,7 @@ static const char *const k_kernel_names[KID_COUNT] = {
     "k_bgr2gray", "k_pyr_down", "k_fast_select", "k_compact", "k_describe", "k_hamming_nn", "k_match_finalize", "k_track_load",
     "k_find_direct_projection", "k_align2d", "k_sparse_align", "k_scharr", "k_klt", "k_klt_pad", "k_ba_pose_prep", "k_ba_points", "k_ba_final",
     "k_ba_chi2", "k_pose_only_ba", "k_ba_lm", "k_bow_transform", "k_bow_match", "k_depth_from_triangulation", "k_lmap_match", "k_lmap_aux",
-    "k_match_postfilter", "k_track_aux", "k_depth_filter", "k_window" };
+    "k_match_postfilter", "k_track_aux", "k_depth_filter", "k_window", "k_undistort" };
 
 int ygz_hip_probe_begin(ygz_hip_ctx *ctx, const char *kernel_name, int max_launches)
 {
@@ -599,11 +600,13 @@ static int klt_flip_sets(ygz_hip_ctx *ctx)
     return YGZ_OK;
 }
 
-int ygz_hip_build_pyramid(ygz_hip_ctx *ctx, int slot_begin, int n_slots, int from_bgr)
+// the one body of ygz_hip_build_pyramid and ygz_hip_build_pyramid_undistorted (undistort: level 0 is first remapped through the map)
+static int build_pyramid_body(ygz_hip_ctx *ctx, int slot_begin, int n_slots, int from_bgr, bool undistort)
 {
     YgzDeviceGuard dg_(ctx, YGZ_HEAD_CALL);
     if (!ctx || slot_begin < 0 || n_slots < 1 || slot_begin + n_slots > ctx->prm.max_frames) return YGZ_E_INVALID;
     if (from_bgr && !ctx->bgr) return YGZ_E_STATE;
+    if (undistort && (!ctx->undist_qx || !ctx->undist_qy)) return YGZ_E_STATE;
     // LK is still at the tail of the main stream and this call rebuilds every slot its pair table names: the images go to the other set, and
     // this call and the rest of the head run beside that launch (it got its pointers by value).  A partial rebuild, or no trailing LK: as before,
     // on the main stream (behind LK) into the current set.
@@ -618,11 +621,25 @@ int ygz_hip_build_pyramid(ygz_hip_ctx *ctx, int slot_begin, int n_slots, int fro
         YGZ_HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_prep, 0));
         if (!ctx->head_aside) ctx->klt_prep_pending = false;   // (aside: the main stream has not waited)
     }
-    int rc = ygz_launch_gray_pyramid(ctx, slot_begin, n_slots, from_bgr, ctx->n_levels_alloc);
+    // the flip, the join and the wait above happen once; the remap, the pyramid and the framed copies follow on this one stream in that order
+    // (level 0 then holds the undistorted gray, so the pyramid is built as from a gray upload and k_klt_frame writes the framed level 0)
+    int rc = undistort ? ygz_launch_undistort(ctx, slot_begin, n_slots, from_bgr) : YGZ_OK;
+    if (rc != YGZ_OK) return rc;
+    rc = ygz_launch_gray_pyramid(ctx, slot_begin, n_slots, undistort ? 0 : from_bgr, ctx->n_levels_alloc);
     if (rc != YGZ_OK) return rc;
     for (int s = slot_begin; s < slot_begin + n_slots; ++s) ctx->pyr_valid[s] = 1;
     ctx->klt_prep_valid = false;
     return YGZ_OK;
+}
+
+int ygz_hip_build_pyramid(ygz_hip_ctx *ctx, int slot_begin, int n_slots, int from_bgr)
+{
+    return build_pyramid_body(ctx, slot_begin, n_slots, from_bgr, false);
+}
+
+int ygz_hip_build_pyramid_undistorted(ygz_hip_ctx *ctx, int slot_begin, int n_slots, int from_bgr)
+{
+    return build_pyramid_body(ctx, slot_begin, n_slots, from_bgr, true);
 }
 
 int ygz_hip_download_level(ygz_hip_ctx *ctx, int slot, int level, uint8_t *dst)

@@ -162,6 +162,11 @@ struct ygz_hip_ctx {
     // their pace when a VALU-bound kernel of another stream shares their SIMDs (bit 0: sparse alignment, bit 1: direct projection,
     // bit 2: BA linearisation, bit 3: LM / ceres / pose-only loops); YGZ_WAVE_PRIO=<mask> overrides
     int  wave_prio_mask = 0;
+    // lens undistortion (undistort.hip): the map of the context's size, [h][w] source positions in 1/32 pixel, while a map is set; the plane the
+    // raw gray uploads go to while level 0 is rewritten (grown on demand)
+    int32_t *undist_qx = nullptr, *undist_qy = nullptr;
+    ygz_undistort_params undist_prm = {};
+    uint8_t *undist_plane = nullptr; size_t undist_plane_bytes = 0;
 };
 
 #define YGZ_HIPCHK(ctx, call)                                            \
@@ -207,7 +212,7 @@ struct YgzDeviceGuard {
 // kernel ids for the probe
 enum { KID_BGR2GRAY = 0, KID_PYR_DOWN, KID_FAST_SELECT, KID_COMPACT, KID_DESCRIBE, KID_HAMMING_NN, KID_MATCH_FINALIZE,
        KID_TRACK_LOAD, KID_FDP, KID_ALIGN2D, KID_SPARSE_ALIGN, KID_SCHARR, KID_KLT, KID_KLT_PAD, KID_BA_POSE_PREP, KID_BA_POINTS,
-       KID_BA_POSES, KID_BA_CHI2, KID_POSE_ONLY, KID_BA_LM, KID_BOW_TRANSFORM, KID_BOW_MATCH, KID_DEPTH_TRI, KID_LMAP_MATCH, KID_LMAP_AUX, KID_MATCH_POSTFILTER, KID_TRACK_AUX, KID_DEPTH_FILTER, KID_WINDOW, KID_COUNT };
+       KID_BA_POSES, KID_BA_CHI2, KID_POSE_ONLY, KID_BA_LM, KID_BOW_TRANSFORM, KID_BOW_MATCH, KID_DEPTH_TRI, KID_LMAP_MATCH, KID_LMAP_AUX, KID_MATCH_POSTFILTER, KID_TRACK_AUX, KID_DEPTH_FILTER, KID_WINDOW, KID_UNDISTORT, KID_COUNT };
 
 #define YGZ_LAUNCH(ctx, kid, kern, grid, block, ...)                                                         \
     do { const bool pr_ = (ctx)->probe_id == (kid) && (ctx)->probe_used + 2 <= (int)(ctx)->probe_ev.size();    \
@@ -296,6 +301,8 @@ int ygz_ensure_levels(ygz_hip_ctx *ctx, int n_levels);      // allocates image l
 
 // launchers implemented in the kernel translation units
 int ygz_launch_gray_pyramid(ygz_hip_ctx *ctx, int slot_begin, int n_slots, int from_bgr, int up_to_level);
+int ygz_launch_undistort(ygz_hip_ctx *ctx, int slot_begin, int n_slots, int from_bgr);      // undistort.hip: level 0 = the undistorted gray of the uploads
+void ygz_undistort_free(ygz_hip_ctx *ctx);
 int ygz_launch_detect(ygz_hip_ctx *ctx, int slot_begin, int n_slots);
 int ygz_launch_describe(ygz_hip_ctx *ctx, int slot_begin, int n_slots);
 int ygz_track_ensure(ygz_hip_ctx *ctx);                      // allocates the resident tracking state

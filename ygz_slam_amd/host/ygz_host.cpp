@@ -80,6 +80,7 @@ struct Runtime::Impl {
     unsigned long long clock = 0;
     std::map<const uint8_t *, std::pair<Frame *, int>> level_of;     // host level data -> (frame, level)
     FdpMemo fdp;
+    bool undist_set = false; float undist_cam[8] = {0};              // the camera the context's undistortion map was built for (k1 k2 p1 p2 fx fy cx cy)
 };
 Runtime &Runtime::Get() { static Runtime r; return r; }
 Runtime::Runtime() : p_(new Impl) {}
@@ -131,6 +132,24 @@ bool Runtime::FindLevel(const uint8_t *data, Frame **f, int *level)
     *f = it->second.first; *level = it->second.second;
     return true;
 }
+bool Runtime::UploadColor(int slot, const cv::Mat &image)
+{
+    ygz_hip_ctx *c = ctx();
+    const int bgr = image.channels() == 3;
+    if (!check(bgr ? ygz_hip_upload_bgr(c, slot, image.data, (int)image.step) : ygz_hip_upload_gray(c, slot, image.data, (int)image.step), "upload")) return false;
+    const PinholeCamera *set = Frame::GetCamera();
+    const PinholeCamera cam = set ? *set : PinholeCamera();
+    if (!cam.HasDistortion()) return check(ygz_hip_build_pyramid(c, slot, 1, bgr), "build_pyramid");
+    const float now[8] = { cam.k1(), cam.k2(), cam.p1(), cam.p2(), cam.fx(), cam.fy(), cam.cx(), cam.cy() };
+    if (!p_->undist_set || !std::equal(now, now + 8, p_->undist_cam)) {          // once per camera
+        ygz_undistort_params u;
+        if (!check(ygz_hip_default_undistort_params(c, &u), "default_undistort_params")) return false;
+        u.k1 = now[0]; u.k2 = now[1]; u.p1 = now[2]; u.p2 = now[3]; u.fx = now[4]; u.fy = now[5]; u.cx = now[6]; u.cy = now[7];
+        if (!check(ygz_hip_set_undistortion(c, &u), "set_undistortion")) return false;
+        std::copy(now, now + 8, p_->undist_cam); p_->undist_set = true;
+    }
+    return check(ygz_hip_build_pyramid_undistorted(c, slot, 1, bgr), "build_pyramid_undistorted");
+}
 // HBM slot of a frame; uploads (again) when the frame was evicted.  gray_only: level 0 is taken from _pyramid[0].
 int Runtime::Resident(Frame *f)
 {
@@ -146,10 +165,8 @@ int Runtime::Resident(Frame *f)
     p_->owner[slot] = f; p_->stamp[slot] = ++p_->clock; f->_hip_slot = slot;
     bool up = true;
     if (!f->_pyramid.empty() && !f->_color.empty()) {                 // an initialised frame that lost its slot: the image goes up again (Frame.cpp:22-40 on the GPU)
-        const int bgr = f->_color.channels() == 3;
-        up = check(bgr ? ygz_hip_upload_bgr(c, slot, f->_color.data, (int)f->_color.step) : ygz_hip_upload_gray(c, slot, f->_color.data, (int)f->_color.step), "upload")
-             && check(ygz_hip_build_pyramid(c, slot, 1, bgr), "build_pyramid");
-    } else if (!f->_pyramid.empty() && f->_pyramid.fetched(0)) {      // _color was released by the caller: level 0 of the host mirror, if somebody fetched it
+        up = UploadColor(slot, f->_color);
+    } else if (!f->_pyramid.empty() && f->_pyramid.fetched(0)) {      // _color was released by the caller: level 0 of the host mirror, if somebody fetched it (already undistorted: never remapped again)
         up = check(ygz_hip_upload_gray(c, slot, f->_pyramid[0].data, (int)f->_pyramid[0].step), "upload_gray") && check(ygz_hip_build_pyramid(c, slot, 1, 0), "build_pyramid");
     } else if (!f->_pyramid.empty()) {
         LOG(ERROR) << "ygz::hip::Runtime: an evicted frame has neither _color nor a fetched level 0 to be uploaded again (raise YGZ_HIP_MAX_FRAMES)" << endl;
@@ -196,9 +213,7 @@ void Frame::InitFrame()
         return;
     }
     const int slot = rt.Resident(this);                 // no pyramid yet: slot only
-    const int bgr = _color.channels() == 3;             // cv::cvtColor(CV_BGR2GRAY) + pyrDown on the GPU (Frame.cpp:27,38)
-    if (!hip::check(bgr ? ygz_hip_upload_bgr(c, slot, _color.data, (int)_color.step) : ygz_hip_upload_gray(c, slot, _color.data, (int)_color.step), "upload")
-        || !hip::check(ygz_hip_build_pyramid(c, slot, 1, bgr), "build_pyramid")) { rt.Release(this); return; }
+    if (slot < 0 || !rt.UploadColor(slot, _color)) { rt.Release(this); return; }      // cv::cvtColor(CV_BGR2GRAY) + pyrDown on the GPU (Frame.cpp:27,38), behind the lens undistortion if the camera has one
     _pyramid.reset(this, (size_t)_option._pyramid_level);      // levels are fetched when somebody indexes them
 }
 
