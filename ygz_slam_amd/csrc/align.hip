@@ -205,12 +205,13 @@ struct FdpArgs {
 // the body shared by both Matcher::FindDirectProjection overloads (Matcher.cpp:356-417) from Pixel2Camera(px_ref, depth) on:
 // GetWarpAffineMatrix, GetBestSearchLevel, WarpAffine into the lane's LDS column, Align2D, rescale.  px_cur in (prediction) /
 // out (refined, level-0 pixels); returns success && InFrame(px_cur, 10).
-static __device__ __forceinline__ bool fdp_core(const FdpArgs &A, int ref_slot, int cur_slot, const double *Tr7, const double *Tc7,
+// (the camera apart from A: k_find_direct_projection hands in a copy that is opaque per batch)
+static __device__ __forceinline__ bool fdp_core_cam(const FdpArgs &A, const Cam &cam, int ref_slot, int cur_slot, const double *Tr7, const double *Tc7,
                                                 const double px_ref[2], double depth, int Lr, uint8_t *pwb, uint32_t *stg, double px_cur[2],
                                                 int *sl_out)
 {
     double pt_ref[3];
-    pixel2camera_d(A.cam, px_ref, depth, pt_ref);
+    pixel2camera_d(cam, px_ref, depth, pt_ref);
     Se3 T_ref, T_cur, Tri, TCR;
     for (int k = 0; k < 4; ++k) { T_ref.q[k] = Tr7[k]; T_cur.q[k] = Tc7[k]; }
     for (int k = 0; k < 3; ++k) { T_ref.t[k] = Tr7[4 + k]; T_cur.t[k] = Tc7[4 + k]; }
@@ -224,11 +225,11 @@ static __device__ __forceinline__ bool fdp_core(const FdpArgs &A, int ref_slot, 
         const double s = (double)(1 << Lr);
         const double pxu[2] = { px_ref[0] + 4.0 * s, px_ref[1] + 0.0 * s };
         const double pxv[2] = { px_ref[0] + 0.0 * s, px_ref[1] + 4.0 * s };
-        pixel2camera_d(A.cam, pxu, pt_ref[2], pdu);
-        pixel2camera_d(A.cam, pxv, pt_ref[2], pdv);
-        se3_act_d(&TCR, pw, q);  camera2pixel_d(A.cam, q, pc);
-        se3_act_d(&TCR, pdu, q); camera2pixel_d(A.cam, q, pu);
-        se3_act_d(&TCR, pdv, q); camera2pixel_d(A.cam, q, pv);
+        pixel2camera_d(cam, pxu, pt_ref[2], pdu);
+        pixel2camera_d(cam, pxv, pt_ref[2], pdv);
+        se3_act_d(&TCR, pw, q);  camera2pixel_d(cam, q, pc);
+        se3_act_d(&TCR, pdu, q); camera2pixel_d(cam, q, pu);
+        se3_act_d(&TCR, pdv, q); camera2pixel_d(cam, q, pv);
         Am[0] = (pu[0] - pc[0]) / 4; Am[2] = (pu[1] - pc[1]) / 4;
         Am[1] = (pv[0] - pc[0]) / 4; Am[3] = (pv[1] - pc[1]) / 4;
     }
@@ -251,27 +252,46 @@ static __device__ __forceinline__ bool fdp_core(const FdpArgs &A, int ref_slot, 
     return inframe && good;
 }
 
+static __device__ __forceinline__ bool fdp_core(const FdpArgs &A, int ref_slot, int cur_slot, const double *Tr7, const double *Tc7,
+                                                const double px_ref[2], double depth, int Lr, uint8_t *pwb, uint32_t *stg, double px_cur[2],
+                                                int *sl_out)
+{ return fdp_core_cam(A, A.cam, ref_slot, cur_slot, Tr7, Tc7, px_ref, depth, Lr, pwb, stg, px_cur, sl_out); }
+
 // Matcher::FindDirectProjection (Feature* overload, Matcher.cpp:385-417)
-__global__ __launch_bounds__(64) void k_find_direct_projection(FdpArgs A)
+// amdgpu_waves_per_eu: two wavefronts per SIMD (256 registers per lane) is the budget the step is tuned to; the 64-lane bound alone allows 512
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_find_direct_projection(FdpArgs A)
 {
     __shared__ uint8_t pwb_all[100 * 64];
     __shared__ uint32_t stg_all[STG_DWORDS * 64];
     int bx, pair;
     ygz_raise_prio(A.prio);
     if (!ygz_xcd_remap(A.n_pairs, bx, pair)) return;
-    const int ii = bx * 64 + threadIdx.x;
-    if (ii >= A.trk_n[pair]) return;
-    const size_t i = (size_t)pair * A.cells + ii;
-    const double depth = A.trk_depth[i];
-    if (depth < 0 || (A.cand && !A.cand[i])) { A.ok[i] = 0; A.search_level[i] = 0; return; }
-    const double px_ref[2] = { A.trk_px[2 * i], A.trk_px[2 * i + 1] };
-    double px_cur[2] = { A.px_cur[2 * i], A.px_cur[2 * i + 1] };
-    int sl;
-    const bool ok = fdp_core(A, A.pair_t[pair], A.pair_q[pair], A.pair_T + 14 * (size_t)pair, A.pair_T + 14 * (size_t)pair + 7,
-                             px_ref, depth, A.trk_level[i], pwb_all + threadIdx.x, stg_all + threadIdx.x, px_cur, &sl);
-    A.px_cur[2 * i] = px_cur[0]; A.px_cur[2 * i + 1] = px_cur[1];
-    A.search_level[i] = sl;
-    A.ok[i] = (uint8_t)ok;
+    // the grid covers 3 / 8 of the cells as candidates of a pair per pass (ygz_launch_fdp); a workgroup takes the batches bx, bx + gridDim.x, ...
+    // of 64 and reuses its two LDS columns (a lane's columns are its own: no barrier between batches).  The pair's scalars are loaded once
+    // per workgroup; they are wave-uniform (the pair comes from the block index) and held in SGPRs.
+    const int n = __builtin_amdgcn_readfirstlane(A.trk_n[pair]);
+    const int32_t ref_slot = __builtin_amdgcn_readfirstlane(A.pair_t[pair]), cur_slot = __builtin_amdgcn_readfirstlane(A.pair_q[pair]);
+    const double *T_ref = A.pair_T + 14 * (size_t)pair;
+    for (int b0 = bx * 64; b0 < n; b0 += 64 * (int)gridDim.x) {          // wave-uniform
+        const int ii = b0 + (int)threadIdx.x;
+        if (ii >= n) continue;                                            // only in the pair's last batch
+        // the pair's poses and the camera opaque per batch: hoisted out of the loop, the relative pose and the camera as doubles (FP64, so
+        // VGPRs) would stay live across fdp_core and push the kernel past its 256 registers
+        uint64_t tp = (uint64_t)T_ref;
+        Cam cam = A.cam;
+        asm volatile("" : "+s"(tp), "+s"(cam.fx), "+s"(cam.fy), "+s"(cam.cx), "+s"(cam.cy));
+        const double *Tr = (const double *)tp;
+        const size_t i = (size_t)pair * A.cells + ii;
+        const double depth = A.trk_depth[i];
+        if (depth < 0 || (A.cand && !A.cand[i])) { A.ok[i] = 0; A.search_level[i] = 0; continue; }
+        const double px_ref[2] = { A.trk_px[2 * i], A.trk_px[2 * i + 1] };
+        double px_cur[2] = { A.px_cur[2 * i], A.px_cur[2 * i + 1] };
+        int sl;
+        const bool ok = fdp_core_cam(A, cam, ref_slot, cur_slot, Tr, Tr + 7, px_ref, depth, A.trk_level[i], pwb_all + threadIdx.x, stg_all + threadIdx.x, px_cur, &sl);
+        A.px_cur[2 * i] = px_cur[0]; A.px_cur[2 * i + 1] = px_cur[1];
+        A.search_level[i] = sl;
+        A.ok[i] = (uint8_t)ok;
+    }
 }
 
 // ---- LocalMapping::FindCandidates + ProjectMapPoints (src/Module/LocalMapping.cpp:47-120) ----
@@ -375,7 +395,10 @@ int ygz_launch_fdp(ygz_hip_ctx *ctx, int n_pairs)
     A.trk_px = ctx->trk_px; A.trk_depth = ctx->trk_depth; A.trk_level = ctx->trk_level;
     A.px_cur = ctx->fdp_px; A.search_level = ctx->fdp_level; A.ok = ctx->fdp_ok; A.cand = ctx->fdp_cand;
     A.prio = (ctx->wave_prio_mask >> 1) & 1;
-    YGZ_LAUNCH(ctx, KID_FDP, k_find_direct_projection, dim3(ygz_div_up(ctx->cells, 64), ygz_round_up8(n_pairs)), dim3(64), A);
+    // as for k_klt3 (klt.hip): sized to the fill, not to the capacity -- 3 / 8 of the cells as candidates per pass (1152 at VGA), later batches by
+    // the same workgroups.  (cells / 8 candidates per pass, three passes on the bench's frames, was measured too: the kernel alone 0.52 instead of
+    // 0.40 ms -- fewer, longer wavefronts leave a longer tail -- and the step 0.05 ms longer.)
+    YGZ_LAUNCH(ctx, KID_FDP, k_find_direct_projection, dim3(ygz_div_up(ygz_div_up(3 * ctx->cells, 8), 64), ygz_round_up8(n_pairs)), dim3(64), A);
     YGZ_HIPCHK(ctx, hipGetLastError());
     return YGZ_OK;
 }

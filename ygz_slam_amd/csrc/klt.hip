@@ -437,31 +437,47 @@ __device__ __forceinline__ double klt_norm2_d(float dx, float dy)
 // (Round 4 also measured fetching only three of a lane's four window rows and taking the fourth from the lane that owns the next row triple
 // through the LDS crossbar -- two ds_bpermute instead of a gather: bit-identical and SLOWER, 2.68 against 2.52 ms per 512 pairs; the dependent
 // crossbar round trip in front of the arithmetic costs more than the gather it saves.)
-__global__ __launch_bounds__(256) void k_klt3(KltArgs A)
+// Launch geometry.  A pair's grid is sized to the detector's typical fill, not to the capacity of the frame (launch_klt_impl); a wavefront walks the
+// triples t, t + T, ... (T = wavefronts per pair) while 3 t < n, so any count up to the capacity is served.  The walk over triples and the walk
+// over levels are ONE loop -- level runs max_level .. 0, then the next triple starts at max_level again -- so that the iteration loop stays at loop
+// depth 2 (tests/test_klt_isa_budget.py reads it there).  KLT3_WPB wavefronts per workgroup share nothing (no LDS, no barrier); 1, 2 and 4 were
+// measured on the tight grid: one-wavefront workgroups refill every freed slot and finish LK in 2.8 instead of 4.1 ms inside the step, but take
+// that time from the BA build and the matcher beside it, and the step gets longer; four is the shortest step.
+// amdgpu_waves_per_eu pins the register budget: four wavefronts per SIMD, 128 registers.
+#define KLT3_WPB 4
+__global__ __launch_bounds__(64 * KLT3_WPB) __attribute__((amdgpu_waves_per_eu(4))) void k_klt3(KltArgs A)
 {
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int lane = threadIdx.x & 63;
     int bx, pair;
     if (!ygz_xcd_remap(A.n_pairs, bx, pair)) return;
     const int n = A.trk_n[pair];
-    const int first = (bx * 4 + wv) * 3;
+    int first = (bx * KLT3_WPB + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6))) * 3;      // wave-uniform, and the compiler is told so: SGPRs
+    const int step = 3 * KLT3_WPB * (int)gridDim.x;          // points per pass of the pair
     if (first >= n) return;                                  // wave-uniform
     const int sub = lane / 21, q = lane - 21 * sub, rt = q / 3, x0 = 7 * (q - 3 * rt), row0 = 3 * rt, seg = sub < 3 ? 21 * sub : 63;
     const int rowb = row0 + KLT_B, colb = x0 + KLT_B;      // the lane's window corner in frame coordinates: (y + rowb) * pw + x + colb
     const KltSegIdx six = klt_seg_idx(lane, q, sub, seg);
-    const int pi = first + sub;
-    const bool live = sub < 3 && pi < n;                     // lane 63 and the lanes of points past the end idle
-    const size_t p = (size_t)pair * A.cells + (live ? pi : first);
-    const size_t ref_slot = (size_t)A.pair_t[pair], cur_slot = (size_t)A.pair_q[pair];
+    const size_t ref_slot = (size_t)A.pair_t[pair], cur_slot = (size_t)A.pair_q[pair];    // per pair: loaded once per wavefront, not per pass
     const int win = KLT_MAXWIN;
     const float half = (float)(win - 1) * 0.5f;
     const float FLT_SCALE = 1.f / (float)(1 << 20);
-    const float ppx = (float)A.trk_px[2 * p], ppy = (float)A.trk_px[2 * p + 1];   // cv::Point2f(fea->_pixel) (Tracker.cpp:85)
-    float outx = A.use_initial_flow ? A.next_pts[2 * p] : ppx;
-    float outy = A.use_initial_flow ? A.next_pts[2 * p + 1] : ppy;
-    bool status = true;
-    float errv = 0.f;
+    // per triple
+    bool live, status;
+    size_t p;
+    float ppx, ppy, outx, outy, errv;
+    auto begin_triple = [&]() {
+        const int pi = first + sub;
+        live = sub < 3 && pi < n;                            // lane 63 and the lanes of points past the end idle
+        p = (size_t)pair * A.cells + (live ? pi : first);
+        ppx = (float)A.trk_px[2 * p]; ppy = (float)A.trk_px[2 * p + 1];   // cv::Point2f(fea->_pixel) (Tracker.cpp:85)
+        outx = A.use_initial_flow ? A.next_pts[2 * p] : ppx;
+        outy = A.use_initial_flow ? A.next_pts[2 * p + 1] : ppy;
+        status = true;
+        errv = 0.f;
+    };
+    begin_triple();
 
-    for (int level = A.max_level; level >= 0; --level) {
+    for (int level = A.max_level; ; ) {
         const int w = A.w[level], h = A.h[level];
         const int pw = KLT_PW(w);
         const size_t psz = (size_t)pw * (h + 2 * KLT_B);
@@ -608,10 +624,15 @@ __global__ __launch_bounds__(256) void k_klt3(KltArgs A)
             const float tot = klt_seg21_sum(se, six);
             if (want) errv = __fdiv_rn(__fmul_rn(tot, 1.f), (float)(32 * win * win));
         }
-    }
-    if (live && q == 0) {
-        A.next_pts[2 * p] = outx; A.next_pts[2 * p + 1] = outy;
-        A.status[p] = (uint8_t)status; A.err[p] = errv;
+        if (level > 0) { --level; continue; }
+        if (live && q == 0) {
+            A.next_pts[2 * p] = outx; A.next_pts[2 * p + 1] = outy;
+            A.status[p] = (uint8_t)status; A.err[p] = errv;
+        }
+        first += step;                                           // the wavefront's next triple of this pair
+        if (first >= n) break;
+        begin_triple();
+        level = A.max_level;
     }
 }
 
@@ -695,7 +716,11 @@ static int launch_klt_impl(ygz_hip_ctx *ctx, int n_pairs, const ygz_klt_params *
     A.next_pts = ctx->klt_pts; A.status = ctx->klt_status; A.err = ctx->klt_err;
     A.dbg = nullptr;
     // 21 x 21 (the reference's window, Tracker.h:25): three points per wavefront; any other window size: one point per wavefront
-    if (A.win == KLT_MAXWIN) YGZ_LAUNCH(ctx, KID_KLT, k_klt3, dim3(ygz_div_up(ctx->cells, 12), ygz_round_up8(n_pairs)), dim3(256), A);
+    // k_klt3's grid: the host does not know trk_n without a synchronisation, so it stays a function of the cells -- but of the detector's
+    // typical fill, not of the capacity.  cells / 8 triples = 3 / 8 of the cells as points per pass: 1152 at VGA, where frames carry 940-1000
+    // points, so a frame somewhat richer than those still takes one pass (two thirds of a capacity-sized grid only load trk_n and exit); the
+    // wavefronts take later passes themselves, up to the capacity.
+    if (A.win == KLT_MAXWIN) YGZ_LAUNCH(ctx, KID_KLT, k_klt3, dim3(ygz_div_up(ygz_div_up(ctx->cells, 8), KLT3_WPB), ygz_round_up8(n_pairs)), dim3(64 * KLT3_WPB), A);
     else YGZ_LAUNCH(ctx, KID_KLT, k_klt<false>, dim3(ygz_div_up(ctx->cells, KLT_WPB), ygz_round_up8(n_pairs)), dim3(64 * KLT_WPB), A);
     YGZ_HIPCHK(ctx, hipGetLastError());
     return YGZ_OK;
