@@ -11,4 +11,5 @@
 #include "ygz/Algorithm/KeyFrameCulling.h"
 #include "ygz/Algorithm/Relocalizer.h"
 #include "ygz/Algorithm/LoopClosing.h"
+#include "ygz/Algorithm/StereoMatcher.h"
 #endif

@@ -59,7 +59,9 @@ extern "C" {
  * Still 6: keyframe culling added (ygz_cull_params, ygz_hip_default_cull_params, ygz_hip_keyframe_redundancy, ygz_hip_cull_keyframes) -- no
  * existing argument list changed.
  * Still 6: lens undistortion added (ygz_undistort_params, ygz_hip_default_undistort_params, ygz_hip_set_undistortion, ygz_hip_undistort_map,
- * ygz_hip_build_pyramid_undistorted) -- no existing argument list changed. */
+ * ygz_hip_build_pyramid_undistorted) -- no existing argument list changed.
+ * Still 6: stereo input added (ygz_stereo_params, ygz_hip_default_stereo_params, ygz_hip_stereo_depths_slots, ygz_hip_stereo_match,
+ * ygz_hip_stereo_candidates) -- no existing argument list changed. */
 #define YGZ_HIP_ABI_VERSION 6
 
 typedef struct ygz_hip_ctx ygz_hip_ctx;
@@ -381,6 +383,55 @@ int  ygz_hip_get_keypoint_counts(ygz_hip_ctx *ctx, int slot_begin, int n_slots, 
 int  ygz_hip_upload_depth_batch(ygz_hip_ctx *ctx, int slot_begin, int n_slots, const void *depth, int dw, int dh, int kind, double scale,
                                 int wait);
 int  ygz_hip_keypoint_depths_from_image(ygz_hip_ctx *ctx, int slot_begin, int n_slots);
+/* ---- S0: stereo input -- the depth of every left keypoint from a rectified pair (epipolar lines are image rows), both pictures resident as
+ * slots of this context.  The reference is monocular and RGB-D only; Feature::_depth, ygz_hip_set_keypoint_depths[_batch] and
+ * LoopClosing::Options::_fix_scale were waiting for this sensor.  The four steps are those of ORB-SLAM2's Frame::ComputeStereoMatches; the spec is
+ * frozen in tests/stereo_ref.c and DESIGN.md section 19, and every output is bit-identical to it.  Per left keypoint (uL, vL, l), with
+ * fx_d = (double)fx of the context, bf = fx_d * baseline, minD = min_disparity, maxD = max_disparity or fx_d when that is 0:
+ *  1. uL - minD < 0: NO_CANDIDATE.  2. right keypoint j (uR, vR, lr) is a candidate when |lr - l| <= 1, floor(vR - r) <= floor(vL) <= ceil(vR + r)
+ *  with r = 2 * 2^lr, and uL - maxD <= uR <= uL - minD; none: NO_CANDIDATE.  3. the candidate with the smallest 256-bit Hamming distance, a tie to
+ *  the smallest j; distance >= th_dist: DESCRIPTOR.  4. s = 2^l, su = floor(uL / s + 0.5), sv = floor(vL / s + 0.5), sr = floor(uR / s + 0.5).
+ *  5. unless 5 <= su < Wl - 5, 5 <= sv < Hl - 5, sr - 10 >= 0 and sr + 10 < Wl: BORDER.  6. D[inc], inc = -5 .. 5: the sum over the 11 x 11 window
+ *  of |(IL(sv + dy, su + dx) - IL(sv, su)) - (IR(sv + dy, sr + inc + dx) - IR(sv, sr + inc))|; k = the smallest inc of the smallest D.
+ *  7. k = -5 or 5: EDGE.  8. delta = (D[k-1] - D[k+1]) / (2 (D[k-1] + D[k+1] - 2 D[k])), u_right = s * ((sr + k) + delta), disp = uL - u_right.
+ *  9. unless minD <= disp < maxD: DISPARITY; disp <= 0: disp = 0.01, u_right = uL - 0.01.  10. depth = bf / disp, sad = D[k], OK.
+ * Per pair: med = element m / 2 of the ascending sad values of the m OK keypoints; an OK keypoint with 10 sad > 21 med becomes MEDIAN.
+ * Pixels are finite and below 2^31; levels lie inside the pyramid. */
+#define YGZ_STEREO_OK            0
+#define YGZ_STEREO_NO_CANDIDATE  1
+#define YGZ_STEREO_DESCRIPTOR    2
+#define YGZ_STEREO_BORDER        3
+#define YGZ_STEREO_EDGE          4
+#define YGZ_STEREO_DISPARITY     5
+#define YGZ_STEREO_MEDIAN        6
+#define YGZ_STEREO_N_STATUS      7
+typedef struct {
+    double baseline;        /* metres between the two cameras, > 0 (0.1) */
+    double min_disparity;   /* >= 0 (0) */
+    double max_disparity;   /* >= 0; 0: the context's fx (0) */
+    int    th_dist;         /* a best descriptor distance >= th_dist is no match; [0, 256] (75) */
+    int    write_depths;    /* slot form: != 0 also sets the left slot's keypoint depths (1) */
+} ygz_stereo_params;
+void ygz_hip_default_stereo_params(ygz_stereo_params *p);
+/* The resident keypoints (ygz_hip_detect) of n_pairs pairs of slots in one call: one upload of the pair table, two launches, one copy back, one
+ * wait.  Outputs [n_pairs][max_keypoints] (counts [n_pairs][7], one count per status), each may be NULL; entries past a pair's left keypoints are
+ * -1.  right_idx and sad are -1 unless the status is OK or MEDIAN, u_right and depth -1.0 unless it is OK.  With write_depths the left slot's
+ * Feature::_depth = depth and _mappoint != nullptr = (status is OK), as ygz_hip_keypoint_depths_from_image sets them from a depth picture; the right
+ * slot's are untouched.  YGZ_E_INVALID: a null context, params or slot array, n_pairs < 1, a slot out of range, left == right, a left slot named
+ * twice, baseline <= 0, a non-finite or negative parameter, th_dist outside [0, 256]; YGZ_E_STATE: a slot without a pyramid or without keypoints. */
+int  ygz_hip_stereo_depths_slots(ygz_hip_ctx *ctx, int n_pairs, const int32_t *left_slot, const int32_t *right_slot, const ygz_stereo_params *params,
+                                 int32_t *right_idx, double *u_right, double *depth, int32_t *sad, int32_t *status, int32_t *counts);
+/* The same kernels on one pair with the keypoints from host arrays (px [n][2] level-0 pixels, level [n], desc [n][32]) and the pictures of the two
+ * slots; outputs [n_l] (counts [7]), each may be NULL.  Never writes depths.  n_l = 0 and n_r = 0 are legal.  In addition YGZ_E_INVALID: a level
+ * outside the pyramid; YGZ_E_CAPACITY: n_l or n_r above ygz_hip_max_keypoints. */
+int  ygz_hip_stereo_match(ygz_hip_ctx *ctx, int left_slot, int right_slot, const double *px_l, const int32_t *level_l, const uint8_t *desc_l, int n_l,
+                          const double *px_r, const int32_t *level_r, const uint8_t *desc_r, int n_r, const ygz_stereo_params *params,
+                          int32_t *right_idx, double *u_right, double *depth, int32_t *sad, int32_t *status, int32_t *counts);
+/* The stages for tests, array form: best_idx / best_dist [n_l] after step 3 (-1 without a candidate), n_cand [n_l], sads [n_l][11] (-1 where step 6
+ * was not reached); each may be NULL. */
+int  ygz_hip_stereo_candidates(ygz_hip_ctx *ctx, int left_slot, int right_slot, const double *px_l, const int32_t *level_l, const uint8_t *desc_l, int n_l,
+                               const double *px_r, const int32_t *level_r, const uint8_t *desc_r, int n_r, const ygz_stereo_params *params,
+                               int32_t *best_idx, int32_t *best_dist, int32_t *n_cand, int32_t *sads);
 /* Feature::_depth / _mappoint != nullptr of the keypoints of a slot as they stand on the device (either output may be NULL) */
 int  ygz_hip_get_keypoint_depths(ygz_hip_ctx *ctx, int slot, double *depth, uint8_t *has_mappoint, int capacity, int *n);
 /* per pair of the resident pair table 32 doubles, reduced on the device: [0..6] pose after sparse alignment, [7] its n_meas / 16,

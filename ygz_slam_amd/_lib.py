@@ -429,6 +429,21 @@ def undistort_argtypes(lib):
     lib.ygz_hip_build_pyramid_undistorted.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
 
 
+class StereoParams(C.Structure):
+    """ygz_stereo_params (include/ygz_hip.h)"""
+    _fields_ = [("baseline", C.c_double), ("min_disparity", C.c_double), ("max_disparity", C.c_double), ("th_dist", C.c_int), ("write_depths", C.c_int)]
+
+
+def stereo_argtypes(lib):
+    ip, dp, bp, pp = C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.POINTER(StereoParams)
+    lib.ygz_hip_default_stereo_params.argtypes = [pp]
+    lib.ygz_hip_default_stereo_params.restype = None
+    lib.ygz_hip_stereo_depths_slots.argtypes = [C.c_void_p, C.c_int, ip, ip, pp, ip, dp, dp, ip, ip, ip]
+    arrays = [C.c_void_p, C.c_int, C.c_int, dp, ip, bp, C.c_int, dp, ip, bp, C.c_int, pp]
+    lib.ygz_hip_stereo_match.argtypes = arrays + [ip, dp, dp, ip, ip, ip]
+    lib.ygz_hip_stereo_candidates.argtypes = arrays + [ip, ip, ip, ip]
+
+
 # every symbol include/ygz_hip.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
     "ygz_hip_default_params", "ygz_hip_create", "ygz_hip_destroy", "ygz_hip_synchronize", "ygz_hip_join", "ygz_hip_set_overlap", "ygz_hip_error_string",
@@ -461,6 +476,7 @@ ABI_SYMBOLS = [
     "ygz_hip_kfdb_create", "ygz_hip_kfdb_destroy", "ygz_hip_kfdb_add", "ygz_hip_kfdb_erase", "ygz_hip_kfdb_clear", "ygz_hip_kfdb_info", "ygz_hip_kfdb_query",
     "ygz_hip_default_cull_params", "ygz_hip_keyframe_redundancy", "ygz_hip_cull_keyframes",
     "ygz_hip_default_undistort_params", "ygz_hip_set_undistortion", "ygz_hip_undistort_map", "ygz_hip_build_pyramid_undistorted",
+    "ygz_hip_default_stereo_params", "ygz_hip_stereo_depths_slots", "ygz_hip_stereo_match", "ygz_hip_stereo_candidates",
 ]
 INIT_SYMBOLS = ["ygz_hip_default_init_params", "ygz_hip_initialize", "ygz_hip_init_sample_sets", "ygz_hip_init_hypotheses", "ygz_hip_init_reconstruct"]
 INIT_NONE, INIT_H, INIT_F = 0, 1, 2
@@ -490,6 +506,10 @@ CULL_MAX_KEYFRAMES = 4096
 
 UNDISTORT_SYMBOLS = ["ygz_hip_default_undistort_params", "ygz_hip_set_undistortion", "ygz_hip_undistort_map", "ygz_hip_build_pyramid_undistorted"]
 UNDISTORT_OUTSIDE = -2 ** 31
+
+STEREO_SYMBOLS = ["ygz_hip_default_stereo_params", "ygz_hip_stereo_depths_slots", "ygz_hip_stereo_match", "ygz_hip_stereo_candidates"]
+STEREO_OK, STEREO_NO_CANDIDATE, STEREO_DESCRIPTOR, STEREO_BORDER, STEREO_EDGE, STEREO_DISPARITY, STEREO_MEDIAN = range(7)
+STEREO_N_STATUS, STEREO_COLUMNS = 7, 11
 
 SUMMARY_FIELDS = 32
 
@@ -706,6 +726,65 @@ class HipContext:
 
     def keypoint_depths_from_image(self, slot_begin, n_slots):
         self._chk(self.lib.ygz_hip_keypoint_depths_from_image(self._ctx, slot_begin, n_slots), "keypoint_depths_from_image")
+
+    # ---- stereo input
+    def default_stereo_params(self, **fields):
+        """ygz_stereo_params with the library's defaults, then the given fields"""
+        p = StereoParams()
+        stereo_argtypes(self.lib)
+        self.lib.ygz_hip_default_stereo_params(C.byref(p))
+        for k, v in fields.items():
+            getattr(p, k)                   # AttributeError for a field the struct does not have
+            setattr(p, k, v)
+        return p
+
+    def stereo_depths_slots(self, left_slots, right_slots, params=None, **fields):
+        """the resident keypoints of the pairs (left_slots[q], right_slots[q]): dict of right_idx, u_right, depth, sad, status [n_pairs, cells]
+        (-1 past a pair's left keypoints) and counts [n_pairs, 7]; with write_depths (the default) the left slots' keypoint depths are set"""
+        p = params if params is not None else self.default_stereo_params(**fields)
+        ls, rs = np.ascontiguousarray(left_slots, np.int32).reshape(-1), np.ascontiguousarray(right_slots, np.int32).reshape(-1)
+        if len(ls) != len(rs):
+            raise ValueError("left_slots and right_slots differ in length")
+        n, c = len(ls), self.cells
+        o = dict(right_idx=np.empty((n, c), np.int32), u_right=np.empty((n, c)), depth=np.empty((n, c)), sad=np.empty((n, c), np.int32),
+                 status=np.empty((n, c), np.int32), counts=np.empty((n, STEREO_N_STATUS), np.int32))
+        self._chk(self.lib.ygz_hip_stereo_depths_slots(self._ctx, n, _p(ls, C.c_int32), _p(rs, C.c_int32), C.byref(p), _p(o["right_idx"], C.c_int32),
+                                                       _p(o["u_right"], C.c_double), _p(o["depth"], C.c_double), _p(o["sad"], C.c_int32),
+                                                       _p(o["status"], C.c_int32), _p(o["counts"], C.c_int32)), "stereo_depths_slots")
+        return o
+
+    def _stereo_arrays(self, left_slot, right_slot, kl, kr, p):
+        a = [np.ascontiguousarray(kl["px"], np.float64).reshape(-1, 2), np.ascontiguousarray(kl["level"], np.int32).reshape(-1),
+             np.ascontiguousarray(kl["desc"], np.uint8).reshape(-1, 32)]
+        b = [np.ascontiguousarray(kr["px"], np.float64).reshape(-1, 2), np.ascontiguousarray(kr["level"], np.int32).reshape(-1),
+             np.ascontiguousarray(kr["desc"], np.uint8).reshape(-1, 32)]
+        if not (len(a[0]) == len(a[1]) == len(a[2]) and len(b[0]) == len(b[1]) == len(b[2])):
+            raise ValueError("px, level and desc of a keypoint list differ in length")
+        f = lambda v, t: _p(v, t) if len(v) else None
+        args = [self._ctx, int(left_slot), int(right_slot), f(a[0], C.c_double), f(a[1], C.c_int32), f(a[2], C.c_uint8), len(a[1]),
+                f(b[0], C.c_double), f(b[1], C.c_int32), f(b[2], C.c_uint8), len(b[1]), C.byref(p)]
+        return args, (a, b), len(a[1])
+
+    def stereo_match(self, left_slot, right_slot, kl, kr, params=None, **fields):
+        """the array form: keypoint lists kl, kr = dict(px [n, 2], level [n], desc [n, 32]) against the pictures of the two slots; dict of
+        right_idx, u_right, depth, sad, status [nl] and counts [7].  Never writes depths."""
+        p = params if params is not None else self.default_stereo_params(**fields)
+        args, keep, n = self._stereo_arrays(left_slot, right_slot, kl, kr, p)
+        o = dict(right_idx=np.empty(n, np.int32), u_right=np.empty(n), depth=np.empty(n), sad=np.empty(n, np.int32), status=np.empty(n, np.int32),
+                 counts=np.empty(STEREO_N_STATUS, np.int32))
+        self._chk(self.lib.ygz_hip_stereo_match(*args, _p(o["right_idx"], C.c_int32), _p(o["u_right"], C.c_double), _p(o["depth"], C.c_double),
+                                                _p(o["sad"], C.c_int32), _p(o["status"], C.c_int32), _p(o["counts"], C.c_int32)), "stereo_match")
+        return o
+
+    def stereo_candidates(self, left_slot, right_slot, kl, kr, params=None, **fields):
+        """the stages of the array form: best_idx, best_dist [nl] after the descriptor search (-1 without a candidate), n_cand [nl],
+        sads [nl, 11] (-1 where the SAD search was not reached)"""
+        p = params if params is not None else self.default_stereo_params(**fields)
+        args, keep, n = self._stereo_arrays(left_slot, right_slot, kl, kr, p)
+        o = dict(best_idx=np.empty(n, np.int32), best_dist=np.empty(n, np.int32), n_cand=np.empty(n, np.int32), sads=np.empty((n, STEREO_COLUMNS), np.int32))
+        self._chk(self.lib.ygz_hip_stereo_candidates(*args, _p(o["best_idx"], C.c_int32), _p(o["best_dist"], C.c_int32), _p(o["n_cand"], C.c_int32),
+                                                     _p(o["sads"], C.c_int32)), "stereo_candidates")
+        return o
 
     # ---- keyframe store / device-built BA windows (configs[4])
     def stream_wait(self, signaler):

@@ -707,6 +707,7 @@ int ygz_hip_detect(ygz_hip_ctx *ctx, int slot_begin, int n_slots, const uint8_t 
         YGZ_HIPCHK(ctx, hipMemcpyAsync(ctx->occupied + (size_t)slot_begin * Cn, st, (size_t)n_slots * Cn, hipMemcpyHostToDevice, ctx->stream));
     }
     { const int rc = detect_clear(ctx, slot_begin, n_slots, occupied == nullptr); if (rc != YGZ_OK) return rc; }
+    for (int s = slot_begin; s < slot_begin + n_slots; ++s) ctx->kp_valid[s] = 1;
     return ygz_launch_detect(ctx, slot_begin, n_slots);
 }
 
