@@ -12,4 +12,5 @@
 #include "ygz/Algorithm/Relocalizer.h"
 #include "ygz/Algorithm/LoopClosing.h"
 #include "ygz/Algorithm/StereoMatcher.h"
+#include "ygz/Algorithm/PoseOptimizer.h"
 #endif

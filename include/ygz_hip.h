@@ -61,7 +61,9 @@ extern "C" {
  * Still 6: lens undistortion added (ygz_undistort_params, ygz_hip_default_undistort_params, ygz_hip_set_undistortion, ygz_hip_undistort_map,
  * ygz_hip_build_pyramid_undistorted) -- no existing argument list changed.
  * Still 6: stereo input added (ygz_stereo_params, ygz_hip_default_stereo_params, ygz_hip_stereo_depths_slots, ygz_hip_stereo_match,
- * ygz_hip_stereo_candidates) -- no existing argument list changed. */
+ * ygz_hip_stereo_candidates) -- no existing argument list changed.
+ * Still 6: stereo pose optimisation added (ygz_pose_opt_params, ygz_hip_default_pose_opt_params, ygz_hip_optimize_pose_stereo) -- no existing
+ * argument list changed. */
 #define YGZ_HIP_ABI_VERSION 6
 
 typedef struct ygz_hip_ctx ygz_hip_ctx;
@@ -632,6 +634,53 @@ int  ygz_hip_ba_solve_ceres_resident(ygz_hip_ctx *ctx, int window_begin, int n_w
 int  ygz_hip_optimize_pose_only(ygz_hip_ctx *ctx, int n_frames, const int32_t *frame_off, const double *px,
                                 const double *pw, double *poses_io, uint8_t *bad, double *depth, int32_t *inliers,
                                 int32_t *rounds);
+
+/* ---- P0: stereo pose optimisation -- ORB-SLAM2's Optimizer::PoseOptimization for a batch of frames, the per-frame routine of every stereo and
+ * RGB-D system of that family (ygz_hip_optimize_pose_only above is the reference's monocular ceres functor and stays as it is).  Frame f owns the
+ * edges frame_off[f] .. frame_off[f+1]-1 (the CSR layout of ygz_hip_optimize_pose_only): pw [n][3] world points, obs [n][3] = (u, v, uR) level-0
+ * pixels, level [n] (inside the context's pyramid), kind [n]: 0 absent (never used, never classified), 1 mono (u, v), 2 stereo (u, v, uR).
+ * poses_io [n_frames][7] = T_cw as qx qy qz qw tx ty tz, in and out.  The spec is frozen in tests/popt_ref.c and DESIGN.md section 20, and every
+ * output is bit-identical to it.  With fx_d .. cy_d the context's float intrinsics as doubles, bf = fx_d * baseline, w = 4^-level, P = R X + t:
+ *   r0 = u - (fx x/z + cx), r1 = v - (fy y/z + cy), stereo r2 = uR - (fx x/z + cx - bf/z), chi2 = w |r|^2; an edge is rejected in an evaluation
+ *   when !(z > 0) or a residual is not finite (it adds nothing and is counted); g2o's Huber kernel on chi2 with delta^2 = chi2_mono / chi2_stereo.
+ * Round k = 0 .. rounds-1: T <- the entry pose; active edges: kind != 0 and not an outlier of the previous classification (round 0: all); the
+ * kernel is on while k < robust_rounds; at most `iterations` Levenberg-Marquardt iterations under g2o's rules (lambda0 = 1e-5 max |diag H|, nu = 2,
+ * at most max_trials trials per iteration, dense Cholesky of H + lambda I, gain ratio (chi - chi_trial) / (d (lambda d + b) + 1e-3), the
+ * min_rel_decrease stop); a trial fails on a bad pivot, a non-finite cost or more rejected edges than the iteration's linearisation had; a round
+ * whose first linearisation has fewer than min_edges accepted edges is FAILED and leaves T at the entry pose.  Then every edge with kind != 0 is
+ * classified at the round's T by a fresh evaluation (rejected, or chi2 above its threshold: outlier); fewer than min_inliers inliers end the call
+ * after this round.  The pose returned is the T of the last round that ran. */
+#define YGZ_POPT_MAX_ROUNDS     8
+#define YGZ_POPT_MAX_STEPS      64         /* the most `iterations` and the most `max_trials` may be: trials whose pivot fails are retried by one
+                                            * lane without a pass in between, so the product bounds how long a frame can hold its workgroup */
+#define YGZ_POPT_FAILED         0          /* the values of YGZ_GBA_*, with their meanings */
+#define YGZ_POPT_CONVERGED      1
+#define YGZ_POPT_MAX_ITERATIONS 2
+#define YGZ_POPT_STALLED        3
+typedef struct {
+    double baseline;          /* metres between the two cameras; no default (0): must be > 0 when a stereo edge exists */
+    double chi2_mono;         /* > 0 (5.991): Huber width and outlier threshold of a mono edge */
+    double chi2_stereo;       /* > 0 (7.815): of a stereo edge */
+    int    rounds;            /* 1 .. 8 (4) */
+    int    iterations;        /* 1 .. 64 (10): LM iterations per round */
+    int    max_trials;        /* 1 .. 64 (10): trials per iteration */
+    int    robust_rounds;     /* the kernel is on in rounds 0 .. robust_rounds-1 (3: ORB-SLAM2 drops it for the last round) */
+    int    min_edges;         /* (3) any value: <= 0 lets a frame without an accepted edge run (its trials fail at the pivot) */
+    int    min_inliers;       /* (10) any value: <= 0 never ends the call early */
+    double min_rel_decrease;  /* (0: off) a round is CONVERGED when an accepted step lowers the cost by no more than this share of it */
+} ygz_pose_opt_params;
+void ygz_hip_default_pose_opt_params(ygz_pose_opt_params *p);
+/* One packed upload, one launch (k_pose_opt: one workgroup per frame), one copy back, one wait.  Outputs, each but poses_io may be NULL:
+ * outlier [n] and chi2 [n] of the last classification (chi2 -1.0 for kind 0, 0.0 for a rejected edge, which is an outlier); inliers, rounds_run
+ * [n_frames]; round_status (YGZ_POPT_*), round_iterations, round_cost_initial, round_cost_final, round_lambda [n_frames][8], unused rounds zero.
+ * All checks run before the device is touched.  YGZ_E_INVALID: a null context, params or required array; n_frames < 0; frame_off[0] != 0 or a
+ * non-monotone frame_off; a kind outside {0, 1, 2}; a level outside the context's pyramid; a non-finite parameter; baseline <= 0 with a stereo edge
+ * present; a non-positive chi2_*; rounds outside 1 .. 8; iterations or max_trials outside 1 .. 64.  n_frames = 0 and frames without edges are legal: such a
+ * frame is FAILED in round 0 and its pose is untouched. */
+int  ygz_hip_optimize_pose_stereo(ygz_hip_ctx *ctx, int n_frames, const int32_t *frame_off, const double *pw, const double *obs, const int32_t *level,
+                                  const uint8_t *kind, const ygz_pose_opt_params *params, double *poses_io, uint8_t *outlier, double *chi2,
+                                  int32_t *inliers, int32_t *rounds_run, int32_t *round_status, int32_t *round_iterations,
+                                  double *round_cost_initial, double *round_cost_final, double *round_lambda);
 
 /* ---- cvutils::DepthFromTriangulation (include/ygz/Algorithm/CVUtils.h:18-38) for n ray pairs: the step after
  *      SearchForTriangulation in LocalMapping::CreateNewMapPoints (src/Module/LocalMapping.cpp:430-452).  f_ref / f_cur [n][3]

@@ -444,6 +444,19 @@ def stereo_argtypes(lib):
     lib.ygz_hip_stereo_candidates.argtypes = arrays + [ip, ip, ip, ip]
 
 
+class PoseOptParams(C.Structure):
+    """ygz_pose_opt_params (include/ygz_hip.h)"""
+    _fields_ = [("baseline", C.c_double), ("chi2_mono", C.c_double), ("chi2_stereo", C.c_double), ("rounds", C.c_int), ("iterations", C.c_int),
+                ("max_trials", C.c_int), ("robust_rounds", C.c_int), ("min_edges", C.c_int), ("min_inliers", C.c_int), ("min_rel_decrease", C.c_double)]
+
+
+def popt_argtypes(lib):
+    ip, dp, bp, pp = C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.POINTER(PoseOptParams)
+    lib.ygz_hip_default_pose_opt_params.argtypes = [pp]
+    lib.ygz_hip_default_pose_opt_params.restype = None
+    lib.ygz_hip_optimize_pose_stereo.argtypes = [C.c_void_p, C.c_int, ip, dp, dp, ip, bp, pp, dp, bp, dp, ip, ip, ip, ip, dp, dp, dp]
+
+
 # every symbol include/ygz_hip.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
     "ygz_hip_default_params", "ygz_hip_create", "ygz_hip_destroy", "ygz_hip_synchronize", "ygz_hip_join", "ygz_hip_set_overlap", "ygz_hip_error_string",
@@ -477,6 +490,7 @@ ABI_SYMBOLS = [
     "ygz_hip_default_cull_params", "ygz_hip_keyframe_redundancy", "ygz_hip_cull_keyframes",
     "ygz_hip_default_undistort_params", "ygz_hip_set_undistortion", "ygz_hip_undistort_map", "ygz_hip_build_pyramid_undistorted",
     "ygz_hip_default_stereo_params", "ygz_hip_stereo_depths_slots", "ygz_hip_stereo_match", "ygz_hip_stereo_candidates",
+    "ygz_hip_default_pose_opt_params", "ygz_hip_optimize_pose_stereo",
 ]
 INIT_SYMBOLS = ["ygz_hip_default_init_params", "ygz_hip_initialize", "ygz_hip_init_sample_sets", "ygz_hip_init_hypotheses", "ygz_hip_init_reconstruct"]
 INIT_NONE, INIT_H, INIT_F = 0, 1, 2
@@ -510,6 +524,10 @@ UNDISTORT_OUTSIDE = -2 ** 31
 STEREO_SYMBOLS = ["ygz_hip_default_stereo_params", "ygz_hip_stereo_depths_slots", "ygz_hip_stereo_match", "ygz_hip_stereo_candidates"]
 STEREO_OK, STEREO_NO_CANDIDATE, STEREO_DESCRIPTOR, STEREO_BORDER, STEREO_EDGE, STEREO_DISPARITY, STEREO_MEDIAN = range(7)
 STEREO_N_STATUS, STEREO_COLUMNS = 7, 11
+
+POPT_SYMBOLS = ["ygz_hip_default_pose_opt_params", "ygz_hip_optimize_pose_stereo"]
+POPT_FAILED, POPT_CONVERGED, POPT_MAX_ITERATIONS, POPT_STALLED = range(4)
+POPT_MAX_ROUNDS, POPT_MAX_STEPS = 8, 64
 
 SUMMARY_FIELDS = 32
 
@@ -784,6 +802,46 @@ class HipContext:
         o = dict(best_idx=np.empty(n, np.int32), best_dist=np.empty(n, np.int32), n_cand=np.empty(n, np.int32), sads=np.empty((n, STEREO_COLUMNS), np.int32))
         self._chk(self.lib.ygz_hip_stereo_candidates(*args, _p(o["best_idx"], C.c_int32), _p(o["best_dist"], C.c_int32), _p(o["n_cand"], C.c_int32),
                                                      _p(o["sads"], C.c_int32)), "stereo_candidates")
+        return o
+
+    # ---- stereo pose optimisation
+    def default_pose_opt_params(self, **fields):
+        """ygz_pose_opt_params with the library's defaults, then the given fields"""
+        p = PoseOptParams()
+        popt_argtypes(self.lib)
+        self.lib.ygz_hip_default_pose_opt_params(C.byref(p))
+        for k, v in fields.items():
+            getattr(p, k)                   # AttributeError for a field the struct does not have
+            setattr(p, k, v)
+        return p
+
+    def optimize_pose_stereo(self, frame_off, pw, obs, level, kind, poses, params=None, outputs=True, **fields):
+        """ORB-SLAM2's PoseOptimization for the frames of the CSR list frame_off: pw, obs [n, 3], level, kind [n] (0 absent, 1 mono, 2 stereo),
+        poses [n_frames, 7] (qx qy qz qw tx ty tz).  Dict of pose [n_frames, 7], outlier, chi2 [n], inliers, rounds_run [n_frames] and status,
+        lm_iterations, cost_initial, cost_final, lambda [n_frames, 8]; outputs=False passes NULL for everything but the poses."""
+        p = params if params is not None else self.default_pose_opt_params(**fields)
+        popt_argtypes(self.lib)
+        off = np.ascontiguousarray(frame_off, np.int32).reshape(-1)
+        nf = len(off) - 1
+        pw, obs = np.ascontiguousarray(pw, np.float64).reshape(-1, 3), np.ascontiguousarray(obs, np.float64).reshape(-1, 3)
+        level, kind = np.ascontiguousarray(level, np.int32).reshape(-1), np.ascontiguousarray(kind, np.uint8).reshape(-1)
+        n = len(level)
+        if not (len(pw) == len(obs) == len(kind) == n):
+            raise ValueError("pw, obs, level and kind differ in length")
+        o = dict(pose=np.array(poses, np.float64).reshape(nf, 7))
+        R = POPT_MAX_ROUNDS
+        if outputs:
+            o.update(outlier=np.zeros(n, np.uint8), chi2=np.zeros(n), inliers=np.zeros(nf, np.int32), rounds_run=np.zeros(nf, np.int32),
+                     status=np.zeros((nf, R), np.int32), lm_iterations=np.zeros((nf, R), np.int32), cost_initial=np.zeros((nf, R)),
+                     cost_final=np.zeros((nf, R)))
+            o["lambda"] = np.zeros((nf, R))
+        f = lambda key, t: _p(o[key], t) if outputs and o[key].size else None
+        g = lambda v, t: _p(v, t) if len(v) else None
+        self._chk(self.lib.ygz_hip_optimize_pose_stereo(
+            self._ctx, nf, _p(off, C.c_int32), g(pw, C.c_double), g(obs, C.c_double), g(level, C.c_int32), g(kind, C.c_uint8), C.byref(p),
+            _p(o["pose"], C.c_double) if nf else None, f("outlier", C.c_uint8), f("chi2", C.c_double), f("inliers", C.c_int32),
+            f("rounds_run", C.c_int32), f("status", C.c_int32), f("lm_iterations", C.c_int32), f("cost_initial", C.c_double),
+            f("cost_final", C.c_double), f("lambda", C.c_double)), "optimize_pose_stereo")
         return o
 
     # ---- keyframe store / device-built BA windows (configs[4])

@@ -1,0 +1,98 @@
+// ygz::PoseOptimizer (include/ygz/Algorithm/PoseOptimizer.h) over ygz_hip_optimize_pose_stereo: the features with a good map point of all frames
+// as the ABI's CSR arrays, one device call (ygz_slam_amd/csrc/popt.hip), then the effects of ba::OptimizeCurrentPoseOnly on the frames.  Error
+// conventions of the other surfaces: a failed call logs and returns 0, only a missing device throws.
+#include "ygz/Algorithm/PoseOptimizer.h"
+#include "ygz/hip/Runtime.h"
+#include "ygz_hip.h"
+
+namespace ygz {
+
+int PoseOptimizer::URightFromDepth(const Frame *frame, double baseline, std::vector<double> *u_right)
+{
+    if (!frame || !u_right || !Frame::_camera) return 0;
+    const double bf = (double)Frame::_camera->fx() * baseline;
+    u_right->assign(frame->_features.size(), -1.0);
+    int set = 0;
+    for (size_t i = 0; i < frame->_features.size(); ++i) {
+        const Feature *ft = frame->_features[i];
+        if (!ft || !(ft->_depth > 0)) continue;
+        (*u_right)[i] = ft->_pixel[0] - bf / ft->_depth;
+        if ((*u_right)[i] >= 0) ++set;
+    }
+    return set;
+}
+
+void PoseOptimizer::OptimizeBatch(const std::vector<Frame *> &frames, const std::vector<const std::vector<double> *> &u_right)
+{
+    const size_t nf = frames.size();
+    _outliers.assign(nf, std::vector<uint8_t>());
+    _rounds.assign(nf, std::vector<Round>());
+    _inliers.assign(nf, 0);
+    if (nf == 0) return;
+    if (!Frame::_camera) { LOG(ERROR) << "PoseOptimizer::OptimizeBatch: Frame::SetCamera has not been called" << endl; return; }
+    if (!u_right.empty() && u_right.size() != nf) { LOG(ERROR) << "PoseOptimizer::OptimizeBatch: one u_right per frame is needed" << endl; return; }
+    std::vector<int32_t> off(1, 0), level;
+    std::vector<double> pw, obs, poses(7 * nf);
+    std::vector<uint8_t> kind;
+    std::vector<Feature *> edge;                                   // the feature of every edge
+    for (size_t fi = 0; fi < nf; ++fi) {
+        Frame *f = frames[fi];
+        if (!f) { LOG(ERROR) << "PoseOptimizer::OptimizeBatch: a null frame" << endl; return; }
+        const std::vector<double> *ur = u_right.empty() ? nullptr : u_right[fi];
+        if (ur && ur->size() != f->_features.size()) { LOG(ERROR) << "PoseOptimizer::OptimizeBatch: u_right does not match the features" << endl; return; }
+        _outliers[fi].assign(f->_features.size(), 0);
+        for (size_t i = 0; i < f->_features.size(); ++i) {
+            Feature *fea = f->_features[i];
+            if (!fea || !fea->_mappoint || fea->_mappoint->_bad) continue;
+            const bool stereo = ur && (*ur)[i] >= 0;
+            for (int c = 0; c < 3; ++c) pw.push_back(fea->_mappoint->_pos_world[c]);
+            obs.push_back(fea->_pixel[0]); obs.push_back(fea->_pixel[1]); obs.push_back(stereo ? (*ur)[i] : -1.0);
+            level.push_back(fea->_level);
+            kind.push_back(stereo ? 2 : 1);
+            edge.push_back(fea);
+        }
+        off.push_back((int32_t)edge.size());
+        f->_TCW.to7(&poses[7 * fi]);
+    }
+    ygz_pose_opt_params p;
+    ygz_hip_default_pose_opt_params(&p);
+    p.baseline = _options._baseline; p.chi2_mono = _options._chi2_mono; p.chi2_stereo = _options._chi2_stereo;
+    p.rounds = _options._rounds; p.iterations = _options._iterations; p.max_trials = _options._max_trials;
+    p.robust_rounds = _options._robust_rounds; p.min_edges = _options._min_edges; p.min_inliers = _options._min_inliers;
+    p.min_rel_decrease = _options._min_rel_decrease;
+    const size_t n = edge.size();
+    std::vector<uint8_t> outlier(n + 1);
+    std::vector<int32_t> inliers(nf), run(nf), status(8 * nf), iters(8 * nf);
+    std::vector<double> ci(8 * nf), cf(8 * nf), lam(8 * nf);
+    if (!hip::check(ygz_hip_optimize_pose_stereo(hip::Runtime::Get().ctx(), (int)nf, off.data(), pw.data(), obs.data(), level.data(), kind.data(), &p,
+                                                 poses.data(), outlier.data(), nullptr, inliers.data(), run.data(), status.data(), iters.data(),
+                                                 ci.data(), cf.data(), lam.data()), "optimize_pose_stereo")) return;
+    for (size_t fi = 0; fi < nf; ++fi) {
+        Frame *f = frames[fi];
+        f->_TCW = SE3::from7(&poses[7 * fi]);
+        _inliers[fi] = inliers[fi];
+        for (int k = 0; k < run[fi]; ++k)
+            _rounds[fi].push_back(Round{ status[8 * fi + k], iters[8 * fi + k], ci[8 * fi + k], cf[8 * fi + k], lam[8 * fi + k] });
+        size_t g = (size_t)off[fi];
+        for (size_t i = 0; i < f->_features.size(); ++i) {
+            Feature *fea = f->_features[i];
+            if (g >= (size_t)off[fi + 1] || edge[g] != fea) continue;
+            _outliers[fi][i] = outlier[g];
+            fea->_bad = outlier[g] != 0;                            // as ba::OptimizeCurrentPoseOnly: _bad for the outliers, _depth for the inliers
+            if (!fea->_bad) {
+                fea->_depth = Frame::_camera->World2Camera(fea->_mappoint->_pos_world, f->_TCW)[2];
+                if (fea->_mappoint->_bad == false) fea->_mappoint->_cnt_found++;
+            }
+            ++g;
+        }
+    }
+}
+
+int PoseOptimizer::Optimize(Frame *current, const std::vector<double> *u_right)
+{
+    if (!current) { LOG(ERROR) << "PoseOptimizer::Optimize: a null frame" << endl; _outliers.clear(); _rounds.clear(); _inliers.clear(); return 0; }
+    OptimizeBatch(std::vector<Frame *>(1, current), std::vector<const std::vector<double> *>(1, u_right));
+    return _inliers.empty() ? 0 : _inliers[0];
+}
+
+}  // namespace ygz
