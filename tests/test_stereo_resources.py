@@ -48,6 +48,13 @@ def test_kernel_file_keeps_the_constraints():
     # one wavefront per left keypoint, all pairs in one launch; one workgroup per pair for the median
     assert re.search(r"k_stereo_match, dim3\(\(unsigned\)stride, \(unsigned\)n_pairs\), dim3\(64\)", hip)
     assert re.search(r"k_stereo_median, dim3\(\(unsigned\)n_pairs\), dim3\(256\)", hip)
-    # one upload, one copy back, one wait
+    # one upload, one copy back, one wait: the two calls of the blob helper and no transfer of the function's own; the helper's upload is one copy,
+    # its fetch one copy and the one wait
     run = hip[hip.index("static int stereo_run"):hip.index("// the checks of the array form")]
-    assert run.count("hipMemcpyAsync(") == 2 and run.count("hipStreamSynchronize(") == 1
+    assert (run.count("ygz_blob_upload(") == 1 and run.count("ygz_blob_fetch(") == 1 and "hipMemcpyAsync(" not in run
+            and "hipStreamSynchronize(" not in run)
+    ctx = open(os.path.join(ROOT, "ygz_slam_amd", "csrc", "ctx.hip")).read()
+    upload = ctx[ctx.index("int ygz_blob_upload("):ctx.index("int ygz_blob_fetch(")]
+    fetch = ctx[ctx.index("int ygz_blob_fetch("):ctx.index("// ---- packed transfers")]
+    assert upload.count("hipMemcpyAsync(") == 1 and "hipStreamSynchronize(" not in upload
+    assert fetch.count("hipMemcpyAsync(") == 1 and fetch.count("hipStreamSynchronize(") == 1

@@ -674,7 +674,7 @@ int ygz_hip_find_direct_projection_mp_begin(ygz_hip_ctx *ctx, int cur_slot, cons
     m.n_keyframes = n_keyframes; m.kf_slot = kf_slot; m.kf_T = kf_T;
     m.n_candidates = n; m.cand_point = iota.data(); m.cand_kf = cand_kf; m.cand_level = level_ref; m.cand_px_ref = px_ref;
     LmapCandOut co = { nullptr, nullptr, nullptr, nullptr };
-    const int rc = lmap_run(ctx, cur_slot, T_cur, &m, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &co, SCR_GEN_0 + 10, true);
+    const int rc = lmap_run(ctx, cur_slot, T_cur, &m, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &co, SCR_LMAP_ASYNC, true);
     if (rc == YGZ_OK) { ctx->lmap_async_n = n; ctx->lmap_async_k = n_keyframes; }
     return rc;
 }
@@ -687,7 +687,7 @@ int ygz_hip_find_direct_projection_mp_end(ygz_hip_ctx *ctx, int n, uint8_t *in_v
     const size_t Ns = (size_t)n;
     ctx->lmap_async_n = 0;
     YGZ_HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    uint8_t *buf = (uint8_t *)ctx->scratch[SCR_GEN_0 + 10], *hb = (uint8_t *)ctx->scratch_host[SCR_GEN_0 + 10];
+    uint8_t *buf = (uint8_t *)ctx->scratch[SCR_LMAP_ASYNC], *hb = (uint8_t *)ctx->scratch_host[SCR_LMAP_ASYNC];
     if (!buf || !hb) return YGZ_E_STATE;
     const LmapLayout Y = lmap_layout(buf, Ns, (size_t)ctx->lmap_async_k, Ns);
 #define H_(dptr) (hb + ((const uint8_t *)(dptr) - buf))

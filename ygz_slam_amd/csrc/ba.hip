@@ -410,12 +410,12 @@ int ygz_ba_fetch_result(ygz_hip_ctx *ctx, int window, const void *d_stats, ygz_b
     double *stage = nullptr;
     int rc = YGZ_OK;
     if (chi2_edge && E > 0) {
-        if ((rc = ygz_scratch(ctx, SCR_GEN_0 + 9, E * 8, (void **)&stage)) != YGZ_OK) return rc;
+        if ((rc = ygz_scratch(ctx, SCR_BA_CHI2, E * 8, (void **)&stage)) != YGZ_OK) return rc;
         k_ba_unpack_edges<<<dim3(ygz_div_up((int)E, 256)), dim3(256), 0, ctx->stream>>>(w->chi2e_c, w->edge_rl, (int)E, 1, stage);
         YGZ_HIPCHK(ctx, hipGetLastError());
     }
     YgzPack pk;
-    if ((rc = ygz_pack_begin(ctx, &pk, sizeof(ygz_ba_stats) + K * 48 + P * 24 + E * 8 + 64, SCR_GEN_0 + 8)) != YGZ_OK) return rc;
+    if ((rc = ygz_pack_begin(ctx, &pk, sizeof(ygz_ba_stats) + K * 48 + P * 24 + E * 8 + 64, SCR_BA_PACK)) != YGZ_OK) return rc;
     void *h_st = ygz_pack_add(&pk, d_stats, sizeof(ygz_ba_stats)), *h_po = ygz_pack_add(&pk, w->poses, K * 48), *h_pt = ygz_pack_add(&pk, w->points, P * 24);
     void *h_c = stage ? ygz_pack_add(&pk, stage, E * 8) : nullptr;
     if (!h_st || !h_po || !h_pt || (stage && !h_c)) return YGZ_E_CAPACITY;

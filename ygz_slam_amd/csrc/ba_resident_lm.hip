@@ -995,7 +995,7 @@ static int lm_light_barrier_allowed(ygz_hip_ctx *ctx)
     if (ctx->lm_light_barrier >= 0) return ctx->lm_light_barrier;
     void *d = nullptr;
     const size_t bytes = (8 * 64 + 8 * 1024 + 4) * sizeof(unsigned);
-    if (ygz_scratch(ctx, SCR_GEN_0 + 5, bytes, &d) != YGZ_OK) return ctx->lm_light_barrier = 0;
+    if (ygz_scratch(ctx, SCR_LM_REC, bytes, &d) != YGZ_OK) return ctx->lm_light_barrier = 0;
     unsigned *bars = (unsigned *)d, *data = bars + 8 * 64, *result = data + 8 * 1024;
     unsigned res[4] = { 0, 1, 1, 0 };
     if (hipMemsetAsync(d, 0, bytes, ctx->stream) == hipSuccess) {
@@ -1083,7 +1083,7 @@ int ygz_hip_ba_optimize_resident(ygz_hip_ctx *ctx, int window_begin, int n_windo
     A.dbg = nullptr; A.prio = (ctx->wave_prio_mask >> 3) & 1; A.spread = ctx->lm_spread ? 1 : 0;
     A.xcd_barrier = lm_light_barrier_allowed(ctx);               // self-tested once per context (k_lm_barrier_selftest); YGZ_LM_XCD_BARRIER=0 / 1 overrides
     static const bool lm_debug = getenv("YGZ_LM_DEBUG") != nullptr;
-    if (lm_debug) { void *d = nullptr; if (ygz_scratch(ctx, SCR_GEN_0 + 4, 16 * 8, &d) == YGZ_OK) A.dbg = (long long *)d; }
+    if (lm_debug) { void *d = nullptr; if (ygz_scratch(ctx, SCR_LM_DEBUG, 16 * 8, &d) == YGZ_OK) A.dbg = (long long *)d; }
     YgzAuxScope aux(ctx, 1);
     // barrier counters and abort flags zeroed, iterations = -1 until a team finishes (0xFF in the launch's statistics, 0xFE in the windows' own
     // records; 0xFF there = never run, ba_carve): one small launch (a 2-D memset, a memset and one memset per window took 0.15 ms of the
@@ -1138,7 +1138,7 @@ int ygz_hip_ba_get_stats(ygz_hip_ctx *ctx, int window_begin, int n_windows, ygz_
     if (!table) return rc;
     // one gather kernel and ONE copy for the whole range (a copy per window cost 20 us each behind the last LM launch of a run)
     double *d_rec = nullptr;
-    if ((rc = ygz_scratch(ctx, SCR_GEN_0 + 5, (size_t)n_windows * LM_REC * 8, (void **)&d_rec)) != YGZ_OK) return rc;
+    if ((rc = ygz_scratch(ctx, SCR_LM_REC, (size_t)n_windows * LM_REC * 8, (void **)&d_rec)) != YGZ_OK) return rc;
     YGZ_LAUNCH(ctx, KID_BA_LM, k_ba_records, dim3(ygz_div_up(n_windows, 64)), dim3(64), table + window_begin, n_windows, d_rec);
     std::vector<double> hr((size_t)n_windows * LM_REC);
     YGZ_HIPCHK(ctx, hipMemcpyAsync(hr.data(), d_rec, hr.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -1181,7 +1181,7 @@ int ygz_hip_ba_get_outlier_stats(ygz_hip_ctx *ctx, int window_begin, int n_windo
     const BaDev *table = ygz_ba_table(ctx, &rc);
     if (!table) return rc;
     double *d_rec = nullptr;
-    if ((rc = ygz_scratch(ctx, SCR_GEN_0 + 5, (size_t)n_windows * LM_REC * 8, (void **)&d_rec)) != YGZ_OK) return rc;
+    if ((rc = ygz_scratch(ctx, SCR_LM_REC, (size_t)n_windows * LM_REC * 8, (void **)&d_rec)) != YGZ_OK) return rc;
     YGZ_LAUNCH(ctx, KID_BA_LM, k_ba_records, dim3(ygz_div_up(n_windows, 64)), dim3(64), table + window_begin, n_windows, d_rec);
     std::vector<double> hr((size_t)n_windows * LM_REC);
     YGZ_HIPCHK(ctx, hipMemcpyAsync(hr.data(), d_rec, hr.size() * 8, hipMemcpyDeviceToHost, ctx->stream));

@@ -233,7 +233,7 @@ int ygz_hip_track_get_summary(ygz_hip_ctx *ctx, double *out, int capacity_pairs,
     if (ctx->n_pairs > capacity_pairs) return YGZ_E_CAPACITY;
     { int rj = ygz_join(ctx); if (rj != YGZ_OK) return rj; }
     double *d = nullptr;
-    int rc = ygz_scratch(ctx, SCR_GEN_0 + 2, (size_t)ctx->n_pairs * SUM_DOUBLES * 8, (void **)&d);
+    int rc = ygz_scratch(ctx, SCR_BULK_SUMS, (size_t)ctx->n_pairs * SUM_DOUBLES * 8, (void **)&d);
     if (rc != YGZ_OK) return rc;
     SumArgs A;
     A.pair_q = ctx->pair_q; A.n_kp = ctx->n_kp; A.trk_n = ctx->trk_n; A.cells = ctx->cells; A.max_frames = ctx->prm.max_frames;

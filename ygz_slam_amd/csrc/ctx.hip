@@ -84,6 +84,28 @@ void *ygz_stage(ygz_hip_ctx *ctx, size_t bytes)
     return r;
 }
 
+// ---- one packed block per entry point (ygz_internal.h): thin wrappers, no stream operation of their own beyond the two copies and the wait
+int ygz_blob_open(ygz_hip_ctx *ctx, int scratch_id, size_t dev_bytes, size_t host_bytes, YgzBlob *b)
+{
+    if (dev_bytes == YgzBlobLayout::BAD || host_bytes == YgzBlobLayout::BAD) return YGZ_E_CAPACITY;
+    const int rc = ygz_scratch(ctx, scratch_id, dev_bytes, (void **)&b->dev);
+    if (rc != YGZ_OK) return rc;
+    b->host = (uint8_t *)ygz_stage(ctx, host_bytes);
+    return b->host ? YGZ_OK : YGZ_E_HIP;
+}
+int ygz_blob_upload(ygz_hip_ctx *ctx, const YgzBlob &b, size_t end)
+{
+    YGZ_HIPCHK(ctx, hipMemcpyAsync(b.dev, b.host, end, hipMemcpyHostToDevice, ctx->stream));
+    return YGZ_OK;
+}
+int ygz_blob_fetch(ygz_hip_ctx *ctx, const YgzBlob &b, size_t begin, size_t end)
+{
+    YGZ_HIPCHK(ctx, hipGetLastError());
+    if (end > begin) YGZ_HIPCHK(ctx, hipMemcpyAsync(b.host + begin, b.dev + begin, end - begin, hipMemcpyDeviceToHost, ctx->stream));
+    YGZ_HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return YGZ_OK;
+}
+
 // ---- packed transfers of single-frame calls (ygz_internal.h)
 __global__ __launch_bounds__(256) void k_copy_segs(YgzPackSegs S)
 {

@@ -111,8 +111,6 @@ __global__ __launch_bounds__(CULL_WALK_LANES) void k_cull_walk(int n_points, int
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------------
-size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
-
 bool params_ok(const ygz_cull_params &q)
 {
     return q.th_obs >= 1 && q.th_obs <= 256 && q.min_obs >= 0 && q.min_obs <= 256 && q.level_slack >= -1 && q.level_slack <= 15 &&
@@ -169,32 +167,25 @@ int ygz_hip_keyframe_redundancy(ygz_hip_ctx *ctx, int n_points, const int32_t *o
     YgzDeviceGuard dg_(ctx);
     { int rj_ = ygz_join(ctx); if (rj_ != YGZ_OK) return rj_; }
     // [offsets | owner | kl) goes up, [counts) comes back
-    size_t o = 0;
-    const size_t o_off = o; o = al(o + (P + 1) * 4);
-    const size_t o_own = o; o = al(o + N * 4);
-    const size_t o_kl = o; o = al(o + N * 4);
-    const size_t in_end = o;
-    const size_t o_cnt = o; o = al(o + 2 * K * 4);
-    const size_t total = o;
-    uint8_t *dev = nullptr;
-    const int rc = ygz_scratch(ctx, SCR_GEN_0 + 19, total, (void **)&dev);
+    YgzBlobLayout L;
+    const size_t o_off = L.add_n<int32_t>(P + 1), o_own = L.add_n<int32_t>(N), o_kl = L.add_n<int32_t>(N), in_end = L.end;
+    const size_t o_cnt = L.add_n<int32_t>(2 * K);
+    YgzBlob b;
+    int rc = ygz_blob_open(ctx, SCR_CULL, L.end, L.end, &b);
     if (rc != YGZ_OK) return rc;
-    uint8_t *up = (uint8_t *)ygz_stage(ctx, total);
-    if (!up) return YGZ_E_HIP;
-    memcpy(up + o_off, offsets, (P + 1) * 4);
-    int32_t *owner = (int32_t *)(up + o_own);
+    memcpy(b.host + o_off, offsets, (P + 1) * 4);
+    int32_t *owner = ygz_at<int32_t>(b.host, o_own);
     for (int p = 0; p < n_points; ++p)
         for (int g = offsets[p]; g < offsets[p + 1]; ++g) owner[g] = p;
-    pack_lists(n_obs, kf, level, (int32_t *)(up + o_kl));
-    YGZ_HIPCHK(ctx, hipMemcpyAsync(dev, up, in_end, hipMemcpyHostToDevice, ctx->stream));
-    YGZ_HIPCHK(ctx, hipMemsetAsync(dev + o_cnt, 0, 2 * K * 4, ctx->stream));
-    YGZ_LAUNCH(ctx, KID_COUNT, k_cull_counts, dim3(ygz_div_up(n_obs, CULL_RUN)), dim3(CULL_LANES), n_obs, n_keyframes, (const int32_t *)(dev + o_off),
-               (const int32_t *)(dev + o_own), (const int32_t *)(dev + o_kl), (int)q.th_obs, (int)q.level_slack, (int32_t *)(dev + o_cnt));
-    YGZ_HIPCHK(ctx, hipGetLastError());
-    YGZ_HIPCHK(ctx, hipMemcpyAsync(up + o_cnt, dev + o_cnt, 2 * K * 4, hipMemcpyDeviceToHost, ctx->stream));
-    YGZ_HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    memcpy(tracked, up + o_cnt, K * 4);
-    memcpy(redundant, up + o_cnt + K * 4, K * 4);
+    pack_lists(n_obs, kf, level, ygz_at<int32_t>(b.host, o_kl));
+    if ((rc = ygz_blob_upload(ctx, b, in_end)) != YGZ_OK) return rc;
+    YGZ_HIPCHK(ctx, hipMemsetAsync(b.dev + o_cnt, 0, 2 * K * 4, ctx->stream));
+    YGZ_LAUNCH(ctx, KID_COUNT, k_cull_counts, dim3(ygz_div_up(n_obs, CULL_RUN)), dim3(CULL_LANES), n_obs, n_keyframes,
+               ygz_at<const int32_t>(b.dev, o_off), ygz_at<const int32_t>(b.dev, o_own), ygz_at<const int32_t>(b.dev, o_kl), (int)q.th_obs,
+               (int)q.level_slack, ygz_at<int32_t>(b.dev, o_cnt));
+    if ((rc = ygz_blob_fetch(ctx, b, o_cnt, o_cnt + 2 * K * 4)) != YGZ_OK) return rc;
+    memcpy(tracked, b.host + o_cnt, K * 4);
+    memcpy(redundant, b.host + o_cnt + K * 4, K * 4);
     return YGZ_OK;
 }
 
@@ -232,29 +223,19 @@ int ygz_hip_cull_keyframes(ygz_hip_ctx *ctx, int n_points, const int32_t *offset
     YgzDeviceGuard dg_(ctx);
     { int rj_ = ygz_join(ctx); if (rj_ != YGZ_OK) return rj_; }
     // [offsets | kl | cand | koff | kobs | kpt) goes up, live stays, [out | dead) comes back
-    size_t o = 0;
-    const size_t o_off = o; o = al(o + (P + 1) * 4);
-    const size_t o_kl = o; o = al(o + N * 4);
-    const size_t o_cand = o; o = al(o + C * 4);
-    const size_t o_koff = o; o = al(o + (C + 1) * 4);
-    const size_t o_kobs = o; o = al(o + (M + 1) * 4);
-    const size_t o_kpt = o; o = al(o + (M + 1) * 4);
-    const size_t in_end = o;
-    const size_t o_live = o; o = al(o + P * 4);
-    const size_t o_out = o; o = al(o + 3 * C * 4);
-    const size_t o_dead = o; o = al(o + P);
-    const size_t total = o;
-    uint8_t *dev = nullptr;
-    const int rc = ygz_scratch(ctx, SCR_GEN_0 + 19, total, (void **)&dev);
+    YgzBlobLayout L;
+    const size_t o_off = L.add_n<int32_t>(P + 1), o_kl = L.add_n<int32_t>(N), o_cand = L.add_n<int32_t>(C), o_koff = L.add_n<int32_t>(C + 1);
+    const size_t o_kobs = L.add_n<int32_t>(M + 1), o_kpt = L.add_n<int32_t>(M + 1), in_end = L.end;
+    const size_t o_live = L.add_n<int32_t>(P), o_out = L.add_n<int32_t>(3 * C), o_dead = L.add(P), total = L.end;
+    YgzBlob b;
+    int rc = ygz_blob_open(ctx, SCR_CULL, total, total, &b);
     if (rc != YGZ_OK) return rc;
-    uint8_t *up = (uint8_t *)ygz_stage(ctx, total);
-    if (!up) return YGZ_E_HIP;
-    memcpy(up + o_off, offsets, (P + 1) * 4);
-    pack_lists(n_obs, kf, level, (int32_t *)(up + o_kl));
-    memcpy(up + o_cand, cand, C * 4);
-    memcpy(up + o_koff, koff.data(), (C + 1) * 4);
+    memcpy(b.host + o_off, offsets, (P + 1) * 4);
+    pack_lists(n_obs, kf, level, ygz_at<int32_t>(b.host, o_kl));
+    memcpy(b.host + o_cand, cand, C * 4);
+    memcpy(b.host + o_koff, koff.data(), (C + 1) * 4);
     {
-        int32_t *kobs = (int32_t *)(up + o_kobs), *kpt = (int32_t *)(up + o_kpt);
+        int32_t *kobs = ygz_at<int32_t>(b.host, o_kobs), *kpt = ygz_at<int32_t>(b.host, o_kpt);
         std::vector<int32_t> fill(koff.begin(), koff.end() - 1);
         for (int p = 0; p < n_points; ++p)
             for (int g = offsets[p]; g < offsets[p + 1]; ++g) {
@@ -263,18 +244,16 @@ int ygz_hip_cull_keyframes(ygz_hip_ctx *ctx, int n_points, const int32_t *offset
                 kobs[fill[s]] = g; kpt[fill[s]] = p; ++fill[s];
             }
     }
-    YGZ_HIPCHK(ctx, hipMemcpyAsync(dev, up, in_end, hipMemcpyHostToDevice, ctx->stream));
-    YGZ_LAUNCH(ctx, KID_COUNT, k_cull_walk, dim3(1), dim3(CULL_WALK_LANES), n_points, n_keyframes, n_cand, (const int32_t *)(dev + o_off),
-               (const int32_t *)(dev + o_kl), (const int32_t *)(dev + o_cand), (const int32_t *)(dev + o_koff), (const int32_t *)(dev + o_kobs),
-               (const int32_t *)(dev + o_kpt), (int)q.th_obs, (int)q.level_slack, (int)q.min_obs, q.ratio, (int32_t *)(dev + o_live),
-               (uint8_t *)(dev + o_dead), (int32_t *)(dev + o_out));
-    YGZ_HIPCHK(ctx, hipGetLastError());
-    YGZ_HIPCHK(ctx, hipMemcpyAsync(up + o_out, dev + o_out, (point_dead ? total : o_dead) - o_out, hipMemcpyDeviceToHost, ctx->stream));
-    YGZ_HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    memcpy(culled, up + o_out, C * 4);
-    memcpy(tracked, up + o_out + C * 4, C * 4);
-    memcpy(redundant, up + o_out + 2 * C * 4, C * 4);
-    if (point_dead) memcpy(point_dead, up + o_dead, P);
+    if ((rc = ygz_blob_upload(ctx, b, in_end)) != YGZ_OK) return rc;
+    YGZ_LAUNCH(ctx, KID_COUNT, k_cull_walk, dim3(1), dim3(CULL_WALK_LANES), n_points, n_keyframes, n_cand, ygz_at<const int32_t>(b.dev, o_off),
+               ygz_at<const int32_t>(b.dev, o_kl), ygz_at<const int32_t>(b.dev, o_cand), ygz_at<const int32_t>(b.dev, o_koff),
+               ygz_at<const int32_t>(b.dev, o_kobs), ygz_at<const int32_t>(b.dev, o_kpt), (int)q.th_obs, (int)q.level_slack, (int)q.min_obs,
+               q.ratio, ygz_at<int32_t>(b.dev, o_live), b.dev + o_dead, ygz_at<int32_t>(b.dev, o_out));
+    if ((rc = ygz_blob_fetch(ctx, b, o_out, point_dead ? total : o_dead)) != YGZ_OK) return rc;
+    memcpy(culled, b.host + o_out, C * 4);
+    memcpy(tracked, b.host + o_out + C * 4, C * 4);
+    memcpy(redundant, b.host + o_out + 2 * C * 4, C * 4);
+    if (point_dead) memcpy(point_dead, b.host + o_dead, P);
     return YGZ_OK;
 }
 

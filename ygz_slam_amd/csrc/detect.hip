@@ -640,7 +640,7 @@ int ygz_launch_detect(ygz_hip_ctx *ctx, int slot_begin, int n_slots)
         A.slot_begin = slot_begin; A.n_slots = n_slots;
         A.dbg_cyc = nullptr;
 #ifdef YGZ_FAST_TIMERS
-        { void *dd = nullptr; if (getenv("YGZ_FAST_DEBUG") && ygz_scratch(ctx, SCR_GEN_0 + 1, 3 * 65536, &dd) == YGZ_OK) { if (L == 0) (void)hipMemsetAsync(dd, 0, 3 * 65536, ctx->stream); A.dbg_cyc = (long long *)dd + 8192 * L; } }
+        { void *dd = nullptr; if (getenv("YGZ_FAST_DEBUG") && ygz_scratch(ctx, SCR_GEN_1, 3 * 65536, &dd) == YGZ_OK) { if (L == 0) (void)hipMemsetAsync(dd, 0, 3 * 65536, ctx->stream); A.dbg_cyc = (long long *)dd + 8192 * L; } }
 #endif
         AA.tiles_x[L] = ygz_div_up(A.w, FT_W);
         tiles += AA.tiles_x[L] * ygz_div_up(A.h, FT_H);
@@ -654,7 +654,7 @@ int ygz_launch_detect(ygz_hip_ctx *ctx, int slot_begin, int n_slots)
 #ifdef YGZ_FAST_TIMERS
     if (getenv("YGZ_FAST_DEBUG")) {
         void *dd = nullptr; static long long h[3 * 8192];
-        if (ygz_scratch(ctx, SCR_GEN_0 + 1, 3 * 65536, &dd) == YGZ_OK) {
+        if (ygz_scratch(ctx, SCR_GEN_1, 3 * 65536, &dd) == YGZ_OK) {
             (void)hipMemcpyAsync(h, dd, sizeof(h), hipMemcpyDeviceToHost, ctx->stream); (void)hipStreamSynchronize(ctx->stream);
             for (int L = 0; L < 3; ++L) {
                 double acc[6] = { 0, 0, 0, 0, 0, 0 };
@@ -733,7 +733,7 @@ int ygz_hip_get_keypoints(ygz_hip_ctx *ctx, int slot, ygz_kpt_soa *out, int capa
                  b_de = out->desc ? rows * 32 : 0;
     // (one gather kernel + ONE copy back: six copies on the stream before)
     YgzPack pk;
-    int rc = ygz_pack_begin(ctx, &pk, 64 + b_px + b_lv + b_sc + b_an + b_de, SCR_GEN_0 + 7);
+    int rc = ygz_pack_begin(ctx, &pk, 64 + b_px + b_lv + b_sc + b_an + b_de, SCR_DETECT_PACK);
     if (rc != YGZ_OK) return rc;
     uint8_t *st = (uint8_t *)ygz_pack_add(&pk, ctx->n_kp + slot, 4);
     uint8_t *h_px = b_px ? (uint8_t *)ygz_pack_add(&pk, ctx->kp_px + 2 * o, b_px) : nullptr, *h_lv = b_lv ? (uint8_t *)ygz_pack_add(&pk, ctx->kp_level + o, b_lv) : nullptr;

@@ -783,8 +783,6 @@ __global__ __launch_bounds__(GBA_LANES) void k_gba_accept(GbaDev D)
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------------
-size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
-
 bool finite_n(const double *v, size_t n)
 {
     for (size_t k = 0; k < n; ++k) if (!(std::fabs(v[k]) <= GB_DMAX)) return false;
@@ -831,45 +829,45 @@ struct Layout {
 Layout layout(size_t N, size_t L, size_t E)
 {
     Layout Y;
-    size_t o = 0;
-    Y.in = o; o = al(o + sizeof(GbaIn));
-    Y.rec = o; o = al(o + sizeof(GbaRec));
-    Y.fixed = o; o = al(o + N);
-    Y.edge_pose = o; o = al(o + E * 4);
-    Y.edge_point = o; o = al(o + E * 4);
-    Y.obs = o; o = al(o + E * 16);
-    Y.pt_off = o; o = al(o + (L + 1) * 4);
-    Y.pt_adj = o; o = al(o + E * 4);
-    Y.pt_pose = o; o = al(o + E * 4);
-    Y.ps_off = o; o = al(o + (N + 1) * 4);
-    Y.ps_adj = o; o = al(o + E * 4);
-    Y.ps_point = o; o = al(o + E * 4);
-    Y.slot_l = o; o = al(o + E * 4);
-    Y.slot_p = o; o = al(o + E * 4);
-    Y.t = o; o = al(o + N * 56);
-    Y.x = o; o = al(o + L * 24);
-    Y.in_end = o;
-    Y.tn = o; o = al(o + N * 56);
-    Y.xn = o; o = al(o + L * 24);
-    Y.res = o; o = al(o + E * 16);
-    Y.w = o; o = al(o + E * 8);
-    Y.jp = o; o = al(o + E * 96);
-    Y.jl = o; o = al(o + E * 48);
-    Y.hplp = o; o = al(o + E * 144);
-    Y.hpll = o; o = al(o + E * 144);
-    Y.cpart = o; o = al(o + ((E + GBA_CHUNK - 1) / GBA_CHUNK) * 8);
-    Y.lpart = o; o = al(o + ((L + GBA_CHUNK - 1) / GBA_CHUNK) * 8);
-    Y.hpp = o; o = al(o + N * 168);
-    Y.bp = o; o = al(o + N * 48);
-    Y.pose_vec = o; o = al(o + al(N * 168) + 6 * al(N * 48));         // Lf, then bt x r z p q
-    Y.vterm = o; o = al(o + N * 8);
-    Y.sterm = o; o = al(o + N * 8);
-    Y.hll = o; o = al(o + L * 48);
-    Y.bl = o; o = al(o + L * 24);
-    Y.hinv = o; o = al(o + L * 48);
-    Y.wl = o; o = al(o + L * 24);
-    Y.vl = o; o = al(o + L * 24);
-    Y.total = o;
+    YgzBlobLayout B;
+    Y.in = B.add(sizeof(GbaIn));
+    Y.rec = B.add(sizeof(GbaRec));
+    Y.fixed = B.add(N);
+    Y.edge_pose = B.add_n<int32_t>(E);
+    Y.edge_point = B.add_n<int32_t>(E);
+    Y.obs = B.add_n<double>(E * 2);
+    Y.pt_off = B.add_n<int32_t>(L + 1);
+    Y.pt_adj = B.add_n<int32_t>(E);
+    Y.pt_pose = B.add_n<int32_t>(E);
+    Y.ps_off = B.add_n<int32_t>(N + 1);
+    Y.ps_adj = B.add_n<int32_t>(E);
+    Y.ps_point = B.add_n<int32_t>(E);
+    Y.slot_l = B.add_n<int32_t>(E);
+    Y.slot_p = B.add_n<int32_t>(E);
+    Y.t = B.add_n<double>(N * 7);
+    Y.x = B.add_n<double>(L * 3);
+    Y.in_end = B.end;
+    Y.tn = B.add_n<double>(N * 7);
+    Y.xn = B.add_n<double>(L * 3);
+    Y.res = B.add_n<double>(E * 2);
+    Y.w = B.add_n<double>(E);
+    Y.jp = B.add_n<double>(E * 12);
+    Y.jl = B.add_n<double>(E * 6);
+    Y.hplp = B.add_n<double>(E * 18);
+    Y.hpll = B.add_n<double>(E * 18);
+    Y.cpart = B.add_n<double>((E + GBA_CHUNK - 1) / GBA_CHUNK);
+    Y.lpart = B.add_n<double>((L + GBA_CHUNK - 1) / GBA_CHUNK);
+    Y.hpp = B.add_n<double>(N * 21);
+    Y.bp = B.add_n<double>(N * 6);
+    Y.pose_vec = B.add(ygz_round_up_256(N * 168) + 6 * ygz_round_up_256(N * 48));         // Lf, then bt x r z p q
+    Y.vterm = B.add_n<double>(N);
+    Y.sterm = B.add_n<double>(N);
+    Y.hll = B.add_n<double>(L * 6);
+    Y.bl = B.add_n<double>(L * 3);
+    Y.hinv = B.add_n<double>(L * 6);
+    Y.wl = B.add_n<double>(L * 3);
+    Y.vl = B.add_n<double>(L * 3);
+    Y.total = B.end;
     return Y;
 }
 
@@ -902,14 +900,15 @@ int run(ygz_hip_ctx *ctx, int n, const double *poses, const uint8_t *fixed, int 
     { int rj_ = ygz_join(ctx); if (rj_ != YGZ_OK) return rj_; }
     const size_t N = (size_t)n, L = (size_t)nl, E = (size_t)ne;
     const Layout Y = layout(N, L, E);
-    uint8_t *dev = nullptr;
-    int rc = ygz_scratch(ctx, SCR_GEN_0 + 17, Y.total, (void **)&dev);
+    // one page-locked block: [0, in_end) goes up; the results come back compacted into a second area behind it
+    YgzBlobLayout down;
+    down.add(sizeof(GbaRec));
+    if (stage) for (size_t bytes : { E * 16, E * 8, E * 96, E * 48, N * 168, N * 48, L * 48, L * 24 }) down.add(bytes);
+    else { down.add(N * 56); down.add(L * 24); }
+    YgzBlob blob;
+    int rc = ygz_blob_open(ctx, SCR_GBA, Y.total, Y.in_end + down.end, &blob);
     if (rc != YGZ_OK) return rc;
-    // one page-locked block: [0, in_end) goes up; the results come back into a second area behind it
-    const size_t down_bytes = stage ? al(sizeof(GbaRec)) + al(E * 16) + al(E * 8) + al(E * 96) + al(E * 48) + al(N * 168) + al(N * 48) + al(L * 48) + al(L * 24)
-                                    : al(sizeof(GbaRec)) + al(N * 56) + al(L * 24);
-    uint8_t *up = (uint8_t *)ygz_stage(ctx, Y.in_end + down_bytes);
-    if (!up) return YGZ_E_HIP;
+    uint8_t *up = blob.host, *dev = blob.dev;
     GbaIn in;
     memset(&in, 0, sizeof in);
     int n_free = 0;
@@ -935,7 +934,7 @@ int run(ygz_hip_ctx *ctx, int n, const double *poses, const uint8_t *fixed, int 
         pt_pose[s] = fixed[v] ? -1 : v;
         ps_point[s] = edge_point[ps_adj[s]];
     }
-    YGZ_HIPCHK(ctx, hipMemcpyAsync(dev, up, Y.in_end, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = ygz_blob_upload(ctx, blob, Y.in_end)) != YGZ_OK) return rc;
     GbaDev D;
     D.in = (const GbaIn *)(dev + Y.in); D.rec = (GbaRec *)(dev + Y.rec); D.fixed = dev + Y.fixed;
     D.edge_pose = (const int32_t *)(dev + Y.edge_pose); D.edge_point = (const int32_t *)(dev + Y.edge_point); D.obs = (const double *)(dev + Y.obs);
@@ -946,9 +945,9 @@ int run(ygz_hip_ctx *ctx, int n, const double *poses, const uint8_t *fixed, int 
     D.res = (double *)(dev + Y.res); D.w = (double *)(dev + Y.w); D.Jp = (double *)(dev + Y.jp); D.Jl = (double *)(dev + Y.jl);
     D.HplP = (double *)(dev + Y.hplp); D.HplL = (double *)(dev + Y.hpll); D.cpart = (double *)(dev + Y.cpart); D.lpart = (double *)(dev + Y.lpart);
     D.Hpp = (double *)(dev + Y.hpp); D.bp = (double *)(dev + Y.bp);
-    const size_t vs = al(N * 48);
+    const size_t vs = ygz_round_up_256(N * 48);
     uint8_t *pv = dev + Y.pose_vec;
-    D.Lf = (double *)pv; pv += al(N * 168);
+    D.Lf = (double *)pv; pv += ygz_round_up_256(N * 168);
     D.bt = (double *)pv; D.x = (double *)(pv + vs); D.r = (double *)(pv + 2 * vs); D.z = (double *)(pv + 3 * vs); D.p = (double *)(pv + 4 * vs);
     D.q = (double *)(pv + 5 * vs);
     D.vterm = (double *)(dev + Y.vterm); D.sterm = (double *)(dev + Y.sterm);
@@ -977,7 +976,7 @@ int run(ygz_hip_ctx *ctx, int n, const double *poses, const uint8_t *fixed, int 
                                                         { Y.hpp, N * 168 }, { Y.bp, N * 48 }, { Y.hll, L * 48 }, { Y.bl, L * 24 } };
         for (const auto &q : parts) {
             YGZ_HIPCHK(ctx, hipMemcpyAsync(h + o, dev + q.src, q.bytes, hipMemcpyDeviceToHost, ctx->stream));
-            o += al(q.bytes);
+            o += ygz_round_up_256(q.bytes);
         }
         YGZ_HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
         R->rec = *hrec;
@@ -1015,9 +1014,9 @@ int run(ygz_hip_ctx *ctx, int n, const double *poses, const uint8_t *fixed, int 
         }
         if (b == max_batches) return YGZ_E_STATE;                      // cannot happen: the cap ends the solve within max_batches
     }
-    uint8_t *h = up + Y.in_end + al(sizeof(GbaRec));
+    uint8_t *h = up + Y.in_end + ygz_round_up_256(sizeof(GbaRec));
     YGZ_HIPCHK(ctx, hipMemcpyAsync(h, dev + Y.t, N * 56, hipMemcpyDeviceToHost, ctx->stream));
-    YGZ_HIPCHK(ctx, hipMemcpyAsync(h + al(N * 56), dev + Y.x, L * 24, hipMemcpyDeviceToHost, ctx->stream));
+    YGZ_HIPCHK(ctx, hipMemcpyAsync(h + ygz_round_up_256(N * 56), dev + Y.x, L * 24, hipMemcpyDeviceToHost, ctx->stream));
     YGZ_HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     R->rec = *hrec;
     return YGZ_OK;
@@ -1055,9 +1054,9 @@ int ygz_hip_global_ba(ygz_hip_ctx *ctx, int n_poses, const double *poses, const 
     result->status = r.status; result->lm_iterations = r.lm_iterations; result->n_solves = r.n_solves;
     result->cg_iterations_total = r.cg_total; result->cg_capped = r.cg_capped; result->pad = 0;
     const size_t N = (size_t)n_poses, L = (size_t)n_points;
-    const uint8_t *h = R.host + al(sizeof(GbaRec));
+    const uint8_t *h = R.host + ygz_round_up_256(sizeof(GbaRec));
     memcpy(poses_out, failed ? (const void *)poses : (const void *)h, N * 56);
-    memcpy(points_out, failed ? (const void *)points : (const void *)(h + al(N * 56)), L * 24);
+    memcpy(points_out, failed ? (const void *)points : (const void *)(h + ygz_round_up_256(N * 56)), L * 24);
     return YGZ_OK;
 }
 
@@ -1070,21 +1069,21 @@ int ygz_hip_gba_linearize(ygz_hip_ctx *ctx, int n_poses, const double *poses, co
     const int rc = run(ctx, n_poses, poses, fixed, n_points, points, n_edges, edge_pose, edge_point, obs, K4, huber_delta, params, true, &R);
     if (rc != YGZ_OK) return rc;
     const size_t N = (size_t)n_poses, L = (size_t)n_points, E = (size_t)n_edges;
-    const uint8_t *h = R.host + al(sizeof(GbaRec));
+    const uint8_t *h = R.host + ygz_round_up_256(sizeof(GbaRec));
     if (residuals) to_rows((const double *)h, E, 2, residuals);
-    h += al(E * 16);
+    h += ygz_round_up_256(E * 16);
     if (weights) memcpy(weights, h, E * 8);
-    h += al(E * 8);
+    h += ygz_round_up_256(E * 8);
     if (Jp) to_rows((const double *)h, E, 12, Jp);
-    h += al(E * 96);
+    h += ygz_round_up_256(E * 96);
     if (Jl) to_rows((const double *)h, E, 6, Jl);
-    h += al(E * 48);
+    h += ygz_round_up_256(E * 48);
     if (Hpp) memcpy(Hpp, h, N * 168);
-    h += al(N * 168);
+    h += ygz_round_up_256(N * 168);
     if (bp) memcpy(bp, h, N * 48);
-    h += al(N * 48);
+    h += ygz_round_up_256(N * 48);
     if (Hll) to_rows((const double *)h, L, 6, Hll);
-    h += al(L * 48);
+    h += ygz_round_up_256(L * 48);
     if (bl) to_rows((const double *)h, L, 3, bl);
     if (cost) *cost = R.rec.cost_initial;
     return R.rec.status == YGZ_GBA_FAILED ? YGZ_E_STATE : YGZ_OK;

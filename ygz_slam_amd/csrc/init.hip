@@ -729,8 +729,6 @@ const std::vector<int32_t> &ygz_cvrng_cached_sets(int n, int max_iter, int k)
 
 namespace {
 
-size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct Layout {
     size_t in, px1, px2, sets, inl_in, in_end;             // the upload
     size_t res, pts3d, tri, inl_h, inl_f, score_h, score_f, H21, F21, out_end;   // the copy back
@@ -739,53 +737,55 @@ struct Layout {
 Layout layout(int n, int it)
 {
     Layout L;
-    size_t o = 0;
-    L.in = o; o = al(o + sizeof(InitIn));
-    L.px1 = o; o = al(o + (size_t)n * 16);
-    L.px2 = o; o = al(o + (size_t)n * 16);
-    L.sets = o; o = al(o + (size_t)it * 32);
-    L.inl_in = o; o = al(o + (size_t)n);
-    L.in_end = o;
-    L.res = o; o = al(o + sizeof(ygz_init_result));
-    L.pts3d = o; o = al(o + (size_t)n * 24);
-    L.tri = o; o = al(o + (size_t)n);
-    L.inl_h = o; o = al(o + (size_t)n);
-    L.inl_f = o; o = al(o + (size_t)n);
-    L.score_h = o; o = al(o + (size_t)it * 4);
-    L.score_f = o; o = al(o + (size_t)it * 4);
-    L.H21 = o; o = al(o + (size_t)it * 72);
-    L.F21 = o; o = al(o + (size_t)it * 72);
-    L.out_end = o;
-    L.pn1 = o; o = al(o + (size_t)n * 16);
-    L.pn2 = o; o = al(o + (size_t)n * 16);
-    L.T = o; o = al(o + 27 * 8);
-    L.H12 = o; o = al(o + (size_t)it * 72);
-    L.contrib = o; o = al(o + (size_t)n * it * 12);
-    L.rec = o; o = al(o + sizeof(InitRec));
-    L.p3d = o; o = al(o + (size_t)8 * n * 24);
-    L.cosv = o; o = al(o + (size_t)8 * n * 4);
-    L.flags = o; o = al(o + (size_t)8 * n);
-    L.total = o;
+    YgzBlobLayout B;
+    const size_t N = (size_t)n, I = (size_t)it;
+    L.in = B.add(sizeof(InitIn));
+    L.px1 = B.add_n<double>(N * 2);
+    L.px2 = B.add_n<double>(N * 2);
+    L.sets = B.add_n<int32_t>(I * 8);
+    L.inl_in = B.add(N);
+    L.in_end = B.end;
+    L.res = B.add(sizeof(ygz_init_result));
+    L.pts3d = B.add_n<double>(N * 3);
+    L.tri = B.add(N);
+    L.inl_h = B.add(N);
+    L.inl_f = B.add(N);
+    L.score_h = B.add_n<float>(I);
+    L.score_f = B.add_n<float>(I);
+    L.H21 = B.add_n<double>(I * 9);
+    L.F21 = B.add_n<double>(I * 9);
+    L.out_end = B.end;
+    L.pn1 = B.add_n<double>(N * 2);
+    L.pn2 = B.add_n<double>(N * 2);
+    L.T = B.add_n<double>(27);
+    L.H12 = B.add_n<double>(I * 9);
+    L.contrib = B.add_n<float>(N * I * 3);
+    L.rec = B.add(sizeof(InitRec));
+    L.p3d = B.add_n<double>(8 * N * 3);
+    L.cosv = B.add_n<float>(8 * N);
+    L.flags = B.add(8 * N);
+    L.total = B.end;
     return L;
 }
 
 InitDev bind(uint8_t *b, const Layout &L)
 {
     InitDev D;
-    D.in = (const InitIn *)(b + L.in); D.px1 = (const double *)(b + L.px1); D.px2 = (const double *)(b + L.px2);
-    D.sets = (const int32_t *)(b + L.sets); D.inl_in = b + L.inl_in;
-    D.pn1 = (double *)(b + L.pn1); D.pn2 = (double *)(b + L.pn2); D.T = (double *)(b + L.T); D.H12 = (double *)(b + L.H12);
-    D.contrib = (float *)(b + L.contrib); D.rec = (InitRec *)(b + L.rec); D.p3d = (double *)(b + L.p3d); D.cosv = (float *)(b + L.cosv);
-    D.flags = b + L.flags;
-    D.res = (ygz_init_result *)(b + L.res); D.pts3d = (double *)(b + L.pts3d); D.tri = b + L.tri; D.inl_h = b + L.inl_h; D.inl_f = b + L.inl_f;
-    D.score_h = (float *)(b + L.score_h); D.score_f = (float *)(b + L.score_f); D.H21 = (double *)(b + L.H21); D.F21 = (double *)(b + L.F21);
+    D.in = ygz_at<const InitIn>(b, L.in); D.px1 = ygz_at<const double>(b, L.px1); D.px2 = ygz_at<const double>(b, L.px2);
+    D.sets = ygz_at<const int32_t>(b, L.sets); D.inl_in = b + L.inl_in;
+    D.pn1 = ygz_at<double>(b, L.pn1); D.pn2 = ygz_at<double>(b, L.pn2); D.T = ygz_at<double>(b, L.T); D.H12 = ygz_at<double>(b, L.H12);
+    D.contrib = ygz_at<float>(b, L.contrib); D.rec = ygz_at<InitRec>(b, L.rec); D.p3d = ygz_at<double>(b, L.p3d);
+    D.cosv = ygz_at<float>(b, L.cosv); D.flags = b + L.flags;
+    D.res = ygz_at<ygz_init_result>(b, L.res); D.pts3d = ygz_at<double>(b, L.pts3d); D.tri = b + L.tri; D.inl_h = b + L.inl_h;
+    D.inl_f = b + L.inl_f; D.score_h = ygz_at<float>(b, L.score_h); D.score_f = ygz_at<float>(b, L.score_f);
+    D.H21 = ygz_at<double>(b, L.H21); D.F21 = ygz_at<double>(b, L.F21);
     return D;
 }
 
 enum { RUN_HYP = 1, RUN_REC = 2 };
 
 // validation, one upload, the launches of `what`, one copy back of [res, out_end) (or of [res, inl_h) when only the reconstruction's
-// outputs are wanted), one wait; `out` receives the page-locked copy
+// outputs are wanted), one wait; `out` receives the page-locked image of the block
 int run(ygz_hip_ctx *ctx, const double *px1, const double *px2, int n, const double *K4, const ygz_init_params *params, int what,
         int model_in, const double *M, const uint8_t *inl_in, uint8_t **out, Layout *Lout)
 {
@@ -800,12 +800,10 @@ int run(ygz_hip_ctx *ctx, const double *px1, const double *px2, int n, const dou
     { int rj_ = ygz_join(ctx); if (rj_ != YGZ_OK) return rj_; }
     const int it = p.max_iter;
     const Layout L = layout(n, it);
-    uint8_t *dev = nullptr;
-    int rc = ygz_scratch(ctx, SCR_GEN_0 + 11, L.total, (void **)&dev);
+    YgzBlob b;                                               // [0, in_end) goes up, [res, out_end) comes back
+    int rc = ygz_blob_open(ctx, SCR_INIT, L.total, L.out_end, &b);
     if (rc != YGZ_OK) return rc;
-    uint8_t *up = (uint8_t *)ygz_stage(ctx, L.out_end);       // one page-locked block: [0, in_end) goes up, [res, out_end) comes back
-    if (!up) return YGZ_E_HIP;
-    uint8_t *down = up + L.res;
+    uint8_t *up = b.host, *dev = b.dev;
     InitIn in;
     memset(&in, 0, sizeof in);
     for (int k = 0; k < 4; ++k) in.K4[k] = K4 ? K4[k] : 0.0;
@@ -818,7 +816,7 @@ int run(ygz_hip_ctx *ctx, const double *px1, const double *px2, int n, const dou
     if (what & RUN_HYP) memcpy(up + L.sets, ygz_cvrng_cached_sets(n, it, 8).data(), (size_t)it * 32);
     if (inl_in) memcpy(up + L.inl_in, inl_in, (size_t)n);
     const size_t up_bytes = inl_in ? L.in_end : L.inl_in;
-    YGZ_HIPCHK(ctx, hipMemcpyAsync(dev, up, up_bytes, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = ygz_blob_upload(ctx, b, up_bytes)) != YGZ_OK) return rc;
     YGZ_HIPCHK(ctx, hipMemsetAsync(dev + L.res, 0, sizeof(ygz_init_result), ctx->stream));
     const InitDev D = bind(dev, L);
     if (what & RUN_HYP) {
@@ -834,11 +832,9 @@ int run(ygz_hip_ctx *ctx, const double *px1, const double *px2, int n, const dou
         YGZ_LAUNCH(ctx, KID_COUNT, k_init_parallax, dim3(8), dim3(INIT_SEL_THREADS), D);
         YGZ_LAUNCH(ctx, KID_COUNT, k_init_accept, dim3(1), dim3(256), D);
     }
-    YGZ_HIPCHK(ctx, hipGetLastError());
     const size_t down_end = (what & RUN_HYP) && !(what & RUN_REC) ? L.out_end : L.inl_h;
-    YGZ_HIPCHK(ctx, hipMemcpyAsync(down, dev + L.res, down_end - L.res, hipMemcpyDeviceToHost, ctx->stream));
-    YGZ_HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    *out = down;
+    if ((rc = ygz_blob_fetch(ctx, b, L.res, down_end)) != YGZ_OK) return rc;
+    *out = up;
     *Lout = L;
     return YGZ_OK;
 }
@@ -868,9 +864,9 @@ int ygz_hip_initialize(ygz_hip_ctx *ctx, const double *px1, const double *px2, i
     Layout L;
     const int rc = run(ctx, px1, px2, n, K4, params, RUN_HYP | RUN_REC, 0, nullptr, nullptr, &o, &L);
     if (rc != YGZ_OK) return rc;
-    memcpy(result, o, sizeof *result);
-    if (pts3d_out) memcpy(pts3d_out, o + (L.pts3d - L.res), (size_t)n * 24);
-    if (triangulated_out) memcpy(triangulated_out, o + (L.tri - L.res), (size_t)n);
+    memcpy(result, o + L.res, sizeof *result);
+    if (pts3d_out) memcpy(pts3d_out, o + L.pts3d, (size_t)n * 24);
+    if (triangulated_out) memcpy(triangulated_out, o + L.tri, (size_t)n);
     return YGZ_OK;
 }
 
@@ -883,13 +879,13 @@ int ygz_hip_init_hypotheses(ygz_hip_ctx *ctx, const double *px1, const double *p
     const int rc = run(ctx, px1, px2, n, nullptr, params, RUN_HYP, 0, nullptr, nullptr, &o, &L);
     if (rc != YGZ_OK) return rc;
     const int it = params ? params->max_iter : 200;
-    memcpy(result, o, sizeof *result);
-    if (H21) memcpy(H21, o + (L.H21 - L.res), (size_t)it * 72);
-    if (F21) memcpy(F21, o + (L.F21 - L.res), (size_t)it * 72);
-    if (score_h) memcpy(score_h, o + (L.score_h - L.res), (size_t)it * 4);
-    if (score_f) memcpy(score_f, o + (L.score_f - L.res), (size_t)it * 4);
-    if (inliers_h) memcpy(inliers_h, o + (L.inl_h - L.res), (size_t)n);
-    if (inliers_f) memcpy(inliers_f, o + (L.inl_f - L.res), (size_t)n);
+    memcpy(result, o + L.res, sizeof *result);
+    if (H21) memcpy(H21, o + L.H21, (size_t)it * 72);
+    if (F21) memcpy(F21, o + L.F21, (size_t)it * 72);
+    if (score_h) memcpy(score_h, o + L.score_h, (size_t)it * 4);
+    if (score_f) memcpy(score_f, o + L.score_f, (size_t)it * 4);
+    if (inliers_h) memcpy(inliers_h, o + L.inl_h, (size_t)n);
+    if (inliers_f) memcpy(inliers_f, o + L.inl_f, (size_t)n);
     return YGZ_OK;
 }
 
@@ -902,9 +898,9 @@ int ygz_hip_init_reconstruct(ygz_hip_ctx *ctx, const double *px1, const double *
     Layout L;
     const int rc = run(ctx, px1, px2, n, K4, params, RUN_REC, model, M, inliers, &o, &L);
     if (rc != YGZ_OK) return rc;
-    memcpy(result, o, sizeof *result);
-    if (pts3d_out) memcpy(pts3d_out, o + (L.pts3d - L.res), (size_t)n * 24);
-    if (triangulated_out) memcpy(triangulated_out, o + (L.tri - L.res), (size_t)n);
+    memcpy(result, o + L.res, sizeof *result);
+    if (pts3d_out) memcpy(pts3d_out, o + L.pts3d, (size_t)n * 24);
+    if (triangulated_out) memcpy(triangulated_out, o + L.tri, (size_t)n);
     return YGZ_OK;
 }
 

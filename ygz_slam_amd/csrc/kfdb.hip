@@ -96,7 +96,6 @@ __global__ __launch_bounds__(KFDB_LANES) void k_kfdb_query(int n_entries, const 
     }
 }
 
-size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
 size_t row_units(int n) { return (size_t)n + ((size_t)n + 1) / 2; }
 
 // words >= 0 and strictly ascending, weights finite and > 0
@@ -229,37 +228,27 @@ int ygz_hip_kfdb_query(ygz_kfdb *db, int n_queries, const int32_t *q_offsets, co
     { int rj_ = ygz_join(ctx); if (rj_ != YGZ_OK) return rj_; }
     const size_t Q = (size_t)n_queries, W = (size_t)q_offsets[n_queries], E = db->rows.size();
     // [offsets | rows | weights | words) goes up, [score | common) comes back
-    size_t o = 0;
-    const size_t o_off = o; o = al(o + (Q + 1) * 4);
-    const size_t o_rows = o; o = al(o + E * 8);
-    const size_t o_wt = o; o = al(o + W * 8);
-    const size_t o_wd = o; o = al(o + W * 4);
-    const size_t in_end = o;
-    const size_t o_score = o; o = al(o + Q * E * 8);
-    const size_t o_common = o; o = al(o + Q * E * 4);
-    const size_t total = o;
-    uint8_t *dev = nullptr;
-    const int rc = ygz_scratch(ctx, SCR_GEN_0 + 18, total, (void **)&dev);
+    YgzBlobLayout L;
+    const size_t o_off = L.add_n<int32_t>(Q + 1), o_rows = L.add_n<int2>(E), o_wt = L.add_n<double>(W), o_wd = L.add_n<int32_t>(W), in_end = L.end;
+    const size_t o_score = L.add_n<double>(Q * E), o_common = L.add_n<int32_t>(Q * E), total = L.end;
+    YgzBlob b;
+    int rc = ygz_blob_open(ctx, SCR_KFDB, total, total, &b);
     if (rc != YGZ_OK) return rc;
-    uint8_t *up = (uint8_t *)ygz_stage(ctx, total);
-    if (!up) return YGZ_E_HIP;
-    memcpy(up + o_off, q_offsets, (Q + 1) * 4);
-    memcpy(up + o_rows, db->rows.data(), E * 8);
-    memcpy(up + o_wt, q_weight, W * 8);
-    memcpy(up + o_wd, q_word, W * 4);
-    YGZ_HIPCHK(ctx, hipMemcpyAsync(dev, up, in_end, hipMemcpyHostToDevice, ctx->stream));
+    memcpy(b.host + o_off, q_offsets, (Q + 1) * 4);
+    memcpy(b.host + o_rows, db->rows.data(), E * 8);
+    memcpy(b.host + o_wt, q_weight, W * 8);
+    memcpy(b.host + o_wd, q_word, W * 4);
+    if ((rc = ygz_blob_upload(ctx, b, in_end)) != YGZ_OK) return rc;
     const int per_query = KFDB_BLOCKS / n_queries > 1 ? KFDB_BLOCKS / n_queries : 1;
     const int need = ygz_div_up((int)E, KFDB_WAVES);
     const dim3 grid((unsigned)(need < per_query ? need : per_query), (unsigned)n_queries);
     // a database whose rows are all empty has no pool: the kernel then reads no row
-    YGZ_LAUNCH(ctx, KID_COUNT, k_kfdb_query, grid, dim3(KFDB_LANES), (int)E, (const int2 *)(dev + o_rows), (const double *)db->pool,
-               (const int32_t *)(dev + o_off), (const int32_t *)(dev + o_wd), (const double *)(dev + o_wt), (int32_t *)(dev + o_common),
-               (double *)(dev + o_score));
-    YGZ_HIPCHK(ctx, hipGetLastError());
-    YGZ_HIPCHK(ctx, hipMemcpyAsync(up + o_score, dev + o_score, total - o_score, hipMemcpyDeviceToHost, ctx->stream));
-    YGZ_HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    memcpy(score, up + o_score, Q * E * 8);
-    memcpy(common, up + o_common, Q * E * 4);
+    YGZ_LAUNCH(ctx, KID_COUNT, k_kfdb_query, grid, dim3(KFDB_LANES), (int)E, ygz_at<const int2>(b.dev, o_rows), (const double *)db->pool,
+               ygz_at<const int32_t>(b.dev, o_off), ygz_at<const int32_t>(b.dev, o_wd), ygz_at<const double>(b.dev, o_wt),
+               ygz_at<int32_t>(b.dev, o_common), ygz_at<double>(b.dev, o_score));
+    if ((rc = ygz_blob_fetch(ctx, b, o_score, total)) != YGZ_OK) return rc;
+    memcpy(score, b.host + o_score, Q * E * 8);
+    memcpy(common, b.host + o_common, Q * E * 4);
     return YGZ_OK;
 }
 

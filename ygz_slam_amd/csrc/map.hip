@@ -59,8 +59,6 @@ __global__ __launch_bounds__(MAP_LANES) void k_map_covis(int n_obs, int K, const
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------------
-size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // offsets [n_points + 1]: starts at 0, never decreases; *n_obs = its last entry.  per_point > 0: no point holds more
 int check_offsets(int n_points, const int32_t *offsets, int per_point, int *n_obs)
 {
@@ -99,28 +97,20 @@ int ygz_hip_distinctive_descriptors(ygz_hip_ctx *ctx, int n_points, const int32_
         YgzDeviceGuard dg_(ctx);
         { int rj_ = ygz_join(ctx); if (rj_ != YGZ_OK) return rj_; }
         // [offsets | owner | desc | keys) goes up, [keys) comes back
-        size_t o = 0;
-        const size_t o_off = o; o = al(o + (P + 1) * 4);
-        const size_t o_own = o; o = al(o + N * 4);
-        const size_t o_desc = o; o = al(o + N * 32);
-        const size_t o_keys = o; o = al(o + P * 4);
-        const size_t total = o;
-        uint8_t *dev = nullptr;
-        int rc = ygz_scratch(ctx, SCR_GEN_0 + 16, total, (void **)&dev);
+        YgzBlobLayout L;
+        const size_t o_off = L.add_n<int32_t>(P + 1), o_own = L.add_n<int32_t>(N), o_desc = L.add_n<uint32_t>(N * 8), o_keys = L.add_n<uint32_t>(P);
+        YgzBlob b;
+        int rc = ygz_blob_open(ctx, SCR_MAP, L.end, L.end, &b);
         if (rc != YGZ_OK) return rc;
-        uint8_t *up = (uint8_t *)ygz_stage(ctx, total);
-        if (!up) return YGZ_E_HIP;
-        memcpy(up + o_off, offsets, (P + 1) * 4);
-        fill_owner(n_points, offsets, (int32_t *)(up + o_own));
-        memcpy(up + o_desc, desc, N * 32);
-        memset(up + o_keys, 0xFF, P * 4);
-        YGZ_HIPCHK(ctx, hipMemcpyAsync(dev, up, total, hipMemcpyHostToDevice, ctx->stream));
-        YGZ_LAUNCH(ctx, KID_COUNT, k_map_median, dim3(ygz_div_up(n_obs, MAP_LANES)), dim3(MAP_LANES), n_obs, (const int32_t *)(dev + o_off),
-                   (const int32_t *)(dev + o_own), (const uint32_t *)(dev + o_desc), (uint32_t *)(dev + o_keys));
-        YGZ_HIPCHK(ctx, hipGetLastError());
-        YGZ_HIPCHK(ctx, hipMemcpyAsync(up + o_keys, dev + o_keys, P * 4, hipMemcpyDeviceToHost, ctx->stream));
-        YGZ_HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        keys = (const uint32_t *)(up + o_keys);
+        memcpy(b.host + o_off, offsets, (P + 1) * 4);
+        fill_owner(n_points, offsets, ygz_at<int32_t>(b.host, o_own));
+        memcpy(b.host + o_desc, desc, N * 32);
+        memset(b.host + o_keys, 0xFF, P * 4);
+        if ((rc = ygz_blob_upload(ctx, b, L.end)) != YGZ_OK) return rc;
+        YGZ_LAUNCH(ctx, KID_COUNT, k_map_median, dim3(ygz_div_up(n_obs, MAP_LANES)), dim3(MAP_LANES), n_obs, ygz_at<const int32_t>(b.dev, o_off),
+                   ygz_at<const int32_t>(b.dev, o_own), ygz_at<const uint32_t>(b.dev, o_desc), ygz_at<uint32_t>(b.dev, o_keys));
+        if ((rc = ygz_blob_fetch(ctx, b, o_keys, o_keys + P * 4)) != YGZ_OK) return rc;
+        keys = ygz_at<const uint32_t>(b.host, o_keys);
     }
     // the key names the observation; its 32 bytes are the caller's own
     for (int p = 0; p < n_points; ++p) {
@@ -159,31 +149,23 @@ int ygz_hip_covisibility(ygz_hip_ctx *ctx, int n_points, const int32_t *offsets,
     YgzDeviceGuard dg_(ctx);
     { int rj_ = ygz_join(ctx); if (rj_ != YGZ_OK) return rj_; }
     // [offsets | owner | kf | row_of) goes up, [weights) comes back
-    size_t o = 0;
-    const size_t o_off = o; o = al(o + (P + 1) * 4);
-    const size_t o_own = o; o = al(o + N * 4);
-    const size_t o_kf = o; o = al(o + N * 4);
-    const size_t o_row = o; o = al(o + K * 4);
-    const size_t in_end = o;
-    const size_t o_w = o; o = al(o + W);
-    const size_t total = o;
-    uint8_t *dev = nullptr;
-    int rc = ygz_scratch(ctx, SCR_GEN_0 + 16, total, (void **)&dev);
+    YgzBlobLayout L;
+    const size_t o_off = L.add_n<int32_t>(P + 1), o_own = L.add_n<int32_t>(N), o_kf = L.add_n<int32_t>(N), o_row = L.add_n<int32_t>(K), in_end = L.end;
+    const size_t o_w = L.add(W);
+    YgzBlob b;
+    int rc = ygz_blob_open(ctx, SCR_MAP, L.end, L.end, &b);
     if (rc != YGZ_OK) return rc;
-    uint8_t *up = (uint8_t *)ygz_stage(ctx, total);
-    if (!up) return YGZ_E_HIP;
-    memcpy(up + o_off, offsets, (P + 1) * 4);
-    fill_owner(n_points, offsets, (int32_t *)(up + o_own));
-    memcpy(up + o_kf, kf, N * 4);
-    memcpy(up + o_row, row_of.data(), K * 4);
-    YGZ_HIPCHK(ctx, hipMemcpyAsync(dev, up, in_end, hipMemcpyHostToDevice, ctx->stream));
-    YGZ_HIPCHK(ctx, hipMemsetAsync(dev + o_w, 0, W, ctx->stream));
-    YGZ_LAUNCH(ctx, KID_COUNT, k_map_covis, dim3(ygz_div_up(n_obs, MAP_LANES)), dim3(MAP_LANES), n_obs, n_keyframes, (const int32_t *)(dev + o_off),
-               (const int32_t *)(dev + o_own), (const int32_t *)(dev + o_kf), (const int32_t *)(dev + o_row), (int32_t *)(dev + o_w));
-    YGZ_HIPCHK(ctx, hipGetLastError());
-    YGZ_HIPCHK(ctx, hipMemcpyAsync(up + o_w, dev + o_w, W, hipMemcpyDeviceToHost, ctx->stream));
-    YGZ_HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    memcpy(weights, up + o_w, W);
+    memcpy(b.host + o_off, offsets, (P + 1) * 4);
+    fill_owner(n_points, offsets, ygz_at<int32_t>(b.host, o_own));
+    memcpy(b.host + o_kf, kf, N * 4);
+    memcpy(b.host + o_row, row_of.data(), K * 4);
+    if ((rc = ygz_blob_upload(ctx, b, in_end)) != YGZ_OK) return rc;
+    YGZ_HIPCHK(ctx, hipMemsetAsync(b.dev + o_w, 0, W, ctx->stream));
+    YGZ_LAUNCH(ctx, KID_COUNT, k_map_covis, dim3(ygz_div_up(n_obs, MAP_LANES)), dim3(MAP_LANES), n_obs, n_keyframes,
+               ygz_at<const int32_t>(b.dev, o_off), ygz_at<const int32_t>(b.dev, o_own), ygz_at<const int32_t>(b.dev, o_kf),
+               ygz_at<const int32_t>(b.dev, o_row), ygz_at<int32_t>(b.dev, o_w));
+    if ((rc = ygz_blob_fetch(ctx, b, o_w, o_w + W)) != YGZ_OK) return rc;
+    memcpy(weights, b.host + o_w, W);
     return YGZ_OK;
 }
 

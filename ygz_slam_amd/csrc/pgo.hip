@@ -583,8 +583,6 @@ __global__ __launch_bounds__(PGO_LANES) void k_pgo_optimize(PgoDev D)
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------------
-size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
-
 bool finite8(const double *v)
 {
     for (int k = 0; k < 8; ++k) if (!(std::fabs(v[k]) <= PG_DMAX)) return false;
@@ -628,33 +626,33 @@ struct Layout {
 Layout layout(size_t N, size_t E)
 {
     Layout L;
-    size_t o = 0;
-    L.in = o; o = al(o + sizeof(PgoIn));
-    L.s0 = o; o = al(o + N * 64);
-    L.fixed = o; o = al(o + N);
-    L.edges = o; o = al(o + E * 8);
-    L.m = o; o = al(o + E * 64);
-    L.adj_off = o; o = al(o + (N + 1) * 4);
-    L.adj = o; o = al(o + E * 8);
-    L.in_end = o;
-    L.out = o; o = al(o + sizeof(ygz_pgo_result));
-    L.s = o; o = al(o + N * 64);
-    L.out_end = o;
-    L.res = o; o = al(o + E * 56);
-    L.ji = o; o = al(o + E * 392);
-    L.jj = o; o = al(o + E * 392);
-    L.stage_end = o;
-    L.sn = o; o = al(o + N * 64);
-    L.dg = o; o = al(o + N * 224);
-    L.lf = o; o = al(o + N * 224);
-    L.vec = o; o = al(o + 6 * al(N * 56));
-    L.w = o; o = al(o + E * 56);
-    L.total = o;
+    YgzBlobLayout B;
+    L.in = B.add(sizeof(PgoIn));
+    L.s0 = B.add_n<double>(N * 8);
+    L.fixed = B.add(N);
+    L.edges = B.add_n<int32_t>(E * 2);
+    L.m = B.add_n<double>(E * 8);
+    L.adj_off = B.add_n<int32_t>(N + 1);
+    L.adj = B.add_n<int32_t>(E * 2);
+    L.in_end = B.end;
+    L.out = B.add(sizeof(ygz_pgo_result));
+    L.s = B.add_n<double>(N * 8);
+    L.out_end = B.end;
+    L.res = B.add_n<double>(E * 7);
+    L.ji = B.add_n<double>(E * 49);
+    L.jj = B.add_n<double>(E * 49);
+    L.stage_end = B.end;
+    L.sn = B.add_n<double>(N * 8);
+    L.dg = B.add_n<double>(N * 28);
+    L.lf = B.add_n<double>(N * 28);
+    L.vec = B.add(6 * ygz_round_up_256(N * 56));             // b, x, r, z, p, q: [N][7] each, 256-aligned
+    L.w = B.add_n<double>(E * 7);
+    L.total = B.end;
     return L;
 }
 
 // validation, the adjacency, one upload, the launch, one copy back of [out, out_end) (stage = false) or of [out, stage_end), one wait; `down`
-// receives the page-locked copy
+// receives the page-locked image of the block
 int run(ygz_hip_ctx *ctx, int n, const double *S, const uint8_t *fixed, int ne, const int32_t *edges, const double *M,
         const ygz_pgo_params *params, bool stage, uint8_t **down, Layout *Lout)
 {
@@ -666,12 +664,11 @@ int run(ygz_hip_ctx *ctx, int n, const double *S, const uint8_t *fixed, int ne, 
     { int rj_ = ygz_join(ctx); if (rj_ != YGZ_OK) return rj_; }
     const size_t N = (size_t)n, E = (size_t)ne;
     const Layout L = layout(N, E);
-    uint8_t *dev = nullptr;
-    int rc = ygz_scratch(ctx, SCR_GEN_0 + 15, L.total, (void **)&dev);
+    const size_t down_end = stage ? L.stage_end : L.out_end;  // [0, in_end) goes up, [out, down_end) comes back
+    YgzBlob b;
+    int rc = ygz_blob_open(ctx, SCR_PGO, L.total, down_end, &b);
     if (rc != YGZ_OK) return rc;
-    const size_t down_end = stage ? L.stage_end : L.out_end;
-    uint8_t *up = (uint8_t *)ygz_stage(ctx, down_end);        // one page-locked block: [0, in_end) goes up, [out, down_end) comes back
-    if (!up) return YGZ_E_HIP;
+    uint8_t *up = b.host, *dev = b.dev;
     PgoIn in;
     memset(&in, 0, sizeof in);
     int n_free = 0;
@@ -685,29 +682,27 @@ int run(ygz_hip_ctx *ctx, int n, const double *S, const uint8_t *fixed, int ne, 
     memcpy(up + L.edges, edges, E * 8);
     memcpy(up + L.m, M, E * 64);
     // the CSR adjacency (pg_adjacency): per vertex its edges in edge-index order
-    int32_t *adj_off = (int32_t *)(up + L.adj_off), *adj = (int32_t *)(up + L.adj);
+    int32_t *adj_off = ygz_at<int32_t>(up, L.adj_off), *adj = ygz_at<int32_t>(up, L.adj);
     for (int v = 0; v <= n; ++v) adj_off[v] = 0;
     for (int e = 0; e < ne; ++e) { ++adj_off[edges[2 * e] + 1]; ++adj_off[edges[2 * e + 1] + 1]; }
     for (int v = 0; v < n; ++v) adj_off[v + 1] += adj_off[v];
     std::vector<int32_t> fill(adj_off, adj_off + n);
     for (int e = 0; e < ne; ++e) { adj[fill[edges[2 * e]]++] = 2 * e; adj[fill[edges[2 * e + 1]]++] = 2 * e + 1; }
-    YGZ_HIPCHK(ctx, hipMemcpyAsync(dev, up, L.in_end, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = ygz_blob_upload(ctx, b, L.in_end)) != YGZ_OK) return rc;
     PgoDev D;
-    D.in = (const PgoIn *)(dev + L.in); D.S0 = (const double *)(dev + L.s0); D.fixed = dev + L.fixed;
-    D.edges = (const int32_t *)(dev + L.edges); D.M = (const double *)(dev + L.m);
-    D.adj_off = (const int32_t *)(dev + L.adj_off); D.adj = (const int32_t *)(dev + L.adj);
-    D.out = (ygz_pgo_result *)(dev + L.out); D.S = (double *)(dev + L.s);
-    D.res = (double *)(dev + L.res); D.Ji = (double *)(dev + L.ji); D.Jj = (double *)(dev + L.jj);
-    D.Sn = (double *)(dev + L.sn); D.Dg = (double *)(dev + L.dg); D.Lf = (double *)(dev + L.lf);
-    const size_t vs = al(N * 56);
-    D.b = (double *)(dev + L.vec); D.x = (double *)(dev + L.vec + vs); D.r = (double *)(dev + L.vec + 2 * vs);
-    D.z = (double *)(dev + L.vec + 3 * vs); D.p = (double *)(dev + L.vec + 4 * vs); D.q = (double *)(dev + L.vec + 5 * vs);
-    D.w = (double *)(dev + L.w);
+    D.in = ygz_at<const PgoIn>(dev, L.in); D.S0 = ygz_at<const double>(dev, L.s0); D.fixed = dev + L.fixed;
+    D.edges = ygz_at<const int32_t>(dev, L.edges); D.M = ygz_at<const double>(dev, L.m);
+    D.adj_off = ygz_at<const int32_t>(dev, L.adj_off); D.adj = ygz_at<const int32_t>(dev, L.adj);
+    D.out = ygz_at<ygz_pgo_result>(dev, L.out); D.S = ygz_at<double>(dev, L.s);
+    D.res = ygz_at<double>(dev, L.res); D.Ji = ygz_at<double>(dev, L.ji); D.Jj = ygz_at<double>(dev, L.jj);
+    D.Sn = ygz_at<double>(dev, L.sn); D.Dg = ygz_at<double>(dev, L.dg); D.Lf = ygz_at<double>(dev, L.lf);
+    const size_t vs = ygz_round_up_256(N * 56);
+    D.b = ygz_at<double>(dev, L.vec); D.x = ygz_at<double>(dev, L.vec + vs); D.r = ygz_at<double>(dev, L.vec + 2 * vs);
+    D.z = ygz_at<double>(dev, L.vec + 3 * vs); D.p = ygz_at<double>(dev, L.vec + 4 * vs); D.q = ygz_at<double>(dev, L.vec + 5 * vs);
+    D.w = ygz_at<double>(dev, L.w);
     YGZ_LAUNCH(ctx, KID_COUNT, k_pgo_optimize, dim3(1), dim3(PGO_LANES), D);
-    YGZ_HIPCHK(ctx, hipGetLastError());
-    YGZ_HIPCHK(ctx, hipMemcpyAsync(up + L.out, dev + L.out, down_end - L.out, hipMemcpyDeviceToHost, ctx->stream));
-    YGZ_HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    *down = up + L.out;
+    if ((rc = ygz_blob_fetch(ctx, b, L.out, down_end)) != YGZ_OK) return rc;
+    *down = up;
     *Lout = L;
     return YGZ_OK;
 }
@@ -731,8 +726,8 @@ int ygz_hip_pose_graph_optimize(ygz_hip_ctx *ctx, int n_vertices, const double *
     Layout L;
     const int rc = run(ctx, n_vertices, S, fixed, n_edges, edges, M, params, false, &o, &L);
     if (rc != YGZ_OK) return rc;
-    memcpy(result, o, sizeof(ygz_pgo_result));
-    memcpy(S_out, result->status == YGZ_PGO_FAILED ? (const void *)S : (const void *)(o + (L.s - L.out)), (size_t)n_vertices * 64);
+    memcpy(result, o + L.out, sizeof(ygz_pgo_result));
+    memcpy(S_out, result->status == YGZ_PGO_FAILED ? (const void *)S : (const void *)(o + L.s), (size_t)n_vertices * 64);
     return YGZ_OK;
 }
 
@@ -743,11 +738,11 @@ int ygz_hip_pgo_linearize(ygz_hip_ctx *ctx, int n_vertices, const double *S, con
     Layout L;
     const int rc = run(ctx, n_vertices, S, fixed, n_edges, edges, M, params, true, &o, &L);
     if (rc != YGZ_OK) return rc;
-    const ygz_pgo_result *r = (const ygz_pgo_result *)o;
+    const ygz_pgo_result *r = ygz_at<const ygz_pgo_result>(o, L.out);
     const size_t E = (size_t)n_edges;
-    if (residuals) memcpy(residuals, o + (L.res - L.out), E * 56);
-    if (Ji) memcpy(Ji, o + (L.ji - L.out), E * 392);
-    if (Jj) memcpy(Jj, o + (L.jj - L.out), E * 392);
+    if (residuals) memcpy(residuals, o + L.res, E * 56);
+    if (Ji) memcpy(Ji, o + L.ji, E * 392);
+    if (Jj) memcpy(Jj, o + L.jj, E * 392);
     if (cost) *cost = r->cost_initial;
     return r->status == YGZ_PGO_FAILED ? YGZ_E_STATE : YGZ_OK;
 }

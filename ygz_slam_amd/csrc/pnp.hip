@@ -405,8 +405,7 @@ __global__ __launch_bounds__(PNP_SEL_THREADS) void k_pnp_select(PnpDev D)
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------------
-size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
-
+static_assert(sizeof(PnpIn) == 56 && sizeof(ygz_pnp_result) == 176, "tests/cpp/blob_layout_host.cpp restates the block with these sizes");
 struct Layout {
     size_t in, off, pw, px, sets, in_end;                    // the upload
     size_t res, mask, res_end, nsol, counts, sol, total;     // the copy back: [res, res_end) or [res, total)
@@ -414,25 +413,26 @@ struct Layout {
 Layout layout(int P, size_t N, int it)
 {
     Layout L;
-    size_t o = 0;
-    L.in = o; o = al(o + sizeof(PnpIn));
-    L.off = o; o = al(o + (size_t)(P + 1) * 4);
-    L.pw = o; o = al(o + N * 24);
-    L.px = o; o = al(o + N * 16);
-    L.sets = o; o = al(o + (size_t)P * it * 12);
-    L.in_end = o;
-    L.res = o; o = al(o + (size_t)P * sizeof(ygz_pnp_result));
-    L.mask = o; o = al(o + N);
-    L.res_end = o;
-    L.nsol = o; o = al(o + (size_t)P * it * 4);
-    L.counts = o; o = al(o + (size_t)P * it * 16);
-    L.sol = o; o = al(o + (size_t)P * it * 4 * 12 * 8);
-    L.total = o;
+    YgzBlobLayout B;
+    const size_t H = (size_t)P * it;                         // hypothesis sets
+    L.in = B.add(sizeof(PnpIn));
+    L.off = B.add_n<int32_t>((size_t)P + 1);
+    L.pw = B.add_n<double>(N * 3);
+    L.px = B.add_n<double>(N * 2);
+    L.sets = B.add_n<int32_t>(H * 3);
+    L.in_end = B.end;
+    L.res = B.add_n<ygz_pnp_result>((size_t)P);
+    L.mask = B.add(N);
+    L.res_end = B.end;
+    L.nsol = B.add_n<int32_t>(H);
+    L.counts = B.add_n<int32_t>(H * 4);
+    L.sol = B.add_n<double>(H * 4 * 12);
+    L.total = B.end;
     return L;
 }
 
 // validation (before anything touches the device), one upload, the three launches, one copy back of [res, res_end) (all = false) or of
-// [res, total), one wait; `out` receives the page-locked copy
+// [res, total), one wait; `out` receives the page-locked image of the block
 int run(ygz_hip_ctx *ctx, int P, const int32_t *offsets, const double *pw, const double *px, const double *K4, const ygz_pnp_params *params,
         bool all, uint8_t **out, Layout *Lout)
 {
@@ -454,12 +454,11 @@ int run(ygz_hip_ctx *ctx, int P, const int32_t *offsets, const double *pw, const
     const int it = p.max_iter;
     const size_t N = (size_t)offsets[P];
     const Layout L = layout(P, N, it);
-    uint8_t *dev = nullptr;
-    int rc = ygz_scratch(ctx, SCR_GEN_0 + 12, L.total, (void **)&dev);
+    const size_t down_end = all ? L.total : L.res_end;       // [0, in_end) goes up, [res, down_end) comes back
+    YgzBlob b;
+    int rc = ygz_blob_open(ctx, SCR_PNP, L.total, down_end, &b);
     if (rc != YGZ_OK) return rc;
-    const size_t down_end = all ? L.total : L.res_end;
-    uint8_t *up = (uint8_t *)ygz_stage(ctx, down_end);        // one page-locked block: [0, in_end) goes up, [res, down_end) comes back
-    if (!up) return YGZ_E_HIP;
+    uint8_t *up = b.host, *dev = b.dev;
     PnpIn in;
     memset(&in, 0, sizeof in);
     for (int k = 0; k < 4; ++k) in.K4[k] = K4[k];
@@ -470,20 +469,17 @@ int run(ygz_hip_ctx *ctx, int P, const int32_t *offsets, const double *pw, const
     memcpy(up + L.px, px, N * 16);
     for (int q = 0; q < P; ++q)
         memcpy(up + L.sets + (size_t)q * it * 12, ygz_cvrng_cached_sets(offsets[q + 1] - offsets[q], it, 3).data(), (size_t)it * 12);
-    YGZ_HIPCHK(ctx, hipMemcpyAsync(dev, up, L.in_end, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = ygz_blob_upload(ctx, b, L.in_end)) != YGZ_OK) return rc;
     PnpDev D;
-    D.in = (const PnpIn *)(dev + L.in); D.off = (const int32_t *)(dev + L.off); D.pw = (const double *)(dev + L.pw);
-    D.px = (const double *)(dev + L.px); D.sets = (const int32_t *)(dev + L.sets);
-    D.res = (ygz_pnp_result *)(dev + L.res); D.mask = dev + L.mask; D.nsol = (int32_t *)(dev + L.nsol); D.counts = (int32_t *)(dev + L.counts);
-    D.sol = (double *)(dev + L.sol);
+    D.in = ygz_at<const PnpIn>(dev, L.in); D.off = ygz_at<const int32_t>(dev, L.off); D.pw = ygz_at<const double>(dev, L.pw);
+    D.px = ygz_at<const double>(dev, L.px); D.sets = ygz_at<const int32_t>(dev, L.sets);
+    D.res = ygz_at<ygz_pnp_result>(dev, L.res); D.mask = dev + L.mask; D.nsol = ygz_at<int32_t>(dev, L.nsol);
+    D.counts = ygz_at<int32_t>(dev, L.counts); D.sol = ygz_at<double>(dev, L.sol);
     YGZ_LAUNCH(ctx, KID_COUNT, k_pnp_solve, dim3(ygz_div_up(it, PNP_SOLVE_LANES), P), dim3(PNP_SOLVE_LANES), D);
     YGZ_LAUNCH(ctx, KID_COUNT, k_pnp_score, dim3(ygz_div_up(4 * it, PNP_SCORE_LANES), P), dim3(PNP_SCORE_LANES), D);
     YGZ_LAUNCH(ctx, KID_COUNT, k_pnp_select, dim3(P), dim3(PNP_SEL_THREADS), D);
-    YGZ_HIPCHK(ctx, hipGetLastError());
-    uint8_t *down = up + L.res;
-    YGZ_HIPCHK(ctx, hipMemcpyAsync(down, dev + L.res, down_end - L.res, hipMemcpyDeviceToHost, ctx->stream));
-    YGZ_HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    *out = down;
+    if ((rc = ygz_blob_fetch(ctx, b, L.res, down_end)) != YGZ_OK) return rc;
+    *out = up;
     *Lout = L;
     return YGZ_OK;
 }
@@ -513,8 +509,8 @@ int ygz_hip_pnp_ransac(ygz_hip_ctx *ctx, int n_problems, const int32_t *offsets,
     Layout L;
     const int rc = run(ctx, n_problems, offsets, pw, px, K4, params, false, &o, &L);
     if (rc != YGZ_OK) return rc;
-    memcpy(results, o, (size_t)n_problems * sizeof(ygz_pnp_result));
-    if (inliers) memcpy(inliers, o + (L.mask - L.res), (size_t)offsets[n_problems]);
+    memcpy(results, o + L.res, (size_t)n_problems * sizeof(ygz_pnp_result));
+    if (inliers) memcpy(inliers, o + L.mask, (size_t)offsets[n_problems]);
     return YGZ_OK;
 }
 
@@ -527,9 +523,9 @@ int ygz_hip_pnp_hypotheses(ygz_hip_ctx *ctx, const double *pw, const double *px,
     const int rc = run(ctx, 1, off, pw, px, K4, params, true, &o, &L);
     if (rc != YGZ_OK) return rc;
     const int it = params ? params->max_iter : 300;
-    if (solutions) memcpy(solutions, o + (L.sol - L.res), (size_t)it * 4 * 12 * 8);
-    if (n_solutions) memcpy(n_solutions, o + (L.nsol - L.res), (size_t)it * 4);
-    if (counts) memcpy(counts, o + (L.counts - L.res), (size_t)it * 16);
+    if (solutions) memcpy(solutions, o + L.sol, (size_t)it * 4 * 12 * 8);
+    if (n_solutions) memcpy(n_solutions, o + L.nsol, (size_t)it * 4);
+    if (counts) memcpy(counts, o + L.counts, (size_t)it * 16);
     return YGZ_OK;
 }
 

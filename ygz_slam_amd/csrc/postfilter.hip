@@ -218,7 +218,7 @@ static int run_check(ygz_hip_ctx *ctx, const uint32_t *d1, int n1, const uint32_
 {
     uint8_t *buf = nullptr;
     const size_t N = (size_t)n, off_i2 = N * 4, off_d = 2 * N * 4, off_k = 3 * N * 4, off_o = (off_k + N + 15) & ~(size_t)15;
-    int rc = ygz_scratch(ctx, SCR_GEN_0 + 1, off_o + 64, (void **)&buf);
+    int rc = ygz_scratch(ctx, SCR_GEN_1, off_o + 64, (void **)&buf);
     if (rc != YGZ_OK) return rc;
     if (h_i1) YGZ_HIPCHK(ctx, hipMemcpyAsync(buf, h_i1, N * 4, hipMemcpyHostToDevice, ctx->stream));
     if (h_i2) YGZ_HIPCHK(ctx, hipMemcpyAsync(buf + off_i2, h_i2, N * 4, hipMemcpyHostToDevice, ctx->stream));

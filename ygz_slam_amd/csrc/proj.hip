@@ -131,8 +131,6 @@ __global__ __launch_bounds__(PROJ_LANES) void k_proj_search(const ProjIn *__rest
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------------
-size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct Out { const uint32_t *keys; const int32_t *n_cand, *pred; };
 
 // validation (before anything touches the device), one upload, the launch, one copy back, one wait; `out` points into the page-locked copy
@@ -161,36 +159,31 @@ int run(ygz_hip_ctx *ctx, int P, const ygz_proj_problem *pb, const double *K4, c
     { int rj_ = ygz_join(ctx); if (rj_ != YGZ_OK) return rj_; }
 
     // the layout: [in | problems | every problem's arrays) goes up, [keys | n_cand | pred) comes back
-    size_t o = 0;
-    const size_t o_in = o; o = al(o + sizeof(ProjIn));
-    const size_t o_pb = o; o = al(o + (size_t)P * sizeof(ProjProbDev));
+    YgzBlobLayout B;
+    const size_t o_in = B.add(sizeof(ProjIn)), o_pb = B.add_n<ProjProbDev>((size_t)P);
     struct Offs { size_t kp_px, kp_level, kp_desc, kp_taken, pw, pt_desc, pt_dmax, pt_normal, pt_skip; };
     Offs of[YGZ_PROJ_MAX_PROBLEMS];
     int max_pt = 0;
     for (int q = 0; q < P; ++q) {
         const ygz_proj_problem &b = pb[q];
         const size_t nk = (size_t)b.n_kp, np = (size_t)b.n_pt;
-        of[q].kp_px = o; o = al(o + nk * 16);
-        of[q].kp_level = o; o = al(o + nk * 4);
-        of[q].kp_desc = o; o = al(o + nk * 32);
-        of[q].kp_taken = o; if (b.kp_taken) o = al(o + nk);
-        of[q].pw = o; o = al(o + np * 24);
-        of[q].pt_desc = o; o = al(o + np * 32);
-        of[q].pt_dmax = o; o = al(o + np * 8);
-        of[q].pt_normal = o; if (b.pt_normal) o = al(o + np * 24);
-        of[q].pt_skip = o; if (b.pt_skip) o = al(o + np);
+        of[q].kp_px = B.add_n<double>(nk * 2);
+        of[q].kp_level = B.add_n<int32_t>(nk);
+        of[q].kp_desc = B.add_n<uint32_t>(nk * 8);
+        of[q].kp_taken = B.add(b.kp_taken ? nk : 0);         // the optional arrays take no room when absent
+        of[q].pw = B.add_n<double>(np * 3);
+        of[q].pt_desc = B.add_n<uint32_t>(np * 8);
+        of[q].pt_dmax = B.add_n<double>(np);
+        of[q].pt_normal = B.add_n<double>(b.pt_normal ? np * 3 : 0);
+        of[q].pt_skip = B.add(b.pt_skip ? np : 0);
         if (b.n_pt > max_pt) max_pt = b.n_pt;
     }
-    const size_t in_end = o;
-    const size_t o_keys = o; o = al(o + N * YGZ_PROJ_TOPK * 4);
-    const size_t o_nc = o; o = al(o + N * 4);
-    const size_t o_pred = o; o = al(o + N * 4);
-    const size_t total = o;
-    uint8_t *dev = nullptr;
-    int rc = ygz_scratch(ctx, SCR_GEN_0 + 14, total, (void **)&dev);
+    const size_t in_end = B.end;
+    const size_t o_keys = B.add_n<uint32_t>(N * YGZ_PROJ_TOPK), o_nc = B.add_n<int32_t>(N), o_pred = B.add_n<int32_t>(N), total = B.end;
+    YgzBlob blob;                                           // [0, in_end) goes up, [keys, total) comes back
+    int rc = ygz_blob_open(ctx, SCR_PROJ, total, total, &blob);
     if (rc != YGZ_OK) return rc;
-    uint8_t *up = (uint8_t *)ygz_stage(ctx, total);         // one page-locked block: [0, in_end) goes up, [keys, total) comes back
-    if (!up) return YGZ_E_HIP;
+    uint8_t *up = blob.host, *dev = blob.dev;
     ProjIn in;
     memset(&in, 0, sizeof in);
     for (int k = 0; k < 4; ++k) in.K4[k] = K4[k];
@@ -211,25 +204,23 @@ int run(ygz_hip_ctx *ctx, int P, const ygz_proj_problem *pb, const double *K4, c
         if (b.pt_skip) memcpy(up + of[q].pt_skip, b.pt_skip, np);
         ProjProbDev D;
         memset(&D, 0, sizeof D);
-        D.kp_px = (const double *)(dev + of[q].kp_px); D.kp_level = (const int32_t *)(dev + of[q].kp_level);
-        D.kp_desc = (const uint32_t *)(dev + of[q].kp_desc); D.kp_taken = b.kp_taken ? dev + of[q].kp_taken : nullptr;
-        D.pw = (const double *)(dev + of[q].pw); D.pt_desc = (const uint32_t *)(dev + of[q].pt_desc);
-        D.pt_dmax = (const double *)(dev + of[q].pt_dmax); D.pt_normal = b.pt_normal ? (const double *)(dev + of[q].pt_normal) : nullptr;
+        D.kp_px = ygz_at<const double>(dev, of[q].kp_px); D.kp_level = ygz_at<const int32_t>(dev, of[q].kp_level);
+        D.kp_desc = ygz_at<const uint32_t>(dev, of[q].kp_desc); D.kp_taken = b.kp_taken ? dev + of[q].kp_taken : nullptr;
+        D.pw = ygz_at<const double>(dev, of[q].pw); D.pt_desc = ygz_at<const uint32_t>(dev, of[q].pt_desc);
+        D.pt_dmax = ygz_at<const double>(dev, of[q].pt_dmax); D.pt_normal = b.pt_normal ? ygz_at<const double>(dev, of[q].pt_normal) : nullptr;
         D.pt_skip = b.pt_skip ? dev + of[q].pt_skip : nullptr;
         D.n_kp = b.n_kp; D.n_pt = b.n_pt; D.pt_off = (int32_t)off;
         for (int k = 0; k < 8; ++k) D.S[k] = b.S[k];
         memcpy(up + o_pb + (size_t)q * sizeof(ProjProbDev), &D, sizeof D);
         off += np;
     }
-    YGZ_HIPCHK(ctx, hipMemcpyAsync(dev, up, in_end, hipMemcpyHostToDevice, ctx->stream));
-    YGZ_LAUNCH(ctx, KID_COUNT, k_proj_search, dim3(ygz_div_up(max_pt, PROJ_LANES), P), dim3(PROJ_LANES), (const ProjIn *)(dev + o_in),
-               (const ProjProbDev *)(dev + o_pb), (uint32_t *)(dev + o_keys), (int32_t *)(dev + o_nc), (int32_t *)(dev + o_pred));
-    YGZ_HIPCHK(ctx, hipGetLastError());
-    YGZ_HIPCHK(ctx, hipMemcpyAsync(up + o_keys, dev + o_keys, total - o_keys, hipMemcpyDeviceToHost, ctx->stream));
-    YGZ_HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    out->keys = (const uint32_t *)(up + o_keys);
-    out->n_cand = (const int32_t *)(up + o_nc);
-    out->pred = (const int32_t *)(up + o_pred);
+    if ((rc = ygz_blob_upload(ctx, blob, in_end)) != YGZ_OK) return rc;
+    YGZ_LAUNCH(ctx, KID_COUNT, k_proj_search, dim3(ygz_div_up(max_pt, PROJ_LANES), P), dim3(PROJ_LANES), ygz_at<const ProjIn>(dev, o_in),
+               ygz_at<const ProjProbDev>(dev, o_pb), ygz_at<uint32_t>(dev, o_keys), ygz_at<int32_t>(dev, o_nc), ygz_at<int32_t>(dev, o_pred));
+    if ((rc = ygz_blob_fetch(ctx, blob, o_keys, total)) != YGZ_OK) return rc;
+    out->keys = ygz_at<const uint32_t>(up, o_keys);
+    out->n_cand = ygz_at<const int32_t>(up, o_nc);
+    out->pred = ygz_at<const int32_t>(up, o_pred);
     *used = p;
     return YGZ_OK;
 }

@@ -715,8 +715,6 @@ __global__ __launch_bounds__(SIM3_REF_LANES) void k_sim3_refine(Sim3Dev D)
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------------
-size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct Layout {
     size_t in, off, x1, x2, p1, p2, lv, sets, in_end;                 // the upload
     size_t res, mask, res_end, valid, counts, hyp, total;             // the copy back: [res, res_end) or [res, total)
@@ -724,28 +722,29 @@ struct Layout {
 Layout layout(int P, size_t N, int it)
 {
     Layout L;
-    size_t o = 0;
-    L.in = o; o = al(o + sizeof(Sim3In));
-    L.off = o; o = al(o + (size_t)(P + 1) * 4);
-    L.x1 = o; o = al(o + N * 24);
-    L.x2 = o; o = al(o + N * 24);
-    L.p1 = o; o = al(o + N * 16);
-    L.p2 = o; o = al(o + N * 16);
-    L.lv = o; o = al(o + N * 8);
-    L.sets = o; o = al(o + (size_t)P * it * 12);
-    L.in_end = o;
-    L.res = o; o = al(o + (size_t)P * sizeof(ygz_sim3_result));
-    L.mask = o; o = al(o + N);
-    L.res_end = o;
-    L.valid = o; o = al(o + (size_t)P * it * 4);
-    L.counts = o; o = al(o + (size_t)P * it * 4);
-    L.hyp = o; o = al(o + (size_t)P * it * 16 * 8);
-    L.total = o;
+    YgzBlobLayout B;
+    const size_t H = (size_t)P * it;                         // hypothesis sets
+    L.in = B.add(sizeof(Sim3In));
+    L.off = B.add_n<int32_t>((size_t)P + 1);
+    L.x1 = B.add_n<double>(N * 3);
+    L.x2 = B.add_n<double>(N * 3);
+    L.p1 = B.add_n<double>(N * 2);
+    L.p2 = B.add_n<double>(N * 2);
+    L.lv = B.add_n<int32_t>(N * 2);
+    L.sets = B.add_n<int32_t>(H * 3);
+    L.in_end = B.end;
+    L.res = B.add_n<ygz_sim3_result>((size_t)P);
+    L.mask = B.add(N);
+    L.res_end = B.end;
+    L.valid = B.add_n<int32_t>(H);
+    L.counts = B.add_n<int32_t>(H);
+    L.hyp = B.add_n<double>(H * 16);
+    L.total = B.end;
     return L;
 }
 
 // validation (before anything touches the device), one upload, the four launches, one copy back of [res, res_end) (all = false) or of
-// [res, total), one wait; `out` receives the page-locked copy
+// [res, total), one wait; `out` receives the page-locked image of the block
 int run(ygz_hip_ctx *ctx, int P, const int32_t *offsets, const double *X1, const double *X2, const double *px1, const double *px2,
         const int32_t *levels, const double *K4, const ygz_sim3_params *params, bool all, uint8_t **out, Layout *Lout)
 {
@@ -769,12 +768,11 @@ int run(ygz_hip_ctx *ctx, int P, const int32_t *offsets, const double *X1, const
     const int it = p.max_iter;
     const size_t N = (size_t)offsets[P];
     const Layout L = layout(P, N, it);
-    uint8_t *dev = nullptr;
-    int rc = ygz_scratch(ctx, SCR_GEN_0 + 13, L.total, (void **)&dev);
+    const size_t down_end = all ? L.total : L.res_end;       // [0, in_end) goes up, [res, down_end) comes back
+    YgzBlob b;
+    int rc = ygz_blob_open(ctx, SCR_SIM3, L.total, down_end, &b);
     if (rc != YGZ_OK) return rc;
-    const size_t down_end = all ? L.total : L.res_end;
-    uint8_t *up = (uint8_t *)ygz_stage(ctx, down_end);        // one page-locked block: [0, in_end) goes up, [res, down_end) comes back
-    if (!up) return YGZ_E_HIP;
+    uint8_t *up = b.host, *dev = b.dev;
     Sim3In in;
     memset(&in, 0, sizeof in);
     for (int k = 0; k < 4; ++k) in.K4[k] = K4[k];
@@ -789,23 +787,20 @@ int run(ygz_hip_ctx *ctx, int P, const int32_t *offsets, const double *X1, const
     memcpy(up + L.lv, levels, N * 8);
     for (int q = 0; q < P; ++q)
         memcpy(up + L.sets + (size_t)q * it * 12, ygz_cvrng_cached_sets(offsets[q + 1] - offsets[q], it, 3).data(), (size_t)it * 12);
-    YGZ_HIPCHK(ctx, hipMemcpyAsync(dev, up, L.in_end, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = ygz_blob_upload(ctx, b, L.in_end)) != YGZ_OK) return rc;
     Sim3Dev D;
-    D.in = (const Sim3In *)(dev + L.in); D.off = (const int32_t *)(dev + L.off);
-    D.X1 = (const double *)(dev + L.x1); D.X2 = (const double *)(dev + L.x2);
-    D.px1 = (const double *)(dev + L.p1); D.px2 = (const double *)(dev + L.p2);
-    D.lv = (const int32_t *)(dev + L.lv); D.sets = (const int32_t *)(dev + L.sets);
-    D.res = (ygz_sim3_result *)(dev + L.res); D.mask = dev + L.mask; D.valid = (int32_t *)(dev + L.valid);
-    D.counts = (int32_t *)(dev + L.counts); D.hyp = (double *)(dev + L.hyp);
+    D.in = ygz_at<const Sim3In>(dev, L.in); D.off = ygz_at<const int32_t>(dev, L.off);
+    D.X1 = ygz_at<const double>(dev, L.x1); D.X2 = ygz_at<const double>(dev, L.x2);
+    D.px1 = ygz_at<const double>(dev, L.p1); D.px2 = ygz_at<const double>(dev, L.p2);
+    D.lv = ygz_at<const int32_t>(dev, L.lv); D.sets = ygz_at<const int32_t>(dev, L.sets);
+    D.res = ygz_at<ygz_sim3_result>(dev, L.res); D.mask = dev + L.mask; D.valid = ygz_at<int32_t>(dev, L.valid);
+    D.counts = ygz_at<int32_t>(dev, L.counts); D.hyp = ygz_at<double>(dev, L.hyp);
     YGZ_LAUNCH(ctx, KID_COUNT, k_sim3_solve, dim3(ygz_div_up(it, SIM3_SOLVE_LANES), P), dim3(SIM3_SOLVE_LANES), D);
     YGZ_LAUNCH(ctx, KID_COUNT, k_sim3_score, dim3(ygz_div_up(it, SIM3_SCORE_LANES), P), dim3(SIM3_SCORE_LANES), D);
     YGZ_LAUNCH(ctx, KID_COUNT, k_sim3_select, dim3(P), dim3(SIM3_SEL_THREADS), D);
     YGZ_LAUNCH(ctx, KID_COUNT, k_sim3_refine, dim3(P), dim3(SIM3_REF_LANES), D);
-    YGZ_HIPCHK(ctx, hipGetLastError());
-    uint8_t *down = up + L.res;
-    YGZ_HIPCHK(ctx, hipMemcpyAsync(down, dev + L.res, down_end - L.res, hipMemcpyDeviceToHost, ctx->stream));
-    YGZ_HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    *out = down;
+    if ((rc = ygz_blob_fetch(ctx, b, L.res, down_end)) != YGZ_OK) return rc;
+    *out = up;
     *Lout = L;
     return YGZ_OK;
 }
@@ -830,8 +825,8 @@ int ygz_hip_sim3_ransac(ygz_hip_ctx *ctx, int n_problems, const int32_t *offsets
     Layout L;
     const int rc = run(ctx, n_problems, offsets, X1, X2, px1, px2, levels, K4, params, false, &o, &L);
     if (rc != YGZ_OK) return rc;
-    memcpy(results, o, (size_t)n_problems * sizeof(ygz_sim3_result));
-    if (inliers) memcpy(inliers, o + (L.mask - L.res), (size_t)offsets[n_problems]);
+    memcpy(results, o + L.res, (size_t)n_problems * sizeof(ygz_sim3_result));
+    if (inliers) memcpy(inliers, o + L.mask, (size_t)offsets[n_problems]);
     return YGZ_OK;
 }
 
@@ -844,9 +839,9 @@ int ygz_hip_sim3_hypotheses(ygz_hip_ctx *ctx, const double *X1, const double *X2
     const int rc = run(ctx, 1, off, X1, X2, px1, px2, levels, K4, params, true, &o, &L);
     if (rc != YGZ_OK) return rc;
     const int it = params ? params->max_iter : 300;
-    if (hyps) memcpy(hyps, o + (L.hyp - L.res), (size_t)it * 16 * 8);
-    if (valid) memcpy(valid, o + (L.valid - L.res), (size_t)it * 4);
-    if (counts) memcpy(counts, o + (L.counts - L.res), (size_t)it * 4);
+    if (hyps) memcpy(hyps, o + L.hyp, (size_t)it * 16 * 8);
+    if (valid) memcpy(valid, o + L.valid, (size_t)it * 4);
+    if (counts) memcpy(counts, o + L.counts, (size_t)it * 4);
     return YGZ_OK;
 }
 

@@ -697,7 +697,7 @@ int ygz_launch_sparse_align(ygz_hip_ctx *ctx, int n_pairs, int max_level, int mi
     A.lin = ctx->sa_lin; A.rel = ctx->sa_rel ? 1 : 0;
     A.out_host = ctx->sa_out_host;
 #ifdef YGZ_SA_TIMERS
-    { void *dd = nullptr; if (ygz_scratch(ctx, SCR_GEN_0 + 1, (size_t)n_pairs * 16 * 8, &dd) == YGZ_OK) A.dbg = (double *)dd; }
+    { void *dd = nullptr; if (ygz_scratch(ctx, SCR_GEN_1, (size_t)n_pairs * 16 * 8, &dd) == YGZ_OK) A.dbg = (double *)dd; }
 #endif
     // a problem gets 512 lanes when the launch leaves CUs idle anyway (few pairs: the single-frame surface calls) or when the grid is too big
     // for the per-lane feature loop of the 256-lane form; else 256 (one wavefront per SIMD: the VALU-bound stages of other streams fill its
@@ -774,7 +774,7 @@ extern "C" int ygz_hip_sparse_align(ygz_hip_ctx *ctx, int ref_slot, const double
     // copies on the stream before), the 16 result doubles back into the page-locked arena: one wait per call
     const size_t N = (size_t)n;
     YgzPack pk;
-    int rc = ygz_pack_begin(ctx, &pk, N * 25 + 64 + 14 * 8 + 16 + (size_t)ctx->prm.max_frames * 8 + 64, SCR_GEN_0 + 6);
+    int rc = ygz_pack_begin(ctx, &pk, N * 25 + 64 + 14 * 8 + 16 + (size_t)ctx->prm.max_frames * 8 + 64, SCR_SA_PACK);
     if (rc != YGZ_OK) return rc;
     if ((rc = ygz_track_set_pairs(ctx, &cur_slot, &ref_slot, T_cur, T_ref, 1, &pk)) != YGZ_OK) return rc;
     double *h_px = (double *)ygz_pack_add(&pk, ctx->trk_px, N * 16), *h_dep = (double *)ygz_pack_add(&pk, ctx->trk_depth, N * 8);
@@ -826,7 +826,7 @@ extern "C" int ygz_hip_sparse_align_residuals(ygz_hip_ctx *ctx, int ref_slot, in
     if (!ctx->pyr_valid[ref_slot] || !ctx->pyr_valid[cur_slot]) return YGZ_E_STATE;
     const size_t N = (size_t)n;
     YgzPack pk;
-    int rc = ygz_pack_begin(ctx, &pk, N * 25 + 64 + 14 * 8 + 16 + (size_t)ctx->prm.max_frames * 8 + 64, SCR_GEN_0 + 6);
+    int rc = ygz_pack_begin(ctx, &pk, N * 25 + 64 + 14 * 8 + 16 + (size_t)ctx->prm.max_frames * 8 + 64, SCR_SA_PACK);
     if (rc != YGZ_OK) return rc;
     const double I7[7] = { 0, 0, 0, 1, 0, 0, 0 };
     if ((rc = ygz_track_set_pairs(ctx, &cur_slot, &ref_slot, T_cur_from_ref, I7, 1, &pk)) != YGZ_OK) return rc;
@@ -838,7 +838,7 @@ extern "C" int ygz_hip_sparse_align_residuals(ygz_hip_ctx *ctx, int ref_slot, in
     memcpy(h_px, px, N * 16); memcpy(h_dep, depth, N * 8); memcpy(h_mp, has_mappoint, N); memcpy(h_T, T_cur_from_ref, 56); *h_n = n;
     if ((rc = ygz_pack_upload(ctx, &pk)) != YGZ_OK) return rc;
     void *d_lin = nullptr;
-    if ((rc = ygz_scratch(ctx, SCR_GEN_0 + 3, 32 * 8, &d_lin)) != YGZ_OK) return rc;
+    if ((rc = ygz_scratch(ctx, SCR_PACK_STATES_SA_LIN, 32 * 8, &d_lin)) != YGZ_OK) return rc;
     YGZ_HIPCHK(ctx, hipMemsetAsync(d_lin, 0, 32 * 8, ctx->stream));
     double *h_lin = (double *)ygz_stage(ctx, 32 * 8);
     if (!h_lin) return YGZ_E_HIP;

@@ -215,8 +215,6 @@ __global__ __launch_bounds__(256) void k_stereo_median(StereoArgs A)
     if (tid < YGZ_STEREO_N_STATUS) A.counts[(size_t)pair * YGZ_STEREO_N_STATUS + tid] = s_cnt[tid];
 }
 
-static inline size_t st_al(size_t x) { return (x + 63) & ~(size_t)63; }
-
 static bool stereo_params_ok(const ygz_stereo_params &p)
 {
     if (!isfinite(p.baseline) || !isfinite(p.min_disparity) || !isfinite(p.max_disparity)) return false;
@@ -240,30 +238,21 @@ static int stereo_run(ygz_hip_ctx *ctx, int n_pairs, const int32_t *left_slot, c
     const size_t cells = (size_t)ctx->cells;
     const size_t stride = kp ? (size_t)(kp[0].n > 0 ? kp[0].n : 1) : cells, kp_stride = kp ? (size_t)(kp[0].n > kp[1].n ? kp[0].n : kp[1].n) : cells;
     const size_t N = (size_t)n_pairs * stride;
-    // up: [table | px | level | desc), back: [u_right | depth | right_idx | sad | status | counts | best_idx | best_dist | n_cand | sads)
-    size_t o = 0;
-    const size_t o_tab = o; o = st_al(o + (size_t)n_pairs * ST_TAB * 4);
-    const size_t o_px = o; if (kp) o = st_al(o + 2 * kp_stride * 16);
-    const size_t o_lv = o; if (kp) o = st_al(o + 2 * kp_stride * 4);
-    const size_t o_ds = o; if (kp) o = st_al(o + 2 * kp_stride * 32);
-    const size_t in_end = o;
-    const size_t o_ur = o; o = st_al(o + N * 8);
-    const size_t o_dp = o; o = st_al(o + N * 8);
-    const size_t o_ri = o; o = st_al(o + N * 4);
-    const size_t o_sd = o; o = st_al(o + N * 4);
-    const size_t o_st = o; o = st_al(o + N * 4);
-    const size_t o_ct = o; o = st_al(o + (size_t)n_pairs * YGZ_STEREO_N_STATUS * 4);
-    const size_t o_bi = o; if (stage_outputs) o = st_al(o + N * 4);
-    const size_t o_bd = o; if (stage_outputs) o = st_al(o + N * 4);
-    const size_t o_nc = o; if (stage_outputs) o = st_al(o + N * 4);
-    const size_t o_ss = o; if (stage_outputs) o = st_al(o + N * ST_N * 4);
-    const size_t total = o;
-    uint8_t *dev = nullptr;
-    const int rc = ygz_scratch(ctx, SCR_GEN_0 + 20, total, (void **)&dev);
+    // up: [table | px | level | desc), back: [u_right | depth | right_idx | sad | status | counts | best_idx | best_dist | n_cand | sads).
+    // Every array at a multiple of 256 bytes, as in every packed block (this file aligned to 64 before: the block grows by a few KB, no output changes)
+    YgzBlobLayout L;
+    const size_t KP = kp ? 2 * kp_stride : 0, NS = stage_outputs ? N : 0;          // absent arrays take no room
+    const size_t o_tab = L.add_n<int32_t>((size_t)n_pairs * ST_TAB);
+    const size_t o_px = L.add_n<double>(KP * 2), o_lv = L.add_n<int32_t>(KP), o_ds = L.add_n<uint32_t>(KP * 8), in_end = L.end;
+    const size_t o_ur = L.add_n<double>(N), o_dp = L.add_n<double>(N), o_ri = L.add_n<int32_t>(N), o_sd = L.add_n<int32_t>(N);
+    const size_t o_st = L.add_n<int32_t>(N), o_ct = L.add_n<int32_t>((size_t)n_pairs * YGZ_STEREO_N_STATUS);
+    const size_t o_bi = L.add_n<int32_t>(NS), o_bd = L.add_n<int32_t>(NS), o_nc = L.add_n<int32_t>(NS), o_ss = L.add_n<int32_t>(NS * ST_N);
+    const size_t total = L.end;
+    YgzBlob b;
+    int rc = ygz_blob_open(ctx, SCR_STEREO, total, total, &b);
     if (rc != YGZ_OK) return rc;
-    uint8_t *up = (uint8_t *)ygz_stage(ctx, total);
-    if (!up) return YGZ_E_HIP;
-    int32_t *tab = (int32_t *)(up + o_tab);
+    uint8_t *up = b.host, *dev = b.dev;
+    int32_t *tab = ygz_at<int32_t>(up, o_tab);
     for (int q = 0; q < n_pairs; ++q) {
         int32_t *e = tab + ST_TAB * q;
         e[0] = left_slot[q]; e[1] = right_slot[q];
@@ -278,28 +267,27 @@ static int stereo_run(ygz_hip_ctx *ctx, int n_pairs, const int32_t *left_slot, c
             memcpy(up + o_lv + s * kp_stride * 4, kp[s].level, n * 4);
             memcpy(up + o_ds + s * kp_stride * 32, kp[s].desc, n * 32);
         }
-    YGZ_HIPCHK(ctx, hipMemcpyAsync(dev, up, in_end, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = ygz_blob_upload(ctx, b, in_end)) != YGZ_OK) return rc;
     StereoArgs A;
     memset(&A, 0, sizeof(A));
-    A.tab = (const int32_t *)(dev + o_tab); A.n_kp = ctx->n_kp;
-    A.px = kp ? (const double *)(dev + o_px) : ctx->kp_px; A.level = kp ? (const int32_t *)(dev + o_lv) : ctx->kp_level;
-    A.desc = kp ? (const uint32_t *)(dev + o_ds) : ctx->kp_desc;
+    A.tab = ygz_at<const int32_t>(dev, o_tab); A.n_kp = ctx->n_kp;
+    A.px = kp ? ygz_at<const double>(dev, o_px) : ctx->kp_px; A.level = kp ? ygz_at<const int32_t>(dev, o_lv) : ctx->kp_level;
+    A.desc = kp ? ygz_at<const uint32_t>(dev, o_ds) : ctx->kp_desc;
     A.kp_stride = (int)kp_stride; A.out_stride = (int)stride; A.n_levels = ctx->prm.pyramid_levels; A.th_dist = p.th_dist;
     for (int l = 0; l < ctx->prm.pyramid_levels; ++l) { A.lvl[l] = ctx->lvl[l]; A.lw[l] = ctx->lw[l]; A.lh[l] = ctx->lh[l]; }
     const double fx_d = (double)ctx->prm.fx;
     A.bf = fx_d * p.baseline; A.minD = p.min_disparity; A.maxD = p.max_disparity == 0.0 ? fx_d : p.max_disparity;
-    A.u_right = (double *)(dev + o_ur); A.depth = (double *)(dev + o_dp); A.right_idx = (int32_t *)(dev + o_ri); A.sad = (int32_t *)(dev + o_sd);
-    A.status = (int32_t *)(dev + o_st); A.counts = (int32_t *)(dev + o_ct);
+    A.u_right = ygz_at<double>(dev, o_ur); A.depth = ygz_at<double>(dev, o_dp); A.right_idx = ygz_at<int32_t>(dev, o_ri);
+    A.sad = ygz_at<int32_t>(dev, o_sd); A.status = ygz_at<int32_t>(dev, o_st); A.counts = ygz_at<int32_t>(dev, o_ct);
     if (stage_outputs) {
-        A.best_idx = (int32_t *)(dev + o_bi); A.best_dist = (int32_t *)(dev + o_bd); A.n_cand = (int32_t *)(dev + o_nc); A.sads = (int32_t *)(dev + o_ss);
+        A.best_idx = ygz_at<int32_t>(dev, o_bi); A.best_dist = ygz_at<int32_t>(dev, o_bd); A.n_cand = ygz_at<int32_t>(dev, o_nc);
+        A.sads = ygz_at<int32_t>(dev, o_ss);
     }
     if (write_depths) { A.kp_depth = ctx->kp_depth; A.kp_has_mp = ctx->kp_has_mp; }
     YGZ_LAUNCH(ctx, KID_STEREO_MATCH, k_stereo_match, dim3((unsigned)stride, (unsigned)n_pairs), dim3(64), A);
     YGZ_HIPCHK(ctx, hipGetLastError());
     YGZ_LAUNCH(ctx, KID_STEREO_MEDIAN, k_stereo_median, dim3((unsigned)n_pairs), dim3(256), A);
-    YGZ_HIPCHK(ctx, hipGetLastError());
-    YGZ_HIPCHK(ctx, hipMemcpyAsync(up + in_end, dev + in_end, total - in_end, hipMemcpyDeviceToHost, ctx->stream));
-    YGZ_HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if ((rc = ygz_blob_fetch(ctx, b, in_end, total)) != YGZ_OK) return rc;
     const size_t n_out = kp ? (size_t)kp[0].n : N;
     if (out.u_right) memcpy(out.u_right, up + o_ur, n_out * 8);
     if (out.depth) memcpy(out.depth, up + o_dp, n_out * 8);

@@ -620,7 +620,7 @@ int ygz_hip_ba_pack_states(ygz_hip_ctx *ctx, int window_begin, int n_windows, do
     const BaDev *table = ygz_ba_table(ctx, &rc);
     if (!table) return rc;
     double *out = dst;
-    if (!dst_on_device && (rc = ygz_scratch(ctx, SCR_GEN_0 + 3, (size_t)n_windows * row_doubles * 8, (void **)&out)) != YGZ_OK) return rc;
+    if (!dst_on_device && (rc = ygz_scratch(ctx, SCR_PACK_STATES_SA_LIN, (size_t)n_windows * row_doubles * 8, (void **)&out)) != YGZ_OK) return rc;
     if (row_doubles > (size_t)6 * K + (size_t)3 * P + 12) YGZ_HIPCHK(ctx, hipMemsetAsync(out, 0, (size_t)n_windows * row_doubles * 8, ctx->stream));
     YGZ_LAUNCH(ctx, KID_WINDOW, k_ba_pack, dim3(n_windows), dim3(256), table + window_begin, out, row_doubles, K, P);
     YGZ_HIPCHK(ctx, hipGetLastError());

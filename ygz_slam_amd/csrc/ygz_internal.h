@@ -5,6 +5,7 @@
 #include <stddef.h>
 #include <vector>
 #include "../../include/ygz_hip.h"
+#include "ygz_blob.h"
 
 #define YGZ_KLT_LEVELS 5          // Tracker.cpp:97 maxLevel 4 -> 5 levels
 // the tracker's working images: every level inside a reflect-101 frame of KLT_B pixels (klt.hip; written by the pyramid kernels, image.hip)
@@ -228,9 +229,34 @@ enum { KID_BGR2GRAY = 0, KID_PYR_DOWN, KID_FAST_SELECT, KID_COMPACT, KID_DESCRIB
          hipLaunchKernelGGL(kern, grid, block, dyn, (ctx)->stream, __VA_ARGS__);                               \
          if (pr_) { (void)hipEventRecord((ctx)->probe_ev[(ctx)->probe_used + 1], (ctx)->stream); (ctx)->probe_used += 2; } } while (0)
 
-// scratch ids
+// scratch ids: one growable device buffer each (ygz_scratch).  A buffer may be handed out again as soon as the call that asked for it has
+// returned, so an id has ONE owner unless its line says who shares it and why they cannot meet.  (DESIGN.md section 21 has the table.)
 enum { SCR_MATCH_Q = 0, SCR_MATCH_T, SCR_ALIGN_IN, SCR_ALIGN_OUT, SCR_SA_IN, SCR_SA_OUT, SCR_SA_WORK,
-       SCR_KLT_PTS, SCR_KLT_OUT, SCR_BA_0, SCR_BOW, SCR_LMAP, SCR_WIN, SCR_GEN_0 = 16 };
+       SCR_KLT_PTS, SCR_KLT_OUT, SCR_BA_0, SCR_BOW, SCR_LMAP, SCR_WIN,
+       // shared by the synchronous host-array calls of bow.hip (5), align.hip (3), postfilter.hip (ygz_hip_match_postfilter_host), popt.hip and
+       // pose_only.hip: each joins the side streams on entry, works on the main stream and ends in its own hipStreamSynchronize, so the buffer
+       // is idle whenever one of them starts
+       SCR_GEN_0 = 16,
+       // run_check of postfilter.hip; in -DYGZ_FAST_TIMERS / -DYGZ_SA_TIMERS builds also the cycle records of k_fast_select and k_sparse_align.
+       // Each of the three reads its data back and waits inside the launch call that wrote it
+       SCR_GEN_1,
+       SCR_BULK_SUMS,            // bulk.hip: the per-pair sums
+       // ygz_hip_ba_pack_states (window.hip: the rows on their way to the host) and ygz_hip_sparse_align_residuals (sparse_align.hip: the 32
+       // doubles of the last linearisation).  The second waits before it returns; the first may leave its copy back pending (wait = 0), on
+       // the main stream, where the second's memset is ordered behind it
+       SCR_PACK_STATES_SA_LIN,
+       SCR_LM_DEBUG,             // ba_resident_lm.hip: YGZ_LM_DEBUG counters
+       SCR_LM_REC,               // ba_resident_lm.hip: the per-window LM records (and, once per context, the barrier self-test before any of them)
+       SCR_SA_PACK,              // sparse_align.hip: the packed upload of the two single-frame calls (each waits before it returns)
+       SCR_DETECT_PACK,          // detect.hip: ygz_hip_get_keypoints' packed copy back
+       SCR_BA_PACK,              // ba.hip: ygz_ba_fetch_result's packed copy back
+       SCR_BA_CHI2,              // ba.hip: its per-edge chi2
+       SCR_LMAP_ASYNC,           // align.hip: ygz_hip_find_direct_projection_mp_begin .. _end (lives across the two calls)
+       // the packed blocks of the entry points that go through ygz_blob_open, one each
+       SCR_INIT, SCR_PNP, SCR_SIM3, SCR_PROJ, SCR_PGO, SCR_MAP, SCR_GBA, SCR_KFDB, SCR_CULL, SCR_STEREO,
+       SCR_LAST = SCR_STEREO };
+static_assert(SCR_GEN_0 == 16 && SCR_INIT == 27 && SCR_LAST == 36, "the scratch ids keep their values");
+static_assert(SCR_LAST < YGZ_N_SCRATCH, "ygz_hip_ctx::scratch holds every id");
 
 int ygz_scratch(ygz_hip_ctx *ctx, int id, size_t bytes, void **out);
 // the RANSAC sample sets of cv::RNG's scheme (init.hip): a fresh generator (state 0xffffffff), per iteration k distinct indices of [0, n) by the
@@ -241,6 +267,14 @@ const std::vector<int32_t> &ygz_cvrng_cached_sets(int n, int max_iter, int k);
 int ygz_scratch_mirror(ygz_hip_ctx *ctx, int id, void **host);
 // `bytes` of page-locked host memory that stay valid until the next ygz_hip_synchronize (nullptr: allocation failed)
 void *ygz_stage(ygz_hip_ctx *ctx, size_t bytes);
+// One packed block of an entry point (layout: YgzBlobLayout, ygz_blob.h): the device block in scratch buffer `scratch_id` and its page-locked image
+// from the staging arena, at the same offsets.  The host fills [0, in_end) of the image, ygz_blob_upload sends it with ONE copy, the caller
+// launches, ygz_blob_fetch brings [begin, end) back with ONE copy and waits ONCE; the image stays readable until the context's next call.
+struct YgzBlob { uint8_t *dev = nullptr, *host = nullptr; };
+int ygz_blob_open(ygz_hip_ctx *ctx, int scratch_id, size_t dev_bytes, size_t host_bytes, YgzBlob *b);   // ygz_scratch, then ygz_stage; YGZ_E_CAPACITY for a bad layout, before either
+int ygz_blob_upload(ygz_hip_ctx *ctx, const YgzBlob &b, size_t end);                                    // host [0, end) -> device, asynchronous on ctx->stream
+int ygz_blob_fetch(ygz_hip_ctx *ctx, const YgzBlob &b, size_t begin, size_t end);                       // the launches' error, device [begin, end) -> host (nothing when begin == end), the wait
+template <class T> T *ygz_at(uint8_t *base, size_t off) { return reinterpret_cast<T *>(base + off); }    // array `off` of a block
 // Several small arrays of a single-frame call in ONE transfer: the host fills slices of a page-locked block (ygz_pack_add returns the slice of a
 // device destination), ygz_pack_upload copies the block to a device staging area and ONE kernel scatters the slices; ygz_pack_fetch is the mirror
 // image for results (one gather kernel, one copy back; the caller waits and reads the slices).  A pageable or even page-locked hipMemcpyAsync per
