@@ -13,4 +13,5 @@
 #include "ygz/Algorithm/LoopClosing.h"
 #include "ygz/Algorithm/StereoMatcher.h"
 #include "ygz/Algorithm/PoseOptimizer.h"
+#include "ygz/Algorithm/BundleAdjuster.h"
 #endif

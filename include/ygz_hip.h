@@ -54,6 +54,8 @@ extern "C" {
  * Still 6: the map upkeep of loop fusion added (ygz_hip_distinctive_descriptors, ygz_hip_covisibility) -- no existing argument list changed.
  * Still 6: the global bundle adjustment added (ygz_gba_params, ygz_gba_result, ygz_hip_default_gba_params, ygz_hip_global_ba,
  * ygz_hip_gba_linearize) -- no existing argument list changed.
+ * Still 6: the stereo bundle adjustment added (ygz_sba_params, ygz_sba_result, ygz_hip_default_sba_params, ygz_hip_stereo_ba,
+ * ygz_hip_sba_linearize) -- no existing argument list changed.
  * Still 6: the keyframe database added (ygz_kfdb, ygz_hip_kfdb_create, ygz_hip_kfdb_destroy, ygz_hip_kfdb_add, ygz_hip_kfdb_erase,
  * ygz_hip_kfdb_clear, ygz_hip_kfdb_info, ygz_hip_kfdb_query) -- no existing argument list changed.
  * Still 6: keyframe culling added (ygz_cull_params, ygz_hip_default_cull_params, ygz_hip_keyframe_redundancy, ygz_hip_cull_keyframes) -- no
@@ -1048,6 +1050,60 @@ int  ygz_hip_gba_linearize(ygz_hip_ctx *ctx, int n_poses, const double *poses, c
                            int n_edges, const int32_t *edge_pose, const int32_t *edge_point, const double *obs, const double K4[4],
                            double huber_delta, const ygz_gba_params *params, double *residuals, double *weights, double *Jp, double *Jl,
                            double *Hpp, double *bp, double *Hll, double *bl, double *cost);
+
+/* ---- stereo bundle adjustment -- nothing in the reference; ORB-SLAM2's Optimizer::LocalBundleAdjustment / GlobalBundleAdjustemnt with mono
+ * and stereo edges.  The problem of ygz_hip_global_ba with obs [E][3] = (u, v, uR), kind [E] (0 absent, 1 mono, 2 stereo: uR of a mono edge
+ * and all of an absent edge are never read) and level [E] inside the context's pyramid: the information is 4^-level, a stereo edge adds the
+ * residual uR - (fx x / z + cx - bf / z) with bf = fx * baseline, and g2o's Huber kernel acts on chi2 = w |r|^2 with delta^2 = chi2_mono or
+ * chi2_stereo.  Round k = 0 .. rounds - 1: the active edges are the present ones that the last classification did not flag (round 0: all
+ * present), the kernel is on while k < robust_rounds, the Levenberg-Marquardt loop and inner solve of ygz_hip_global_ba run from the
+ * current estimate for at most iterations[k] iterations (lambda_0 anew, the counters from zero); then every present edge is classified at
+ * the round's final state by a fresh evaluation without kernel: an edge whose point is not in front of its camera is an outlier with chi2
+ * 0, chi2 above chi2_mono / chi2_stereo is an outlier.  An absent or inactive edge keeps its place in every sum and adds exact zeros, so a
+ * call on the compacted edge list is not promised the same bits.  YGZ_GBA_FAILED (an active edge undefined at the input) can only arise in
+ * round 0: the outputs are the inputs, the flags those of a classification at the input, rounds_run 1.  The arithmetic is that of
+ * tests/sba_ref.c: every output is bit-identical to it, whatever cg_batch is. */
+#define YGZ_SBA_MAX_ROUNDS 4
+typedef struct {
+    int32_t max_iterations;               /* 10: kept from ygz_gba_params and checked like it; the rounds use iterations[] */
+    int32_t max_trials;                   /* 10 */
+    int32_t cg_max_iterations;            /* 0 */
+    int32_t cg_batch;                     /* 0 */
+    double  cg_tol;                       /* 1e-8 */
+    double  min_rel_decrease;             /* 1e-9 */
+    double  baseline;                     /* 0: no default; > 0 when a stereo edge is present */
+    double  chi2_mono, chi2_stereo;       /* 5.991, 7.815: > 0 */
+    int32_t rounds;                       /* 2: in [1, YGZ_SBA_MAX_ROUNDS] */
+    int32_t robust_rounds;                /* 1: in [0, YGZ_SBA_MAX_ROUNDS] */
+    int32_t iterations[YGZ_SBA_MAX_ROUNDS];   /* 5, 10, 0, 0: each of the first `rounds` entries in [1, 1000] */
+} ygz_sba_params;
+typedef struct {                          /* per round; unused rounds are zero */
+    double  cost_initial[YGZ_SBA_MAX_ROUNDS], cost_final[YGZ_SBA_MAX_ROUNDS], lambda[YGZ_SBA_MAX_ROUNDS];
+    int32_t rounds_run;
+    int32_t launches;                     /* kernels the call queued: a host count, what cg_batch trades against read-backs */
+    int32_t status[YGZ_SBA_MAX_ROUNDS];   /* YGZ_GBA_* */
+    int32_t lm_iterations[YGZ_SBA_MAX_ROUNDS], n_solves[YGZ_SBA_MAX_ROUNDS], cg_iterations[YGZ_SBA_MAX_ROUNDS], cg_capped[YGZ_SBA_MAX_ROUNDS];
+    int32_t inliers[YGZ_SBA_MAX_ROUNDS];  /* present edges that the round's classification did not flag */
+} ygz_sba_result;
+void ygz_hip_default_sba_params(ygz_sba_params *p);
+/* the whole optimisation: params NULL: defaults (refused when a stereo edge is present: the baseline has none); poses_out [N][7],
+ * points_out [L][3]; outlier [E] and chi2 [E] (-1.0 for an absent edge) are those of the last classification and may be NULL.  Checked
+ * in the order of ygz_hip_global_ba, all before the device is touched, the degree rules counting present edges only; in addition
+ * YGZ_E_INVALID for chi2_mono or chi2_stereo not > 0 or not finite (and, with ygz_gba_params' rule, for a max_iterations outside [1, 1000]
+ * although no round reads it: leave it at its default), rounds, robust_rounds or a used iterations entry out of range (with
+ * the parameters), a kind above 2 or a level outside the pyramid (with the indices), a non-finite observation that the edge's kind uses,
+ * a baseline not > 0 or not finite while a stereo edge is present; last, YGZ_E_INVALID for a null context. */
+int  ygz_hip_stereo_ba(ygz_hip_ctx *ctx, int n_poses, const double *poses, const uint8_t *fixed, int n_points, const double *points, int n_edges,
+                       const int32_t *edge_pose, const int32_t *edge_point, const double *obs, const uint8_t *kind, const int32_t *level,
+                       const double K4[4], const ygz_sba_params *params, double *poses_out, double *points_out, uint8_t *outlier, double *chi2,
+                       ygz_sba_result *result);
+/* stage for tests: the linearisation at the input, every present edge active, the kernel on iff robust_rounds > 0 -- residuals [E][3],
+ * weights [E] (rho' w), Jp [E][18] (3x6 row-major), Jl [E][9] (3x3), Hpp [N][21], bp [N][6], Hll [L][6], bl [L][3], cost [1]; each may be
+ * NULL.  The same checks (without the outputs).  Returns YGZ_E_STATE when a present edge is undefined (zeros for such an edge). */
+int  ygz_hip_sba_linearize(ygz_hip_ctx *ctx, int n_poses, const double *poses, const uint8_t *fixed, int n_points, const double *points,
+                           int n_edges, const int32_t *edge_pose, const int32_t *edge_point, const double *obs, const uint8_t *kind,
+                           const int32_t *level, const double K4[4], const ygz_sba_params *params, double *residuals, double *weights,
+                           double *Jp, double *Jl, double *Hpp, double *bp, double *Hll, double *bl, double *cost);
 
 /* ---- keyframe database: place-recognition queries -- nothing in the reference (its relocalisation and loop detection are stubs); ORB-SLAM2's
  * KeyFrameDatabase over DBoW3's L1 scoring.  The BoW vectors of the keyframes live in HBM; one launch gives, for up to YGZ_KFDB_MAX_QUERIES

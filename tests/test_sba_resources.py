@@ -1,0 +1,61 @@
+"""Register budget of the stereo bundle adjustment's kernels (ygz_slam_amd/csrc/sba.hip), from the compiler's own remarks
+(-Rpass-analysis=kernel-resource-usage) for the flags of ygz_slam_amd/csrc/Makefile: nothing goes to scratch memory, nothing spills, and every
+kernel keeps the occupancy DESIGN.md section 22 states.  The two kernels that tree-sum 27 quantities per pose hold 27 x 256 doubles of LDS
+(54 KiB): two workgroups per CU, with three residual rows as with two.  The file and the header it shares with gba.hip keep gba.hip's rules."""
+import os
+import re
+import shutil
+
+import pytest
+
+from conftest import ROOT
+from test_kernel_resources import HIPCC, _usage
+
+# kernel -> minimum wavefronts per SIMD
+BUDGET = {"k_sba_linearize": 4, "k_sba_point_system": 8, "k_sba_pose_system": 2, "k_sba_cost": 8, "k_sba_classify": 8, "k_sba_begin": 8,
+          "k_sba_point_trial": 8, "k_sba_pose_trial": 2, "k_sba_cg_begin": 4, "k_sba_cg_point": 4, "k_sba_cg_pose": 6, "k_sba_cg_step": 4,
+          "k_sba_point_update": 4, "k_sba_pose_update": 8, "k_sba_decide": 8, "k_sba_accept": 8}
+POSE_KERNELS = ("k_sba_pose_system", "k_sba_pose_trial")
+
+
+@pytest.mark.skipif(shutil.which(HIPCC) is None and not os.path.exists(HIPCC), reason="hipcc not available")
+def test_sba_kernels_do_not_spill():
+    u = _usage("sba")
+    assert len([k for k in u if "k_sba_" in k]) == len(BUDGET)
+    problems = []
+    for key, occ in BUDGET.items():
+        hits = [(k, v) for k, v in u.items() if key + "E" in k or k.endswith(key)]
+        assert len(hits) == 1, (key, [k for k, _ in hits])
+        k, v = hits[0]
+        spilled = v.get("SGPRs Spill", 0) + v.get("VGPRs Spill", 0)
+        if v["ScratchSize"] != 0 or spilled != 0 or v["Occupancy"] < occ:
+            problems.append("%s: scratch %d B per lane, %d spilled registers, %d wavefronts per SIMD (budget %d), %d VGPRs"
+                            % (k, v["ScratchSize"], spilled, v["Occupancy"], occ, v["VGPRs"]))
+        lds = v.get("LDS Size", 0)
+        assert lds <= 27 * 256 * 8 + 27 * 8
+        if key in POSE_KERNELS:                                      # two workgroups of four wavefronts per CU: 2 per SIMD, and twice the LDS fits the CU's 160 KiB
+            assert v["Occupancy"] >= 2 and 2 * lds <= 160 * 1024, (key, v["Occupancy"], lds)
+    assert not problems, "\n".join(problems)
+
+
+def test_summation_constants_and_rules_are_shared():
+    """GBA_LANES, GBA_CHUNK and GBA_CG_CAP of sba.hip are gba.hip's and the restatements' GB_LANES, GB_CHUNK and GB_CG_CAP (tests/sba_ref.c
+    includes tests/gba_ref.c and defines none of its own); the shared header asserts their values.  Neither sba.hip nor the header reads the
+    environment, launches cooperatively, fences, spins, adds atomically or waits for another workgroup"""
+    import gba_ref as gb
+    csrc = os.path.join(ROOT, "ygz_slam_amd", "csrc")
+    hip, hdr, old = (open(os.path.join(csrc, f)).read() for f in ("sba.hip", "gba_phases.h", "gba.hip"))
+    ref, ref3 = open(os.path.join(ROOT, "tests", "gba_ref.c")).read(), open(os.path.join(ROOT, "tests", "sba_ref.c")).read()
+    assert '#include "gba_ref.c"' in ref3 and not re.search(r"#define\s+GB_(LANES|CHUNK|CG_CAP)", ref3)
+    for dev, host, value in [("GBA_LANES", "GB_LANES", 256), ("GBA_CHUNK", "GB_CHUNK", 1024), ("GBA_CG_CAP", "GB_CG_CAP", 1024)]:
+        new, was = (int(re.search(r"#define\s+%s\s+(\d+)" % dev, t).group(1)) for t in (hip, old))
+        assert new == was == int(re.search(r"#define\s+%s\s+(\d+)" % host, ref).group(1)) == value
+        assert not re.search(r"#define\s+%s\b" % dev, hdr)
+    assert re.search(r"static_assert\(GBA_LANES == 256 && GBA_CHUNK == 1024 && GBA_CG_CAP == 1024", hdr)
+    assert (gb.LANES, gb.CHUNK, gb.CG_CAP) == (256, 1024, 1024)
+    assert hip.count("__launch_bounds__(GBA_LANES)") == len(BUDGET) and "__global__" not in hdr
+    assert '#include "gba_phases.h"' in hip and '#include "gba_phases.h"' in old and "#pragma clang fp contract(off)" in hip
+    for text in (hip, hdr):
+        code = re.sub(r"//[^\n]*", "", text)
+        for word in ["getenv", "hipLaunchCooperativeKernel", "cooperative_groups", "atomicAdd", "__threadfence", "while ("]:
+            assert word not in code, word

@@ -349,6 +349,61 @@ def gba_argtypes(lib):
     lib.ygz_hip_gba_linearize.argtypes = problem + [dp] * 9
 
 
+class SbaParams(C.Structure):
+    """ygz_sba_params (include/ygz_hip.h)"""
+    _fields_ = [("max_iterations", C.c_int32), ("max_trials", C.c_int32), ("cg_max_iterations", C.c_int32), ("cg_batch", C.c_int32),
+                ("cg_tol", C.c_double), ("min_rel_decrease", C.c_double), ("baseline", C.c_double), ("chi2_mono", C.c_double),
+                ("chi2_stereo", C.c_double), ("rounds", C.c_int32), ("robust_rounds", C.c_int32), ("iterations", C.c_int32 * 4)]
+
+
+class SbaResult(C.Structure):
+    """ygz_sba_result; `lambda_` is the header's `lambda`"""
+    _fields_ = [("cost_initial", C.c_double * 4), ("cost_final", C.c_double * 4), ("lambda_", C.c_double * 4), ("rounds_run", C.c_int32),
+                ("launches", C.c_int32), ("status", C.c_int32 * 4), ("lm_iterations", C.c_int32 * 4), ("n_solves", C.c_int32 * 4),
+                ("cg_iterations", C.c_int32 * 4), ("cg_capped", C.c_int32 * 4), ("inliers", C.c_int32 * 4)]
+
+    def to_dict(self):
+        return dict((k, getattr(self, k) if k in ("rounds_run", "launches") else np.array(getattr(self, k))) for k, _ in self._fields_)
+
+
+def default_sba_params():
+    p = SbaParams()
+    load().ygz_hip_default_sba_params(C.byref(p))
+    return p
+
+
+def _sba_params(**kw):
+    p = default_sba_params()
+    for k, v in kw.items():
+        if v is None:
+            continue
+        if k == "iterations":
+            v = list(v) + [0] * (4 - len(v))
+            for i in range(4):
+                p.iterations[i] = int(v[i])
+        else:
+            setattr(p, k, v)
+    return p
+
+
+def sba_arrays(poses, fixed, points, edge_pose, edge_point, obs, kind, level):
+    """the eight arrays of a stereo bundle-adjustment problem in the ABI's types: gba_arrays' with obs [E][3], kind [E] uint8, level [E] int32"""
+    obs = np.ascontiguousarray(obs, np.float64).reshape(-1, 3)
+    poses, fixed, points, edge_pose, edge_point, _ = gba_arrays(poses, fixed, points, edge_pose, edge_point, obs[:, :2])
+    kind = np.ascontiguousarray(kind, np.uint8).reshape(-1)
+    level = np.ascontiguousarray(level, np.int32).reshape(-1)
+    if not len(kind) == len(level) == len(obs):
+        raise ValueError("kind / level / obs differ in length")
+    return poses, fixed, points, edge_pose, edge_point, obs, kind, level
+
+
+def sba_argtypes(lib):
+    dp, ip, bp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
+    problem = [C.c_void_p, C.c_int, dp, bp, C.c_int, dp, C.c_int, ip, ip, dp, bp, ip, dp, C.POINTER(SbaParams)]
+    lib.ygz_hip_stereo_ba.argtypes = problem + [dp, dp, bp, dp, C.POINTER(SbaResult)]
+    lib.ygz_hip_sba_linearize.argtypes = problem + [dp] * 9
+
+
 def kfdb_argtypes(lib):
     dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
     lib.ygz_hip_kfdb_create.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
@@ -486,6 +541,7 @@ ABI_SYMBOLS = [
     "ygz_hip_default_pgo_params", "ygz_hip_pose_graph_optimize", "ygz_hip_pgo_linearize",
     "ygz_hip_distinctive_descriptors", "ygz_hip_covisibility",
     "ygz_hip_default_gba_params", "ygz_hip_global_ba", "ygz_hip_gba_linearize",
+    "ygz_hip_default_sba_params", "ygz_hip_stereo_ba", "ygz_hip_sba_linearize",
     "ygz_hip_kfdb_create", "ygz_hip_kfdb_destroy", "ygz_hip_kfdb_add", "ygz_hip_kfdb_erase", "ygz_hip_kfdb_clear", "ygz_hip_kfdb_info", "ygz_hip_kfdb_query",
     "ygz_hip_default_cull_params", "ygz_hip_keyframe_redundancy", "ygz_hip_cull_keyframes",
     "ygz_hip_default_undistort_params", "ygz_hip_set_undistortion", "ygz_hip_undistort_map", "ygz_hip_build_pyramid_undistorted",
@@ -510,6 +566,9 @@ GBA_SYMBOLS = ["ygz_hip_default_gba_params", "ygz_hip_global_ba", "ygz_hip_gba_l
 GBA_MAX_POSES, GBA_MAX_POINTS, GBA_MAX_EDGES = 4096, 1048576, 4194304
 GBA_FAILED, GBA_CONVERGED, GBA_MAX_ITERATIONS, GBA_STALLED = 0, 1, 2, 3
 GBA_HUBER = 5.991
+
+SBA_SYMBOLS = ["ygz_hip_default_sba_params", "ygz_hip_stereo_ba", "ygz_hip_sba_linearize"]
+SBA_MAX_ROUNDS = 4
 
 KFDB_SYMBOLS = ["ygz_hip_kfdb_create", "ygz_hip_kfdb_destroy", "ygz_hip_kfdb_add", "ygz_hip_kfdb_erase", "ygz_hip_kfdb_clear", "ygz_hip_kfdb_info",
                 "ygz_hip_kfdb_query"]
@@ -1626,6 +1685,51 @@ class HipContext:
                                             *[_p(o[k], C.c_double) for k in ("res", "w", "Jp", "Jl", "Hpp", "bp", "Hll", "bl")], _p(cost, C.c_double))
         if rc != E_STATE:
             self._chk(rc, "gba_linearize")
+        o.update(ok=rc == OK, cost=float(cost[0]))
+        return o
+
+    # ---- stereo bundle adjustment
+
+    def default_sba_params(self):
+        """ygz_hip_default_sba_params as a dict"""
+        p = default_sba_params()
+        return dict((k, list(getattr(p, k)) if k == "iterations" else getattr(p, k)) for k, _ in p._fields_)
+
+    def stereo_ba(self, poses, fixed, points, edge_pose, edge_point, obs, kind, level, K4, want_flags=True, **params):
+        """mono and stereo edges, rounds of LM with the edges classified in between (ygz_hip_stereo_ba): dict(poses [N][7], points [L][3],
+        outlier [E], chi2 [E] (None without want_flags: NULL is passed), rounds_run and the per-round arrays of ygz_sba_result).  params: the
+        fields of ygz_sba_params; iterations is a list of up to four"""
+        poses, fixed, points, ep, el, obs, kind, level = sba_arrays(poses, fixed, points, edge_pose, edge_point, obs, kind, level)
+        K = np.ascontiguousarray(K4, np.float64).reshape(4)
+        prm, res, po, xo = _sba_params(**params), SbaResult(), np.zeros_like(poses), np.zeros_like(points)
+        out, chi2 = (np.zeros(len(ep), np.uint8), np.zeros(len(ep))) if want_flags else (None, None)
+        sba_argtypes(self.lib)
+        self._chk(self.lib.ygz_hip_stereo_ba(self._ctx, len(poses), _p(poses, C.c_double), _p(fixed, C.c_uint8), len(points), _p(points, C.c_double),
+                                             len(ep), _p(ep, C.c_int32), _p(el, C.c_int32), _p(obs, C.c_double), _p(kind, C.c_uint8),
+                                             _p(level, C.c_int32), _p(K, C.c_double), C.byref(prm), _p(po, C.c_double), _p(xo, C.c_double),
+                                             _p(out, C.c_uint8) if want_flags else None, _p(chi2, C.c_double) if want_flags else None,
+                                             C.byref(res)), "stereo_ba")
+        d = res.to_dict()
+        d.update(poses=po, points=xo, outlier=out, chi2=chi2)
+        return d
+
+    def sba_linearize(self, poses, fixed, points, edge_pose, edge_point, obs, kind, level, K4, **params):
+        """the linearisation at the input (ygz_hip_sba_linearize): dict(ok, res [E][3], w [E], Jp [E][3][6], Jl [E][3][3], Hpp [N][21], bp
+        [N][6], Hll [L][6], bl [L][3], cost); ok is False when a present edge is undefined"""
+        poses, fixed, points, ep, el, obs, kind, level = sba_arrays(poses, fixed, points, edge_pose, edge_point, obs, kind, level)
+        K = np.ascontiguousarray(K4, np.float64).reshape(4)
+        N, L, E = len(poses), len(points), len(ep)
+        prm = _sba_params(**params)
+        o = dict(res=np.zeros((E, 3)), w=np.zeros(E), Jp=np.zeros((E, 3, 6)), Jl=np.zeros((E, 3, 3)), Hpp=np.zeros((N, 21)), bp=np.zeros((N, 6)),
+                 Hll=np.zeros((L, 6)), bl=np.zeros((L, 3)))
+        cost = np.zeros(1)
+        sba_argtypes(self.lib)
+        rc = self.lib.ygz_hip_sba_linearize(self._ctx, N, _p(poses, C.c_double), _p(fixed, C.c_uint8), L, _p(points, C.c_double), E, _p(ep, C.c_int32),
+                                            _p(el, C.c_int32), _p(obs, C.c_double), _p(kind, C.c_uint8), _p(level, C.c_int32), _p(K, C.c_double),
+                                            C.byref(prm), *[_p(o[k], C.c_double) for k in ("res", "w", "Jp", "Jl", "Hpp", "bp", "Hll", "bl")],
+                                            _p(cost, C.c_double))
+        if rc != E_STATE:
+            self._chk(rc, "sba_linearize")
         o.update(ok=rc == OK, cost=float(cost[0]))
         return o
 

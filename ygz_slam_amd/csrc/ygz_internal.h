@@ -253,9 +253,9 @@ enum { SCR_MATCH_Q = 0, SCR_MATCH_T, SCR_ALIGN_IN, SCR_ALIGN_OUT, SCR_SA_IN, SCR
        SCR_BA_CHI2,              // ba.hip: its per-edge chi2
        SCR_LMAP_ASYNC,           // align.hip: ygz_hip_find_direct_projection_mp_begin .. _end (lives across the two calls)
        // the packed blocks of the entry points that go through ygz_blob_open, one each
-       SCR_INIT, SCR_PNP, SCR_SIM3, SCR_PROJ, SCR_PGO, SCR_MAP, SCR_GBA, SCR_KFDB, SCR_CULL, SCR_STEREO,
-       SCR_LAST = SCR_STEREO };
-static_assert(SCR_GEN_0 == 16 && SCR_INIT == 27 && SCR_LAST == 36, "the scratch ids keep their values");
+       SCR_INIT, SCR_PNP, SCR_SIM3, SCR_PROJ, SCR_PGO, SCR_MAP, SCR_GBA, SCR_KFDB, SCR_CULL, SCR_STEREO, SCR_SBA,
+       SCR_LAST = SCR_SBA };
+static_assert(SCR_GEN_0 == 16 && SCR_INIT == 27 && SCR_STEREO == 36 && SCR_LAST == 37, "the scratch ids keep their values");
 static_assert(SCR_LAST < YGZ_N_SCRATCH, "ygz_hip_ctx::scratch holds every id");
 
 int ygz_scratch(ygz_hip_ctx *ctx, int id, size_t bytes, void **out);
