@@ -7,4 +7,5 @@
 #include "ygz/Basic/MapPoint.h"
 #include "ygz/Basic/Frame.h"
 #include "ygz/Basic/Memory.h"
+#include "ygz/Basic/StereoRig.h"
 #endif

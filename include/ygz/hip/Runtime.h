@@ -21,7 +21,12 @@ public:
     int Resident(Frame *f);             // HBM slot of f (uploads / rebuilds the pyramid if it was evicted)
     // image (CV_8UC3 BGR or CV_8UC1) into slot + its pyramid; through the lens undistortion (ygz_hip_build_pyramid_undistorted, the map set once per
     // camera) when Frame's camera -- or, without one, the configuration -- has a non-zero k1, k2, p1 or p2; otherwise exactly the calls made before
+    // A slot whose frame belongs to a stereo rig (SetRigCamera) goes through that camera's rectifying map instead (ygz_hip_build_pyramid_rectified)
     bool UploadColor(int slot, const cv::Mat &image);
+    // Frames of a stereo rig (ygz::StereoRig::InitPair): f was taken by rig camera 0 or 1, so every upload of its _color -- the first one and the
+    // one after an eviction -- is rectified; camera < 0 forgets f, and so does Release.  RigCamera: -1 for a frame of no rig
+    void SetRigCamera(Frame *f, int camera);
+    int RigCamera(const Frame *f);
     void Release(Frame *f);
     void RegisterLevels(Frame *f);
     bool FindLevel(const uint8_t *data, Frame **f, int *level);

@@ -65,7 +65,9 @@ extern "C" {
  * Still 6: stereo input added (ygz_stereo_params, ygz_hip_default_stereo_params, ygz_hip_stereo_depths_slots, ygz_hip_stereo_match,
  * ygz_hip_stereo_candidates) -- no existing argument list changed.
  * Still 6: stereo pose optimisation added (ygz_pose_opt_params, ygz_hip_default_pose_opt_params, ygz_hip_optimize_pose_stereo) -- no existing
- * argument list changed. */
+ * argument list changed.
+ * Still 6: stereo rectification added (ygz_rectify_params, ygz_hip_stereo_rectify, ygz_hip_default_rectify_params, ygz_hip_set_rectification,
+ * ygz_hip_rectify_map, ygz_hip_build_pyramid_rectified) -- no existing argument list changed. */
 #define YGZ_HIP_ABI_VERSION 6
 
 typedef struct ygz_hip_ctx ygz_hip_ctx;
@@ -169,6 +171,36 @@ int  ygz_hip_undistort_map(ygz_hip_ctx *ctx, int32_t *qx, int32_t *qy);
  * is first copied aside on the same stream).  One call: the remap, the pyramid and the tracker's framed copies follow one another on one
  * stream, also beside a trailing LK launch.  YGZ_E_STATE without a map.  ygz_hip_build_pyramid itself never undistorts. */
 int  ygz_hip_build_pyramid_undistorted(ygz_hip_ctx *ctx, int slot_begin, int n_slots, int from_bgr);
+
+/* ---- A0b: stereo rectification in front of the pyramid -- the raw pictures of a two-camera rig resampled so that both are seen by the
+ * context's ideal camera and epipolar lines are image rows, which is what ygz_hip_stereo_depths_slots, ygz_hip_optimize_pose_stereo and
+ * ygz_hip_stereo_ba assume.  The model is OpenCV's: stereoRectify (Bouguet's method) for the two rotations, initUndistortRectifyMap with
+ * R = R1 or R2 for the map of each camera, remap as above.  The map of camera k differs from the lens-only one in its first step: with
+ * (x0, y0) = ((u - cx_d) / fx_d, (v - cy_d) / fy_d) and r = R row-major,  X = (r0 x0 + r3 y0) + r6,  Y = (r1 x0 + r4 y0) + r7,
+ * W = (r2 x0 + r5 y0) + r8  (that is R^T (x0, y0, 1)),  x = X / W,  y = Y / W;  !(W > 0) is outside.  The rotations, the maps and the images
+ * are bit-identical to tests/rect_ref.c.  The output camera is the context's, so bf = fx * baseline. */
+#define YGZ_RECT_CAMERAS 2
+typedef struct {
+    ygz_undistort_params lens;          /* the camera that took the picture */
+    double R[9];                        /* row-major: R1 (camera 0) or R2 (camera 1) of ygz_hip_stereo_rectify */
+} ygz_rectify_params;                   /* 152 bytes */
+/* the rotations of a rig with X_right = R X_left + T (row-major): R1, R2 turn the left and the right camera's rays into the common rectified
+ * frame, in which the right camera sits `baseline` to the right of the left one.  Host code: no device, no context.  YGZ_E_INVALID for a
+ * null argument, a value that is not finite, T = 0, an R that is no rotation (max |R R^T - I| > 1e-6 or det <= 0), cameras 120 degrees or
+ * more apart, and a second camera that is not to the right of the first (after the half rotation: t[0] >= 0 or |t[0]| < max(|t[1]|, |t[2]|)) */
+int  ygz_hip_stereo_rectify(const double R[9], const double T[3], double R1[9], double R2[9], double *baseline);
+/* the default lens (ygz_hip_default_undistort_params) and R = I.  YGZ_E_INVALID for a null argument */
+int  ygz_hip_default_rectify_params(const ygz_hip_ctx *ctx, ygz_rectify_params *p);
+/* builds the map of rig camera `camera` (0 or 1) and the table of its tiles' source boxes (two launches, synchronous); p == NULL drops them.
+ * Independent of ygz_hip_set_undistortion.  YGZ_E_INVALID for a camera outside [0, YGZ_RECT_CAMERAS), the lens rules of
+ * ygz_hip_set_undistortion, an R that is not finite or no rotation (as above); last, for a null context */
+int  ygz_hip_set_rectification(ygz_hip_ctx *ctx, int camera, const ygz_rectify_params *p);
+/* the map of a camera, qx and qy [h][w] (test aid; synchronises).  YGZ_E_STATE without a map */
+int  ygz_hip_rectify_map(ygz_hip_ctx *ctx, int camera, int32_t *qx, int32_t *qy);
+/* ygz_hip_build_pyramid with level 0 of slot slot_begin + i = its upload through the map of camera camera_of_slot[i] (0 or 1), all slots of
+ * both cameras in one launch; otherwise as ygz_hip_build_pyramid_undistorted.  YGZ_E_INVALID for a null table or an entry outside
+ * [0, YGZ_RECT_CAMERAS); YGZ_E_STATE when a named camera has no map */
+int  ygz_hip_build_pyramid_rectified(ygz_hip_ctx *ctx, int slot_begin, int n_slots, int from_bgr, const uint8_t *camera_of_slot);
 
 /* ---- A2-A7: extractor -- replaces FeatureDetector::Detect
  *      (src/Algorithm/FeatureDetector.cpp:345-444: fast_corner_detect_10 + fast_corner_score_10

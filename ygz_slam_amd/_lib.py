@@ -484,6 +484,34 @@ def undistort_argtypes(lib):
     lib.ygz_hip_build_pyramid_undistorted.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
 
 
+class RectifyParams(C.Structure):
+    """ygz_rectify_params (include/ygz_hip.h)"""
+    _fields_ = [("lens", UndistortParams), ("R", C.c_double * 9)]
+
+
+def rectify_argtypes(lib):
+    ip, dp, pp = C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(RectifyParams)
+    lib.ygz_hip_stereo_rectify.argtypes = [dp, dp, dp, dp, dp]
+    lib.ygz_hip_default_rectify_params.argtypes = [C.c_void_p, pp]
+    lib.ygz_hip_set_rectification.argtypes = [C.c_void_p, C.c_int, pp]
+    lib.ygz_hip_rectify_map.argtypes = [C.c_void_p, C.c_int, ip, ip]
+    lib.ygz_hip_build_pyramid_rectified.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint8)]
+
+
+def stereo_rectify(R, T):
+    """ygz_hip_stereo_rectify (host code, no device): (R1 [3, 3], R2 [3, 3], baseline) of the rig X_right = R X_left + T; RuntimeError when
+    the rig is refused"""
+    lib = load()
+    rectify_argtypes(lib)
+    R = np.ascontiguousarray(R, np.float64).reshape(9)
+    T = np.ascontiguousarray(T, np.float64).reshape(3)
+    R1, R2, b = np.zeros(9), np.zeros(9), C.c_double(0)
+    rc = lib.ygz_hip_stereo_rectify(_p(R, C.c_double), _p(T, C.c_double), _p(R1, C.c_double), _p(R2, C.c_double), C.byref(b))
+    if rc != 0:
+        raise RuntimeError("ygz_hip_stereo_rectify: error %d" % rc)
+    return R1.reshape(3, 3), R2.reshape(3, 3), b.value
+
+
 class StereoParams(C.Structure):
     """ygz_stereo_params (include/ygz_hip.h)"""
     _fields_ = [("baseline", C.c_double), ("min_disparity", C.c_double), ("max_disparity", C.c_double), ("th_dist", C.c_int), ("write_depths", C.c_int)]
@@ -547,6 +575,7 @@ ABI_SYMBOLS = [
     "ygz_hip_default_undistort_params", "ygz_hip_set_undistortion", "ygz_hip_undistort_map", "ygz_hip_build_pyramid_undistorted",
     "ygz_hip_default_stereo_params", "ygz_hip_stereo_depths_slots", "ygz_hip_stereo_match", "ygz_hip_stereo_candidates",
     "ygz_hip_default_pose_opt_params", "ygz_hip_optimize_pose_stereo",
+    "ygz_hip_stereo_rectify", "ygz_hip_default_rectify_params", "ygz_hip_set_rectification", "ygz_hip_rectify_map", "ygz_hip_build_pyramid_rectified",
 ]
 INIT_SYMBOLS = ["ygz_hip_default_init_params", "ygz_hip_initialize", "ygz_hip_init_sample_sets", "ygz_hip_init_hypotheses", "ygz_hip_init_reconstruct"]
 INIT_NONE, INIT_H, INIT_F = 0, 1, 2
@@ -579,6 +608,10 @@ CULL_MAX_KEYFRAMES = 4096
 
 UNDISTORT_SYMBOLS = ["ygz_hip_default_undistort_params", "ygz_hip_set_undistortion", "ygz_hip_undistort_map", "ygz_hip_build_pyramid_undistorted"]
 UNDISTORT_OUTSIDE = -2 ** 31
+
+RECTIFY_SYMBOLS = ["ygz_hip_stereo_rectify", "ygz_hip_default_rectify_params", "ygz_hip_set_rectification", "ygz_hip_rectify_map",
+                   "ygz_hip_build_pyramid_rectified"]
+RECT_CAMERAS = 2
 
 STEREO_SYMBOLS = ["ygz_hip_default_stereo_params", "ygz_hip_stereo_depths_slots", "ygz_hip_stereo_match", "ygz_hip_stereo_candidates"]
 STEREO_OK, STEREO_NO_CANDIDATE, STEREO_DESCRIPTOR, STEREO_BORDER, STEREO_EDGE, STEREO_DISPARITY, STEREO_MEDIAN = range(7)
@@ -1025,6 +1058,41 @@ class HipContext:
 
     def build_pyramid_undistorted(self, slot_begin=0, n_slots=1, from_bgr=False):
         self._chk(self.lib.ygz_hip_build_pyramid_undistorted(self._ctx, slot_begin, n_slots, int(from_bgr)), "build_pyramid_undistorted")
+
+    # ---- stereo rectification
+    def default_rectify_params(self):
+        p = RectifyParams()
+        rectify_argtypes(self.lib)
+        self._chk(self.lib.ygz_hip_default_rectify_params(self._ctx, C.byref(p)), "default_rectify_params")
+        return p
+
+    def set_rectification(self, camera, R=None, drop=False, **lens):
+        """builds the map and the tile table of rig camera `camera` from the defaults (the context's camera, no distortion, border 0, R = I)
+        with R [3, 3] and the given fields of the lens replaced; drop=True removes them"""
+        rectify_argtypes(self.lib)
+        if drop:
+            self._chk(self.lib.ygz_hip_set_rectification(self._ctx, camera, None), "set_rectification")
+            return None
+        p = self.default_rectify_params()
+        for k, v in lens.items():
+            setattr(p.lens, k, v)
+        if R is not None:
+            p.R[:] = [float(v) for v in np.asarray(R, np.float64).reshape(9)]
+        self._chk(self.lib.ygz_hip_set_rectification(self._ctx, camera, C.byref(p)), "set_rectification")
+        return p
+
+    def rectify_map(self, camera):
+        """(qx, qy) [h, w] int32 of a rig camera: source positions in 1/32 pixel, UNDISTORT_OUTSIDE in both where the picture has nothing"""
+        rectify_argtypes(self.lib)
+        qx, qy = np.empty((self.height, self.width), np.int32), np.empty((self.height, self.width), np.int32)
+        self._chk(self.lib.ygz_hip_rectify_map(self._ctx, camera, _p(qx, C.c_int32), _p(qy, C.c_int32)), "rectify_map")
+        return qx, qy
+
+    def build_pyramid_rectified(self, camera_of_slot, slot_begin=0, from_bgr=False):
+        """level 0 of slot slot_begin + i = its upload through the map of rig camera camera_of_slot[i]"""
+        rectify_argtypes(self.lib)
+        cams = np.ascontiguousarray(camera_of_slot, np.uint8).reshape(-1)
+        self._chk(self.lib.ygz_hip_build_pyramid_rectified(self._ctx, slot_begin, len(cams), int(from_bgr), _p(cams, C.c_uint8)), "build_pyramid_rectified")
 
     def level_size(self, level):
         w, h = C.c_int(0), C.c_int(0)

@@ -321,6 +321,7 @@ void ygz_hip_destroy(ygz_hip_ctx *ctx)
     ygz_hip_vocab_free(ctx);
     ygz_kf_store_free(ctx);
     ygz_undistort_free(ctx);
+    ygz_rectify_free(ctx);
     if (ctx->stage) (void)hipHostFree(ctx->stage);
     if (ctx->depth_img) (void)hipFree(ctx->depth_img);
     if (ctx->ev_xctx) (void)hipEventDestroy(ctx->ev_xctx);
@@ -518,7 +519,7 @@ static const char *const k_kernel_names[KID_COUNT] = {
     "k_bgr2gray", "k_pyr_down", "k_fast_select", "k_compact", "k_describe", "k_hamming_nn", "k_match_finalize", "k_track_load",
     "k_find_direct_projection", "k_align2d", "k_sparse_align", "k_scharr", "k_klt", "k_klt_pad", "k_ba_pose_prep", "k_ba_points", "k_ba_final",
     "k_ba_chi2", "k_pose_only_ba", "k_ba_lm", "k_bow_transform", "k_bow_match", "k_depth_from_triangulation", "k_lmap_match", "k_lmap_aux",
-    "k_match_postfilter", "k_track_aux", "k_depth_filter", "k_window", "k_undistort", "k_stereo_match", "k_stereo_median", "k_pose_opt" };
+    "k_match_postfilter", "k_track_aux", "k_depth_filter", "k_window", "k_undistort", "k_stereo_match", "k_stereo_median", "k_pose_opt", "k_rectify" };
 
 int ygz_hip_probe_begin(ygz_hip_ctx *ctx, const char *kernel_name, int max_launches)
 {
@@ -623,13 +624,16 @@ static int klt_flip_sets(ygz_hip_ctx *ctx)
     return YGZ_OK;
 }
 
-// the one body of ygz_hip_build_pyramid and ygz_hip_build_pyramid_undistorted (undistort: level 0 is first remapped through the map)
-static int build_pyramid_body(ygz_hip_ctx *ctx, int slot_begin, int n_slots, int from_bgr, bool undistort)
+// the one body of ygz_hip_build_pyramid, ygz_hip_build_pyramid_undistorted and ygz_hip_build_pyramid_rectified: level 0 is first remapped through
+// the lens-only map (YGZ_REMAP_LENS) or through the maps of the slots' rig cameras (YGZ_REMAP_RIG, camera_of_slot [n_slots])
+enum { YGZ_REMAP_NONE = 0, YGZ_REMAP_LENS, YGZ_REMAP_RIG };
+static int build_pyramid_remapped(ygz_hip_ctx *ctx, int remap, const uint8_t *camera_of_slot, int slot_begin, int n_slots, int from_bgr)
 {
     YgzDeviceGuard dg_(ctx, YGZ_HEAD_CALL);
     if (!ctx || slot_begin < 0 || n_slots < 1 || slot_begin + n_slots > ctx->prm.max_frames) return YGZ_E_INVALID;
     if (from_bgr && !ctx->bgr) return YGZ_E_STATE;
-    if (undistort && (!ctx->undist_qx || !ctx->undist_qy)) return YGZ_E_STATE;
+    if (remap == YGZ_REMAP_LENS && (!ctx->undist_qx || !ctx->undist_qy)) return YGZ_E_STATE;
+    if (remap == YGZ_REMAP_RIG) for (int i = 0; i < n_slots; ++i) { const int c = camera_of_slot[i]; if (!ctx->rect_qx[c] || !ctx->rect_qy[c] || !ctx->rect_box[c]) return YGZ_E_STATE; }
     // LK is still at the tail of the main stream and this call rebuilds every slot its pair table names: the images go to the other set, and
     // this call and the rest of the head run beside that launch (it got its pointers by value).  A partial rebuild, or no trailing LK: as before,
     // on the main stream (behind LK) into the current set.
@@ -645,14 +649,20 @@ static int build_pyramid_body(ygz_hip_ctx *ctx, int slot_begin, int n_slots, int
         if (!ctx->head_aside) ctx->klt_prep_pending = false;   // (aside: the main stream has not waited)
     }
     // the flip, the join and the wait above happen once; the remap, the pyramid and the framed copies follow on this one stream in that order
-    // (level 0 then holds the undistorted gray, so the pyramid is built as from a gray upload and k_klt_frame writes the framed level 0)
-    int rc = undistort ? ygz_launch_undistort(ctx, slot_begin, n_slots, from_bgr) : YGZ_OK;
+    // (level 0 then holds the remapped gray, so the pyramid is built as from a gray upload and k_klt_frame writes the framed level 0)
+    int rc = YGZ_OK;
+    if (remap == YGZ_REMAP_LENS) rc = ygz_launch_undistort(ctx, slot_begin, n_slots, from_bgr);
+    else if (remap == YGZ_REMAP_RIG) rc = ygz_launch_rectify(ctx, slot_begin, n_slots, from_bgr, camera_of_slot);
     if (rc != YGZ_OK) return rc;
-    rc = ygz_launch_gray_pyramid(ctx, slot_begin, n_slots, undistort ? 0 : from_bgr, ctx->n_levels_alloc);
+    rc = ygz_launch_gray_pyramid(ctx, slot_begin, n_slots, remap != YGZ_REMAP_NONE ? 0 : from_bgr, ctx->n_levels_alloc);
     if (rc != YGZ_OK) return rc;
     for (int s = slot_begin; s < slot_begin + n_slots; ++s) ctx->pyr_valid[s] = 1;
     ctx->klt_prep_valid = false;
     return YGZ_OK;
+}
+static int build_pyramid_body(ygz_hip_ctx *ctx, int slot_begin, int n_slots, int from_bgr, bool undistort)
+{
+    return build_pyramid_remapped(ctx, undistort ? YGZ_REMAP_LENS : YGZ_REMAP_NONE, nullptr, slot_begin, n_slots, from_bgr);
 }
 
 int ygz_hip_build_pyramid(ygz_hip_ctx *ctx, int slot_begin, int n_slots, int from_bgr)
@@ -663,6 +673,14 @@ int ygz_hip_build_pyramid(ygz_hip_ctx *ctx, int slot_begin, int n_slots, int fro
 int ygz_hip_build_pyramid_undistorted(ygz_hip_ctx *ctx, int slot_begin, int n_slots, int from_bgr)
 {
     return build_pyramid_body(ctx, slot_begin, n_slots, from_bgr, true);
+}
+
+int ygz_hip_build_pyramid_rectified(ygz_hip_ctx *ctx, int slot_begin, int n_slots, int from_bgr, const uint8_t *camera_of_slot)
+{
+    if (!camera_of_slot || n_slots < 1 || slot_begin < 0) return YGZ_E_INVALID;       // parameters first, the context last
+    if (ctx && n_slots > ctx->prm.max_frames - slot_begin) return YGZ_E_INVALID;       // (before the table is read up to n_slots)
+    for (int i = 0; i < n_slots; ++i) if (camera_of_slot[i] >= YGZ_RECT_CAMERAS) return YGZ_E_INVALID;
+    return build_pyramid_remapped(ctx, YGZ_REMAP_RIG, camera_of_slot, slot_begin, n_slots, from_bgr);
 }
 
 int ygz_hip_download_level(ygz_hip_ctx *ctx, int slot, int level, uint8_t *dst)

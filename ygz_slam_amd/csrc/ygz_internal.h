@@ -169,6 +169,11 @@ struct ygz_hip_ctx {
     int32_t *undist_qx = nullptr, *undist_qy = nullptr;
     ygz_undistort_params undist_prm = {};
     uint8_t *undist_plane = nullptr; size_t undist_plane_bytes = 0;
+    // stereo rectification (rectify.hip): per camera of the rig the map (as above) and the table of its 64 x 32 tiles' source boxes, while a map
+    // is set; independent of the lens-only map.  Gray uploads go aside into undist_plane
+    int32_t *rect_qx[YGZ_RECT_CAMERAS] = {nullptr, nullptr}, *rect_qy[YGZ_RECT_CAMERAS] = {nullptr, nullptr};
+    void *rect_box[YGZ_RECT_CAMERAS] = {nullptr, nullptr};
+    ygz_rectify_params rect_prm[YGZ_RECT_CAMERAS] = {};
 };
 
 #define YGZ_HIPCHK(ctx, call)                                            \
@@ -214,7 +219,7 @@ struct YgzDeviceGuard {
 // kernel ids for the probe
 enum { KID_BGR2GRAY = 0, KID_PYR_DOWN, KID_FAST_SELECT, KID_COMPACT, KID_DESCRIBE, KID_HAMMING_NN, KID_MATCH_FINALIZE,
        KID_TRACK_LOAD, KID_FDP, KID_ALIGN2D, KID_SPARSE_ALIGN, KID_SCHARR, KID_KLT, KID_KLT_PAD, KID_BA_POSE_PREP, KID_BA_POINTS,
-       KID_BA_POSES, KID_BA_CHI2, KID_POSE_ONLY, KID_BA_LM, KID_BOW_TRANSFORM, KID_BOW_MATCH, KID_DEPTH_TRI, KID_LMAP_MATCH, KID_LMAP_AUX, KID_MATCH_POSTFILTER, KID_TRACK_AUX, KID_DEPTH_FILTER, KID_WINDOW, KID_UNDISTORT, KID_STEREO_MATCH, KID_STEREO_MEDIAN, KID_POSE_OPT, KID_COUNT };
+       KID_BA_POSES, KID_BA_CHI2, KID_POSE_ONLY, KID_BA_LM, KID_BOW_TRANSFORM, KID_BOW_MATCH, KID_DEPTH_TRI, KID_LMAP_MATCH, KID_LMAP_AUX, KID_MATCH_POSTFILTER, KID_TRACK_AUX, KID_DEPTH_FILTER, KID_WINDOW, KID_UNDISTORT, KID_STEREO_MATCH, KID_STEREO_MEDIAN, KID_POSE_OPT, KID_RECTIFY, KID_COUNT };
 
 #define YGZ_LAUNCH(ctx, kid, kern, grid, block, ...)                                                         \
     do { const bool pr_ = (ctx)->probe_id == (kid) && (ctx)->probe_used + 2 <= (int)(ctx)->probe_ev.size();    \
@@ -253,9 +258,9 @@ enum { SCR_MATCH_Q = 0, SCR_MATCH_T, SCR_ALIGN_IN, SCR_ALIGN_OUT, SCR_SA_IN, SCR
        SCR_BA_CHI2,              // ba.hip: its per-edge chi2
        SCR_LMAP_ASYNC,           // align.hip: ygz_hip_find_direct_projection_mp_begin .. _end (lives across the two calls)
        // the packed blocks of the entry points that go through ygz_blob_open, one each
-       SCR_INIT, SCR_PNP, SCR_SIM3, SCR_PROJ, SCR_PGO, SCR_MAP, SCR_GBA, SCR_KFDB, SCR_CULL, SCR_STEREO, SCR_SBA,
-       SCR_LAST = SCR_SBA };
-static_assert(SCR_GEN_0 == 16 && SCR_INIT == 27 && SCR_STEREO == 36 && SCR_LAST == 37, "the scratch ids keep their values");
+       SCR_INIT, SCR_PNP, SCR_SIM3, SCR_PROJ, SCR_PGO, SCR_MAP, SCR_GBA, SCR_KFDB, SCR_CULL, SCR_STEREO, SCR_SBA, SCR_RECT,
+       SCR_LAST = SCR_RECT };
+static_assert(SCR_GEN_0 == 16 && SCR_INIT == 27 && SCR_STEREO == 36 && SCR_SBA == 37 && SCR_LAST == 38, "the scratch ids keep their values");
 static_assert(SCR_LAST < YGZ_N_SCRATCH, "ygz_hip_ctx::scratch holds every id");
 
 int ygz_scratch(ygz_hip_ctx *ctx, int id, size_t bytes, void **out);
@@ -338,6 +343,8 @@ int ygz_ensure_levels(ygz_hip_ctx *ctx, int n_levels);      // allocates image l
 int ygz_launch_gray_pyramid(ygz_hip_ctx *ctx, int slot_begin, int n_slots, int from_bgr, int up_to_level);
 int ygz_launch_undistort(ygz_hip_ctx *ctx, int slot_begin, int n_slots, int from_bgr);      // undistort.hip: level 0 = the undistorted gray of the uploads
 void ygz_undistort_free(ygz_hip_ctx *ctx);
+int ygz_launch_rectify(ygz_hip_ctx *ctx, int slot_begin, int n_slots, int from_bgr, const uint8_t *camera_of_slot);   // rectify.hip: level 0 = the slots' uploads through their cameras' rectifying maps
+void ygz_rectify_free(ygz_hip_ctx *ctx);
 int ygz_launch_detect(ygz_hip_ctx *ctx, int slot_begin, int n_slots);
 int ygz_launch_describe(ygz_hip_ctx *ctx, int slot_begin, int n_slots);
 int ygz_track_ensure(ygz_hip_ctx *ctx);                      // allocates the resident tracking state

@@ -81,6 +81,7 @@ struct Runtime::Impl {
     std::map<const uint8_t *, std::pair<Frame *, int>> level_of;     // host level data -> (frame, level)
     FdpMemo fdp;
     bool undist_set = false; float undist_cam[8] = {0};              // the camera the context's undistortion map was built for (k1 k2 p1 p2 fx fy cx cy)
+    std::map<const Frame *, int> rig_camera;                          // frames of a stereo rig -> the camera that took them (StereoRig::InitPair)
 };
 Runtime &Runtime::Get() { static Runtime r; return r; }
 Runtime::Runtime() : p_(new Impl) {}
@@ -114,9 +115,12 @@ ygz_hip_ctx *Runtime::ctx()
     return p_->ctx;
 }
 int Runtime::cells() { ctx(); return p_->cells; }
+void Runtime::SetRigCamera(Frame *f, int camera) { if (camera < 0) p_->rig_camera.erase(f); else p_->rig_camera[f] = camera; }
+int Runtime::RigCamera(const Frame *f) { auto it = p_->rig_camera.find(f); return it == p_->rig_camera.end() ? -1 : it->second; }
 void Runtime::Release(Frame *f)
 {
     p_->fdp.forget(f);
+    p_->rig_camera.erase(f);
     for (auto it = p_->level_of.begin(); it != p_->level_of.end();) { if (it->second.first == f) it = p_->level_of.erase(it); else ++it; }
     if (f->_hip_slot >= 0 && f->_hip_slot < (int)p_->owner.size() && p_->owner[f->_hip_slot] == f) p_->owner[f->_hip_slot] = nullptr;
     f->_hip_slot = -1;
@@ -137,6 +141,11 @@ bool Runtime::UploadColor(int slot, const cv::Mat &image)
     ygz_hip_ctx *c = ctx();
     const int bgr = image.channels() == 3;
     if (!check(bgr ? ygz_hip_upload_bgr(c, slot, image.data, (int)image.step) : ygz_hip_upload_gray(c, slot, image.data, (int)image.step), "upload")) return false;
+    const int rig = slot >= 0 && slot < (int)p_->owner.size() && p_->owner[slot] ? RigCamera(p_->owner[slot]) : -1;
+    if (rig >= 0) {                                            // a frame of a stereo rig: its camera's rectifying map, set by StereoRig::Rectify
+        const uint8_t cam = (uint8_t)rig;
+        return check(ygz_hip_build_pyramid_rectified(c, slot, 1, bgr, &cam), "build_pyramid_rectified");
+    }
     const PinholeCamera *set = Frame::GetCamera();
     const PinholeCamera cam = set ? *set : PinholeCamera();
     if (!cam.HasDistortion()) return check(ygz_hip_build_pyramid(c, slot, 1, bgr), "build_pyramid");
