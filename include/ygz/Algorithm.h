@@ -14,4 +14,5 @@
 #include "ygz/Algorithm/StereoMatcher.h"
 #include "ygz/Algorithm/PoseOptimizer.h"
 #include "ygz/Algorithm/BundleAdjuster.h"
+#include "ygz/Algorithm/StereoMapper.h"
 #endif

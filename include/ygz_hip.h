@@ -67,7 +67,9 @@ extern "C" {
  * Still 6: stereo pose optimisation added (ygz_pose_opt_params, ygz_hip_default_pose_opt_params, ygz_hip_optimize_pose_stereo) -- no existing
  * argument list changed.
  * Still 6: stereo rectification added (ygz_rectify_params, ygz_hip_stereo_rectify, ygz_hip_default_rectify_params, ygz_hip_set_rectification,
- * ygz_hip_rectify_map, ygz_hip_build_pyramid_rectified) -- no existing argument list changed. */
+ * ygz_hip_rectify_map, ygz_hip_build_pyramid_rectified) -- no existing argument list changed.
+ * Still 6: stereo map-point creation added (ygz_smap_params, ygz_smap_problem, ygz_hip_default_smap_params, ygz_hip_stereo_create_map_points,
+ * ygz_hip_stereo_keyframe_points) -- no existing argument list changed. */
 #define YGZ_HIP_ABI_VERSION 6
 
 typedef struct ygz_hip_ctx ygz_hip_ctx;
@@ -1208,6 +1210,64 @@ int  ygz_hip_keyframe_redundancy(ygz_hip_ctx *ctx, int n_points, const int32_t *
 int  ygz_hip_cull_keyframes(ygz_hip_ctx *ctx, int n_points, const int32_t *offsets, const int32_t *kf, const int32_t *level, int n_keyframes,
                             int n_cand, const int32_t *cand, const ygz_cull_params *params, int32_t *culled, int32_t *tracked,
                             int32_t *redundant, uint8_t *point_dead);
+
+/* ---- stereo map-point creation -- nothing in the reference, whose LocalMapping::CreateNewMapPoints (ygz_hip_create_map_points) is monocular;
+ * ORB-SLAM2's two creation paths for a rectified rig (bf = fx * baseline; the pyramid's factor is 2: sigma^2 of level l is 4^l).  Poses are
+ * qx qy qz qw tx ty tz, world -> camera, unit quaternions; K4 = fx fy cx cy.  The arithmetic is that of tests/smap_ref.c (DESIGN.md section
+ * 24): FP64, uncontracted, no trigonometry; every output is bit-identical to it.
+ *
+ * Pairs (LocalMapping::CreateNewMapPoints with stereo): a problem is one (keyframe 1, keyframe 2) with its poses and n matched pairs -- px1,
+ * px2 [n][2] level-0 pixels, level1, level2 [n], ur1, ur2 [n] (< 0: the side is mono), depth1, depth2 [n] (read only where the side's ur is
+ * >= 0; may be NULL when no side of the problem is stereo).  Per pair, the first failing step sets the code:
+ *   rays xn = ((u - cx) / fx, (v - cy) / fy, 1), ray = R^T xn, cosRays = ray1 . ray2 / (|ray1| |ray2|);
+ *   stereo parallax cosS_k = (d_k^2 - b^2 / 4) / (d_k^2 + b^2 / 4) for side 1 when stereo, for side 2 only when side 1 is not stereo; a side
+ *   without it keeps cosRays + 1; cosS = min(cosS_1, cosS_2);
+ *   cosRays < cosS && cosRays > 0 && (stereo1 || stereo2 || cosRays < cos_parallax_max): method 1, linear triangulation (the null vector of the
+ *   rows xn.x T.row(2) - T.row(0), xn.y T.row(2) - T.row(1) of both cameras by a one-sided Jacobi; a fourth component of 0 or a non-finite
+ *   point: code 2); else stereo1 && cosS_1 < cosS_2: method 2, feature 1 un-projected with depth1; else stereo2 && cosS_2 < cosS_1: method 3,
+ *   feature 2 with depth2; else code 1 (method 0);
+ *   z1 <= 0: code 3; z2 <= 0: code 4; the reprojection in camera 1, then 2 (codes 5, 6): ex^2 + ey^2 > chi2_mono 4^level for a mono side,
+ *   ex^2 + ey^2 + (u - bf / z - ur)^2 > chi2_stereo 4^level for a stereo side; a distance to a camera centre of 0: code 7; with ratioDist =
+ *   dist2 / dist1 and ratioOctave = 2^level1 / 2^level2, ratioDist ratio_factor < ratioOctave || ratioDist > ratioOctave ratio_factor: code 8;
+ *   code 0: pos_world is the point (zero for every other code). */
+#define YGZ_SMAP_MAX_PROBLEMS 32
+#define YGZ_SMAP_MAX_PAIRS    65536      /* per call, over all problems */
+typedef struct {
+    double  baseline;                     /* 0.1: metres between the rig's cameras, > 0 */
+    double  chi2_mono, chi2_stereo;       /* 5.991, 7.8 (ORB-SLAM2's value in this function, not 7.815): > 0 */
+    double  cos_parallax_max;             /* 0.9998: two mono sides are triangulated below it only; > 0 */
+    double  ratio_factor;                 /* 3.0 = 1.5 x the pyramid's factor 2; >= 1 */
+    double  th_depth;                     /* 3.5 metres: a keyframe's feature up to it is close; > 0 */
+    int32_t min_close;                    /* 100: at least this many of the nearest features are walked; >= 0 */
+    int32_t pad;
+} ygz_smap_params;
+typedef struct {
+    double T1[7], T2[7];
+    const double *px1, *px2, *ur1, *ur2, *depth1, *depth2;
+    const int32_t *level1, *level2;
+    int n;
+} ygz_smap_problem;
+void ygz_hip_default_smap_params(ygz_smap_params *p);
+/* all pairs of all problems in one launch; the outputs run over the concatenated pairs in problem order: code, method [N], pos_world [N][3];
+ * counts [n_problems][2] (created = code 0, triangulated = code 0 by method 1) may be NULL.  params NULL: defaults.  One upload, one launch,
+ * one copy back and one wait.  Checked in this order, all before the device is touched: YGZ_E_INVALID for null problems, K4, code, method or
+ * pos_world or n_problems < 1; YGZ_E_CAPACITY above YGZ_SMAP_MAX_PROBLEMS; YGZ_E_INVALID for a problem's n < 0; YGZ_E_CAPACITY above
+ * YGZ_SMAP_MAX_PAIRS pairs in the call; YGZ_E_INVALID for a parameter that is not finite, baseline, a chi2, cos_parallax_max or th_depth <= 0,
+ * ratio_factor < 1, min_close < 0, a non-finite K4 or a focal length <= 0, a non-finite pose, a null array of a problem with n > 0 (depth_k
+ * only when a ur_k is >= 0), a non-finite pixel or ur, a non-finite depth of a stereo side; last, YGZ_E_INVALID for a null context and for a
+ * level outside the context's pyramid.  A problem with n = 0 is allowed. */
+int  ygz_hip_stereo_create_map_points(ygz_hip_ctx *ctx, int n_problems, const ygz_smap_problem *problems, const double K4[4],
+                                      const ygz_smap_params *params, int32_t *code, int32_t *method, double *pos_world, int32_t *counts);
+/* Keyframe insertion (Tracking::StereoInitialization / CreateNewKeyFrame): the features with depth > 0 are ranked by (depth, index)
+ * ascending; c of them have depth <= th_depth; the ranks 0 .. min(n_depth - 1, max(c, min_close)) are walked (ORB-SLAM2's loop breaks behind
+ * the first walked feature that is both beyond th_depth and past the min_close-th); selected = walked and has_point == 0.  rank [n]: the rank
+ * of a walked feature, selected or not, -1 for every other; selected [n]; pos_world [n][3] = R^T (z xn - t) of a selected feature, zero
+ * otherwise; n_depth, n_close (= c), n_selected may be NULL.  One upload, one launch (rank, selection and un-projection), one copy back and
+ * one wait.  YGZ_E_INVALID for a null T, K4 or (n > 0) array or output, n < 0, the parameter rules above, a non-finite K4, pose, pixel or
+ * depth; then for a null context; YGZ_E_CAPACITY for n above ygz_hip_max_keypoints.  n = 0 is allowed (no launch). */
+int  ygz_hip_stereo_keyframe_points(ygz_hip_ctx *ctx, const double T[7], int n, const double *px, const double *depth, const uint8_t *has_point,
+                                    const double K4[4], const ygz_smap_params *params, int32_t *rank, uint8_t *selected, double *pos_world,
+                                    int *n_depth, int *n_close, int *n_selected);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,250 @@
+"""tests/smap_ref.c, the restatement of stereo map-point creation, against a numpy witness written another way: rotation
+matrices and matrix products from numpy, np.linalg.svd for the null vector of the triangulation, the stereo parallax as the real
+cos(2 atan2(b / 2, d)), np.lexsort for the keyframe's ranking.  Codes and methods must be EQUAL for every pair the witness does not mark as
+near a threshold (a compared quantity within 1e-9 relative of its bound); marked pairs are a condition on the scenes, not a tolerance: at
+most 2 % of a scene, never a whole code class.  Also what the stereo columns buy on the forward-motion scene."""
+import numpy as np
+import pytest
+
+import smap_ref as sm
+
+REL = 1e-9
+N_SCENE = 600
+SEEDS = {"sideways": 11, "forward": 12, "mono": 13, "wrong": 14}
+
+# measured on the scenes below: the largest |X_ref - X_witness| / |X_witness| over the code-0 pairs is 4.78e-13 (a triangulation of the sideways
+# scene; 7.4e-14, 7.1e-14 and 3.4e-14 on the other three); asserted at 10 x (section 20's practice)
+POS_DEVIATION_MEASURED = 4.8e-13
+# measured: the largest |closed form - cos(2 atan2(b / 2, d))| over 2000 depths in 0.05 .. 500 m, b = 0.1: 2.22e-16 (one unit in the last place below 1); asserted at 10 x
+COS_DEVIATION_MEASURED = 2.22e-16
+
+
+def near(a, b, scale=None):
+    s = max(abs(a), abs(b)) if scale is None else scale
+    return abs(a - b) <= REL * s
+
+
+def witness_pair(T1, T2, px1, px2, ur1, ur2, d1, d2, l1, l2, K4, p):
+    """(code, method, X, marked)"""
+    fx, fy, cx, cy = K4
+    b, bf = p.baseline, K4[0] * p.baseline
+    R1, R2, t1, t2 = sm.quat_to_R(T1[:4]), sm.quat_to_R(T2[:4]), np.asarray(T1[4:]), np.asarray(T2[4:])
+    xn1, xn2 = np.array([(px1[0] - cx) / fx, (px1[1] - cy) / fy, 1.0]), np.array([(px2[0] - cx) / fx, (px2[1] - cy) / fy, 1.0])
+    ray1, ray2 = R1.T @ xn1, R2.T @ xn2
+    cosRays = float(ray1 @ ray2 / (np.linalg.norm(ray1) * np.linalg.norm(ray2)))
+    s1, s2 = ur1 >= 0, ur2 >= 0
+    cs1 = cs2 = cosRays + 1.0
+    if s1:
+        cs1 = float(np.cos(2.0 * np.arctan2(b / 2.0, d1)))
+    elif s2:
+        cs2 = float(np.cos(2.0 * np.arctan2(b / 2.0, d2)))
+    cosS = min(cs1, cs2)
+    marked = near(cosRays, cosS, 1.0) or near(cosRays, 0.0, 1.0)
+    if not (s1 or s2):
+        marked = marked or near(cosRays, p.cos_parallax_max, 1.0)
+    if (s1 or s2) and not (cosRays < cosS and cosRays > 0):
+        marked = marked or near(cs1, cs2, 1.0)
+    if cosRays < cosS and cosRays > 0 and (s1 or s2 or cosRays < p.cos_parallax_max):
+        method = sm.TRIANGULATE
+        P1, P2 = np.hstack([R1, t1[:, None]]), np.hstack([R2, t2[:, None]])
+        A = np.stack([xn1[0] * P1[2] - P1[0], xn1[1] * P1[2] - P1[1], xn2[0] * P2[2] - P2[0], xn2[1] * P2[2] - P2[1]])
+        x = np.linalg.svd(A)[2][3]
+        if x[3] == 0 or abs(x[3]) < 1e-300:
+            return sm.DEGENERATE, method, np.zeros(3), marked
+        X = x[:3] / x[3]
+        if not np.all(np.isfinite(X)):
+            return sm.DEGENERATE, method, np.zeros(3), marked
+    elif s1 and cs1 < cs2:
+        method = sm.UNPROJECT_1
+        X = R1.T @ (d1 * xn1 - t1)
+    elif s2 and cs2 < cs1:
+        method = sm.UNPROJECT_2
+        X = R2.T @ (d2 * xn2 - t2)
+    else:
+        return sm.NO_METHOD, sm.NONE, np.zeros(3), marked
+    Pc1, Pc2 = R1 @ X + t1, R2 @ X + t2
+    O1, O2 = -R1.T @ t1, -R2.T @ t2
+    dist1, dist2 = float(np.linalg.norm(X - O1)), float(np.linalg.norm(X - O2))
+    marked = marked or near(Pc1[2], 0.0, max(dist1, 1e-300)) or near(Pc2[2], 0.0, max(dist2, 1e-300))
+
+    def reproj(Pc, px, ur, level):
+        u, v = fx * Pc[0] / Pc[2] + cx, fy * Pc[1] / Pc[2] + cy
+        e2 = (u - px[0]) ** 2 + (v - px[1]) ** 2
+        if ur >= 0:
+            return e2 + (u - bf / Pc[2] - ur) ** 2, p.chi2_stereo * 4.0 ** level
+        return e2, p.chi2_mono * 4.0 ** level
+    code = None
+    if not Pc1[2] > 0:
+        code = sm.BEHIND_1
+    elif not Pc2[2] > 0:
+        code = sm.BEHIND_2
+    if code is None:
+        e1, th1 = reproj(Pc1, px1, ur1, l1)
+        marked = marked or near(e1, th1)
+        if e1 > th1:
+            code = sm.REPROJ_1
+    if code is None:
+        e2, th2 = reproj(Pc2, px2, ur2, l2)
+        marked = marked or near(e2, th2)
+        if e2 > th2:
+            code = sm.REPROJ_2
+    if code is None and (dist1 == 0 or dist2 == 0):
+        code = sm.ZERO_DIST
+    if code is None:
+        rd, ro = dist2 / dist1, 2.0 ** l1 / 2.0 ** l2
+        marked = marked or near(rd * p.ratio_factor, ro) or near(rd, ro * p.ratio_factor)
+        code = sm.SCALE if (rd * p.ratio_factor < ro or rd > ro * p.ratio_factor) else sm.OK
+    return code, method, (X if code == sm.OK else np.zeros(3)), marked
+
+
+def witness(pb, K4=sm.K4, p=None):
+    p = p if p is not None else sm.default_params()
+    n = pb["n"]
+    code, method, X, marked = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros((n, 3)), np.zeros(n, bool)
+    for i in range(n):
+        code[i], method[i], X[i], marked[i] = witness_pair(pb["T1"], pb["T2"], pb["px1"][i], pb["px2"][i], pb["ur1"][i], pb["ur2"][i],
+                                                           pb["depth1"][i], pb["depth2"][i], int(pb["level1"][i]), int(pb["level2"][i]), K4, p)
+    return code, method, X, marked
+
+
+_cache = {}
+
+
+def scene_results(kind):
+    """(problem, restatement, witness) of a scene, computed once"""
+    if kind not in _cache:
+        pb = sm.scene(kind, N_SCENE, SEEDS[kind])
+        _cache[kind] = (pb, sm.create(pb), witness(pb))
+    return _cache[kind]
+
+
+@pytest.mark.parametrize("kind", sm.SCENE_KINDS)
+def test_codes_and_methods_equal_the_witness(kind):
+    pb, (code, method, pos), (wc, wm, wX, marked) = scene_results(kind)
+    print("%s: %d pairs, %d marked near a threshold; codes %s methods %s" % (kind, pb["n"], marked.sum(), np.bincount(code, minlength=9),
+                                                                             np.bincount(method, minlength=4)))
+    assert marked.sum() <= 0.02 * pb["n"]
+    for c in np.unique(wc):
+        assert not marked[wc == c].all(), "every pair of code %d is marked" % c
+    keep = ~marked
+    assert np.array_equal(code[keep], wc[keep]) and np.array_equal(method[keep], wm[keep])
+    assert np.all(pos[code != sm.OK] == 0.0)
+    mono = pb["kind"] == "mono"
+    assert (pb["ur1"] < 0).all() == mono
+    if not mono:
+        share = ((pb["ur1"] < 0).mean() + (pb["ur2"] < 0).mean()) / 2
+        assert 0.3 < share < 0.5
+
+
+def test_positions_against_the_witness():
+    worst = 0.0
+    for kind in sm.SCENE_KINDS:
+        pb, (code, method, pos), (wc, wm, wX, marked) = scene_results(kind)
+        ok = (code == sm.OK) & (wc == sm.OK)
+        dev = np.linalg.norm(pos[ok] - wX[ok], axis=1) / np.linalg.norm(wX[ok], axis=1)
+        print("%s: largest relative deviation of a position %.3g over %d points" % (kind, dev.max(), ok.sum()))
+        worst = max(worst, float(dev.max()))
+    print("largest: %.3g" % worst)
+    assert worst <= 10 * POS_DEVIATION_MEASURED
+
+
+def test_every_code_and_method_occurs():
+    codes, methods = np.zeros(9, np.int64), np.zeros(4, np.int64)
+    for kind in sm.SCENE_KINDS:
+        _, (code, method, _), _ = scene_results(kind)
+        codes += np.bincount(code, minlength=9)
+        methods += np.bincount(method, minlength=4)
+    for pb, K4, p, want_code, want_method in sm.edge_cases():
+        code, method, pos = sm.create(pb, K4, p)
+        wc, wm, _, _ = witness(pb, K4, p)
+        assert code[0] == want_code == wc[0] and method[0] == want_method == wm[0] and np.all(pos == 0.0)
+        codes[code[0]] += 1
+        methods[method[0]] += 1
+    print("codes", codes, "methods", methods)
+    assert np.all(codes > 0) and np.all(methods[1:] > 0)
+
+
+def test_closed_form_stereo_parallax():
+    d = np.exp(np.linspace(np.log(0.05), np.log(500.0), 2000))
+    ref = np.array([sm.cos_stereo(v, 0.1) for v in d])
+    trig = np.cos(2.0 * np.arctan2(0.05, d))
+    dev = float(np.abs(ref - trig).max())
+    print("largest deviation of the closed form from cos(2 atan2(b / 2, d)): %.3g" % dev)
+    assert dev <= 10 * COS_DEVIATION_MEASURED
+    assert np.all(np.diff(ref) >= 0) and ref[0] > 0 and ref[-1] < 1
+
+
+def witness_keyframe(T, px, depth, has, K4, p):
+    n = len(depth)
+    idx = np.flatnonzero(depth > 0)
+    order = idx[np.lexsort((idx, depth[idx]))]
+    nd, c = len(idx), int((depth[idx] <= p.th_depth).sum())
+    last = min(nd - 1, max(c, p.min_close))
+    rank, sel, pos = np.full(n, -1, np.int32), np.zeros(n, np.uint8), np.zeros((n, 3))
+    R, t = sm.quat_to_R(T[:4]), np.asarray(T[4:])
+    for r, i in enumerate(order[:last + 1]):
+        rank[i] = r
+        if not has[i]:
+            sel[i] = 1
+            xn = np.array([(px[i, 0] - K4[0 + 2]) / K4[0], (px[i, 1] - K4[3]) / K4[1], 1.0])
+            pos[i] = R.T @ (depth[i] * xn - t)
+    return rank, sel, pos, nd, c
+
+
+@pytest.mark.parametrize("n_depth,c", sm.KEYFRAME_GRID)
+def test_keyframe_rule(n_depth, c):
+    p = sm.default_params()
+    T, px, depth, has = sm.keyframe_scene(n_depth + 37, n_depth, c, 100 + 7 * n_depth + c)
+    if n_depth > 5:
+        assert len(np.unique(depth[depth > 0])) < n_depth          # ties in depth
+    r = sm.keyframe_points(T, px, depth, has, sm.K4, p)
+    rank, sel, pos, nd, nc = witness_keyframe(T, px, depth, has, sm.K4, p)
+    assert (r["n_depth"], r["n_close"]) == (nd, nc) == (n_depth, c)
+    assert np.array_equal(r["rank"], rank) and np.array_equal(r["selected"], sel)
+    walked = int((rank >= 0).sum())
+    assert walked == min(n_depth, max(c, p.min_close) + 1)
+    assert np.all(r["pos_world"][sel == 0] == 0.0)
+    if sel.any():
+        assert np.abs(r["pos_world"] - pos).max() <= 1e-12 * max(1.0, np.abs(pos).max())
+    if n_depth > 5:
+        assert has[rank >= 0].any() and (sel == 0)[rank >= 0].any()     # walked features that already have a point are not selected
+
+
+# ---- what the stereo columns buy ------------------------------------------------------------------------------------------------------
+# The forward-motion scene with its true matches (2000 pairs, levels 0, a quarter of the pixels within 30 px of the epipole), once with every
+# ur = -1 and once with the stereo columns, measured on the restatement:
+#                  pairs lost   lost within 30 px of the epipole   median relative depth error of the points made
+#   mono  (ur=-1)    0.532                1.000 (of 513)                        0.0145
+#   stereo           0.087                0.144                                 0.0157
+# The thresholds below separate the two rows where they differ, each at least a factor 2 away from both; they are no performance claim.  The
+# depth error does not separate the rows (the mono row keeps only the pairs with parallax, which are as exact as a stereo measurement at
+# 2-8 m), so it is recorded and bounded for both rows alike (0.2 px of disparity noise on at least 42 / 8 px is 3.8 % at one sigma, a median of
+# |N| below 2.6 %: 5 % bounds either row): nothing is claimed for it.
+BUYS_N, BUYS_SEED = 2000, 21
+LOST_BETWEEN, LOST_EPIPOLE_BETWEEN = 0.21, 0.38
+
+
+def _buys_rows():
+    pb = sm.scene("forward", BUYS_N, BUYS_SEED, true_matches=True)
+    epi = np.hypot(pb["px1"][:, 0] - sm.K4[2], pb["px1"][:, 1] - sm.K4[3]) < 30.0
+    rows = {}
+    for name in ("mono", "stereo"):
+        q = dict(pb)
+        if name == "mono":
+            q["ur1"], q["ur2"] = np.full(BUYS_N, -1.0), np.full(BUYS_N, -1.0)
+        code, method, pos = sm.create(q)
+        ok = code == sm.OK
+        z = sm.project(pb["T1"], pos[ok])[1]
+        rows[name] = (1.0 - ok.mean(), 1.0 - ok[epi].mean(), float(np.median(np.abs(z - pb["z1"][ok]) / pb["z1"][ok])))
+    return rows, int(epi.sum())
+
+
+def test_what_the_stereo_columns_buy():
+    rows, n_epi = _buys_rows()
+    for name, r in rows.items():
+        print("%-6s pairs lost %.3f   lost within 30 px of the epipole (%d pairs) %.3f   median relative depth error %.4f" % ((name, r[0], n_epi) + r[1:]))
+    assert n_epi >= 100
+    assert rows["mono"][0] >= 2 * LOST_BETWEEN and rows["stereo"][0] <= LOST_BETWEEN / 2
+    assert rows["mono"][1] >= 2 * LOST_EPIPOLE_BETWEEN and rows["stereo"][1] <= LOST_EPIPOLE_BETWEEN / 2
+    for r in rows.values():
+        assert r[2] < 0.05

@@ -540,6 +540,28 @@ def popt_argtypes(lib):
     lib.ygz_hip_optimize_pose_stereo.argtypes = [C.c_void_p, C.c_int, ip, dp, dp, ip, bp, pp, dp, bp, dp, ip, ip, ip, ip, dp, dp, dp]
 
 
+class SmapParams(C.Structure):
+    """ygz_smap_params (include/ygz_hip.h)"""
+    _fields_ = [("baseline", C.c_double), ("chi2_mono", C.c_double), ("chi2_stereo", C.c_double), ("cos_parallax_max", C.c_double),
+                ("ratio_factor", C.c_double), ("th_depth", C.c_double), ("min_close", C.c_int32), ("pad", C.c_int32)]
+
+
+class SmapProblem(C.Structure):
+    """ygz_smap_problem (include/ygz_hip.h)"""
+    _fields_ = [("T1", C.c_double * 7), ("T2", C.c_double * 7), ("px1", C.POINTER(C.c_double)), ("px2", C.POINTER(C.c_double)),
+                ("ur1", C.POINTER(C.c_double)), ("ur2", C.POINTER(C.c_double)), ("depth1", C.POINTER(C.c_double)), ("depth2", C.POINTER(C.c_double)),
+                ("level1", C.POINTER(C.c_int32)), ("level2", C.POINTER(C.c_int32)), ("n", C.c_int)]
+
+
+def smap_argtypes(lib):
+    ip, dp, bp, pp = C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.POINTER(SmapParams)
+    cp = C.POINTER(C.c_int)
+    lib.ygz_hip_default_smap_params.argtypes = [pp]
+    lib.ygz_hip_default_smap_params.restype = None
+    lib.ygz_hip_stereo_create_map_points.argtypes = [C.c_void_p, C.c_int, C.POINTER(SmapProblem), dp, pp, ip, ip, dp, ip]
+    lib.ygz_hip_stereo_keyframe_points.argtypes = [C.c_void_p, dp, C.c_int, dp, dp, bp, dp, pp, ip, bp, dp, cp, cp, cp]
+
+
 # every symbol include/ygz_hip.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
     "ygz_hip_default_params", "ygz_hip_create", "ygz_hip_destroy", "ygz_hip_synchronize", "ygz_hip_join", "ygz_hip_set_overlap", "ygz_hip_error_string",
@@ -576,6 +598,7 @@ ABI_SYMBOLS = [
     "ygz_hip_default_stereo_params", "ygz_hip_stereo_depths_slots", "ygz_hip_stereo_match", "ygz_hip_stereo_candidates",
     "ygz_hip_default_pose_opt_params", "ygz_hip_optimize_pose_stereo",
     "ygz_hip_stereo_rectify", "ygz_hip_default_rectify_params", "ygz_hip_set_rectification", "ygz_hip_rectify_map", "ygz_hip_build_pyramid_rectified",
+    "ygz_hip_default_smap_params", "ygz_hip_stereo_create_map_points", "ygz_hip_stereo_keyframe_points",
 ]
 INIT_SYMBOLS = ["ygz_hip_default_init_params", "ygz_hip_initialize", "ygz_hip_init_sample_sets", "ygz_hip_init_hypotheses", "ygz_hip_init_reconstruct"]
 INIT_NONE, INIT_H, INIT_F = 0, 1, 2
@@ -616,6 +639,9 @@ RECT_CAMERAS = 2
 STEREO_SYMBOLS = ["ygz_hip_default_stereo_params", "ygz_hip_stereo_depths_slots", "ygz_hip_stereo_match", "ygz_hip_stereo_candidates"]
 STEREO_OK, STEREO_NO_CANDIDATE, STEREO_DESCRIPTOR, STEREO_BORDER, STEREO_EDGE, STEREO_DISPARITY, STEREO_MEDIAN = range(7)
 STEREO_N_STATUS, STEREO_COLUMNS = 7, 11
+
+SMAP_SYMBOLS = ["ygz_hip_default_smap_params", "ygz_hip_stereo_create_map_points", "ygz_hip_stereo_keyframe_points"]
+SMAP_MAX_PROBLEMS, SMAP_MAX_PAIRS = 32, 65536
 
 POPT_SYMBOLS = ["ygz_hip_default_pose_opt_params", "ygz_hip_optimize_pose_stereo"]
 POPT_FAILED, POPT_CONVERGED, POPT_MAX_ITERATIONS, POPT_STALLED = range(4)
@@ -935,6 +961,75 @@ class HipContext:
             f("rounds_run", C.c_int32), f("status", C.c_int32), f("lm_iterations", C.c_int32), f("cost_initial", C.c_double),
             f("cost_final", C.c_double), f("lambda", C.c_double)), "optimize_pose_stereo")
         return o
+
+    # ---- stereo map-point creation
+    def default_smap_params(self, **fields):
+        """ygz_hip_default_smap_params, with the given fields overwritten"""
+        smap_argtypes(self.lib)
+        p = SmapParams()
+        self.lib.ygz_hip_default_smap_params(C.byref(p))
+        for k, v in fields.items():
+            getattr(p, k)                   # AttributeError for a field the struct does not have
+            setattr(p, k, v)
+        return p
+
+    def stereo_create_map_points(self, problems, K4, params=None, **fields):
+        """ORB-SLAM2's CreateNewMapPoints with stereo for a list of problems, each a dict of T1, T2 [7], px1, px2 [n, 2], ur1, ur2, depth1,
+        depth2 [n] (ur < 0: mono) and level1, level2 [n]; K4 = (fx, fy, cx, cy).  Dict of code, method [N], pos_world [N, 3] over the
+        concatenated pairs, counts [n_problems, 2] (created, triangulated) and offsets [n_problems + 1]."""
+        p = params if params is not None else self.default_smap_params(**fields)
+        smap_argtypes(self.lib)
+        arr = (SmapProblem * max(len(problems), 1))()
+        keep, off = [], [0]
+        for q, pb in enumerate(problems):
+            T1, T2 = np.ascontiguousarray(pb["T1"], np.float64).reshape(7), np.ascontiguousarray(pb["T2"], np.float64).reshape(7)
+            for k in range(7):
+                arr[q].T1[k], arr[q].T2[k] = T1[k], T2[k]
+            n = len(np.asarray(pb["ur1"]).reshape(-1))
+            for name in ("px1", "px2", "ur1", "ur2", "depth1", "depth2", "level1", "level2"):
+                t = np.int32 if name.startswith("level") else np.float64
+                if pb.get(name) is None:
+                    continue
+                a = np.ascontiguousarray(pb[name], t).reshape(-1)
+                if len(a) != n * (2 if name.startswith("px") else 1):
+                    raise ValueError("problem %d: %s has the wrong length" % (q, name))
+                keep.append(a)
+                if n:
+                    setattr(arr[q], name, _p(a, C.c_int32 if t is np.int32 else C.c_double))
+            arr[q].n = n
+            off.append(off[-1] + n)
+        N = off[-1]
+        m = max(N, 1)
+        o = dict(code=np.zeros(m, np.int32), method=np.zeros(m, np.int32), pos_world=np.zeros((m, 3)),
+                 counts=np.zeros((max(len(problems), 1), 2), np.int32), offsets=np.array(off, np.int32))
+        k = np.ascontiguousarray(K4, np.float64).reshape(4)
+        self._chk(self.lib.ygz_hip_stereo_create_map_points(self._ctx, len(problems), arr, _p(k, C.c_double), C.byref(p), _p(o["code"], C.c_int32),
+                                                            _p(o["method"], C.c_int32), _p(o["pos_world"], C.c_double), _p(o["counts"], C.c_int32)),
+                  "stereo_create_map_points")
+        o["code"], o["method"], o["pos_world"], o["counts"] = o["code"][:N], o["method"][:N], o["pos_world"][:N], o["counts"][:len(problems)]
+        return o
+
+    def stereo_keyframe_points(self, T, px, depth, has_point, K4, params=None, **fields):
+        """ORB-SLAM2's keyframe insertion for a stereo or RGB-D keyframe: the features with a depth, nearest first, the close ones and at least
+        min_close of them un-projected into the world.  Dict of rank [n], selected [n], pos_world [n, 3], n_depth, n_close, n_selected."""
+        p = params if params is not None else self.default_smap_params(**fields)
+        smap_argtypes(self.lib)
+        T = np.ascontiguousarray(T, np.float64).reshape(7)
+        px = np.ascontiguousarray(px, np.float64).reshape(-1, 2)
+        depth = np.ascontiguousarray(depth, np.float64).reshape(-1)
+        has = np.ascontiguousarray(has_point, np.uint8).reshape(-1)
+        n = len(depth)
+        if not (len(px) == len(has) == n):
+            raise ValueError("px, depth and has_point differ in length")
+        m = max(n, 1)
+        rank, sel, pos = np.zeros(m, np.int32), np.zeros(m, np.uint8), np.zeros((m, 3))
+        nd, nc, ns = C.c_int(0), C.c_int(0), C.c_int(0)
+        k = np.ascontiguousarray(K4, np.float64).reshape(4)
+        g = lambda v, t: _p(v, t) if n else None
+        self._chk(self.lib.ygz_hip_stereo_keyframe_points(self._ctx, _p(T, C.c_double), n, g(px, C.c_double), g(depth, C.c_double), g(has, C.c_uint8),
+                                                          _p(k, C.c_double), C.byref(p), _p(rank, C.c_int32), _p(sel, C.c_uint8), _p(pos, C.c_double),
+                                                          C.byref(nd), C.byref(nc), C.byref(ns)), "stereo_keyframe_points")
+        return dict(rank=rank[:n], selected=sel[:n], pos_world=pos[:n], n_depth=nd.value, n_close=nc.value, n_selected=ns.value)
 
     # ---- keyframe store / device-built BA windows (configs[4])
     def stream_wait(self, signaler):

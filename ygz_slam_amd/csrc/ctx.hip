@@ -519,7 +519,8 @@ static const char *const k_kernel_names[KID_COUNT] = {
     "k_bgr2gray", "k_pyr_down", "k_fast_select", "k_compact", "k_describe", "k_hamming_nn", "k_match_finalize", "k_track_load",
     "k_find_direct_projection", "k_align2d", "k_sparse_align", "k_scharr", "k_klt", "k_klt_pad", "k_ba_pose_prep", "k_ba_points", "k_ba_final",
     "k_ba_chi2", "k_pose_only_ba", "k_ba_lm", "k_bow_transform", "k_bow_match", "k_depth_from_triangulation", "k_lmap_match", "k_lmap_aux",
-    "k_match_postfilter", "k_track_aux", "k_depth_filter", "k_window", "k_undistort", "k_stereo_match", "k_stereo_median", "k_pose_opt", "k_rectify" };
+    "k_match_postfilter", "k_track_aux", "k_depth_filter", "k_window", "k_undistort", "k_stereo_match", "k_stereo_median", "k_pose_opt", "k_rectify",
+    "k_smap_pairs", "k_smap_keyframe" };
 
 int ygz_hip_probe_begin(ygz_hip_ctx *ctx, const char *kernel_name, int max_launches)
 {
