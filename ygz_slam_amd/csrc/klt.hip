@@ -166,10 +166,11 @@ __device__ __forceinline__ int klt_dot2_keep(uint32_t a, uint32_t b, int acc)
 { int d; asm("v_dot2_i32_i16 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(acc)); return d; }
 __device__ __forceinline__ int klt_dot2_sacc(uint32_t a, uint32_t b, int acc /* wave-uniform */)
 { int d; asm("v_dot2_i32_i16 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "s"(acc)); return d; }
-#define KLT_DIFF9P(l0, h0, l1, h1, k, c) (klt_dot2(KLT_PAIR(l1, h1, k), wbot, klt_dot2_keep(KLT_PAIR(l0, h0, k), wtop, (c))) >> 9)
-// the raw sum S + c of KLT_DIFF9P for two pixels -> (diff_0, diff_1) as int16 pair: |S + c| < 2^23, so bytes 1-2 of each are
+// on pixel pairs that are unpacked already (p0 = KLT_PAIR of the upper row, p1 of the lower one: k_klt3 keeps them between evaluations)
+#define KLT_SUM9Q(p0, p1, c) klt_dot2((p1), wbot, klt_dot2_keep((p0), wtop, (c)))
+#define KLT_DIFF9Q(p0, p1, c) (KLT_SUM9Q(p0, p1, c) >> 9)
+// the raw sum S + c of KLT_DIFF9Q for two pixels -> (diff_0, diff_1) as int16 pair: |S + c| < 2^23, so bytes 1-2 of each are
 // (S + c) >> 8 as int16; one packed arithmetic shift finishes the >> 9 of both (2 instructions per pair instead of 3)
-#define KLT_SUM9P(l0, h0, l1, h1, k, c) klt_dot2(KLT_PAIR(l1, h1, k), wbot, klt_dot2_keep(KLT_PAIR(l0, h0, k), wtop, (c)))
 __device__ __forceinline__ uint32_t klt_diff_pair(int x0, int x1)
 {
     const klt_s2 h = __builtin_bit_cast(klt_s2, __builtin_amdgcn_perm((uint32_t)x1, (uint32_t)x0, 0x06050201u));
@@ -426,6 +427,30 @@ __device__ __forceinline__ void klt_load8_row(klt_gbytes row /* wave-uniform */,
     lo = __builtin_amdgcn_alignbyte(d1, d0, sh);
     hi = __builtin_amdgcn_alignbyte(d2, d1, sh);
 }
+// The lane's window of the current image as k_klt3 keeps it between mismatch evaluations: the 4 x 7 zero-extended pixel pairs of
+// KLT_PAIR.  They depend on the integer window position only, so an evaluation that stays on the same pixels reuses them.
+// the position the kept pairs belong to, as one float: exact and injective for |fx| < 2048 (an admissible window: -21 <= fx < w <= 1280)
+#define KLT_WINDOW_KEY(fx, fy) __builtin_fmaf((fy), 4096.f, (fx))
+__device__ __forceinline__ void klt_window_load(const klt_gbytes (&row)[4], uint32_t o, uint32_t (&pj)[4][7])
+{
+    const uint32_t oa = o & ~3u;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        uint32_t jl, jh;
+        klt_load8_row(row[r], oa, o, jl, jh);
+#pragma unroll
+        for (int kk = 0; kk < 7; ++kk) pj[r][kk] = KLT_PAIR(jl, jh, kk);
+    }
+}
+// the pairs at the start of a level: whatever the registers hold (no instruction), never read before the first klt_window_load
+__device__ __forceinline__ void klt_window_undef(uint32_t (&pj)[4][7])
+{
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+#pragma unroll
+        for (int kk = 0; kk < 7; ++kk) asm volatile("" : "=v"(pj[r][kk]));
+    }
+}
 // (double)fabsf(x) < 0.01 without FP64: 0.01 is no float, and 0.01f (0x3C23D70A = 0.0099999997764825820922851562) is the largest float
 // below it, so for every float f: (double)f < 0.01  <=>  f <= 0.01f (NaN: false on both sides).  tests/test_klt_rewrites.py checks it.
 #define KLT_ABS_LT_001(x) (fabsf(x) <= 0.01f)
@@ -444,6 +469,15 @@ __device__ __forceinline__ double klt_norm2_d(float dx, float dy)
 // measured on the tight grid: one-wavefront workgroups refill every freed slot and finish LK in 2.8 instead of 4.1 ms inside the step, but take
 // that time from the BA build and the matcher beside it, and the step gets longer; four is the shortest step.
 // amdgpu_waves_per_eu pins the register budget: four wavefronts per SIMD, 128 registers.
+// The window of the current image.  What a mismatch evaluation reads of it -- the four row gathers, their realignment and the 28 pixel pairs --
+// depends on the integer window position only, and after the first step of a level the update is a fraction of a pixel: the pairs of all
+// four rows stay in registers (127 of the 128, nothing spilled) with the key of the position they belong to, and the wavefront gathers
+// again only when a lane that still iterates is on new pixels (one ballot: a lane-divergent branch around the gathers makes the compiler
+// copy the loop-carried registers).  The bounds tests sit behind the same ballot: a window that did not move is still inside.  The lanes
+// that are done are kept as a scalar lane mask, so that every test around the gathers is one compare and scalar logic
+// (tests/test_klt_isa_budget.py counts 183 VALU with the reload; 47 of them and the four gathers sit behind the ballot, which
+// tests/test_klt_window_reuse_isa.py holds; the measured reload rate and times are in DESIGN.md section 4).  The error pass of level 0 takes the kept pairs too when they are those
+// of the final position.
 #define KLT3_WPB 4
 __global__ __launch_bounds__(64 * KLT3_WPB) __attribute__((amdgpu_waves_per_eu(4))) void k_klt3(KltArgs A)
 {
@@ -502,7 +536,7 @@ __global__ __launch_bounds__(64 * KLT3_WPB) __attribute__((amdgpu_waves_per_eu(4
         KLT_WEIGHTS_P(a, b);
         // the lane's 3 x 7 patch values stay in registers for the whole level: image << 5, and the derivatives of two
         // consecutive pixels per register (dx_k | dx_k+1 << 16, same for dy) -- the layout v_dot2 wants for the mismatch sums
-        int cI[21]; uint32_t pDx[11], pDy[11];                      // cI = 256 - (patch value << 9), see KLT_DIFF9P; only read where in_lv
+        int cI[21]; uint32_t pDx[11], pDy[11];                      // cI = 256 - (patch value << 9), see KLT_DIFF9Q; only read where in_lv
         float sA11 = 0.f, sA12 = 0.f, sA22 = 0.f;
         if (in_lv) {
             const uint32_t o = (uint32_t)(__mul24(ipy, pw) + ipx + lo), oa = o & ~3u, o4 = o << 2;
@@ -547,33 +581,46 @@ __global__ __launch_bounds__(64 * KLT3_WPB) __attribute__((amdgpu_waves_per_eu(4
         if (in_lv && !it_ok && level == 0) status = false;
         Dd = __fdiv_rn(1.f, Dd);
         nx = it_ok ? __fsub_rn(nx, half) : nx; ny = it_ok ? __fsub_rn(ny, half) : ny;
-        float pdx = 0.f, pdy = 0.f;
-        bool done = !it_ok;
+        // the previous step: NaN before the first one, so that the oscillation test fails there without a test of j
+        float pdx = __int_as_float(0x7fc00000), pdy = pdx;
+        // The lanes that are done, as the wave's lane mask: all 64 lanes of the wavefront run the loop (blockDim is a multiple of 64 and
+        // the control flow down to here is wave-uniform), so the mask is complete, and every update is scalar.
+        uint64_t dm = __builtin_amdgcn_ballot_w64(!it_ok);
         // the lane sums of the mismatch, kept across iterations: a lane that no longer evaluates keeps its last sums instead of being
         // zeroed every iteration.  Only lane 63 is read by another segment (the +16 step of klt_seg21_sum), and it never evaluates: +0.0.
         float sb1 = 0.f, sb2 = 0.f;
-        for (int j = 0; j < A.max_count; ++j) {
-            if (__builtin_amdgcn_ballot_w64(!done) == 0ull) break;      // the lane mask itself (__ballot rebuilds it with two VALU ops)
-            const int inx = (int)floorf(nx), iny = (int)floorf(ny);
-            if (!done && (inx < -win || inx >= w || iny < -win || iny >= h)) {
-                if (level == 0) status = false;
-                done = true;
+        uint32_t pj[4][7];
+        klt_window_undef(pj);
+        float kkey = __int_as_float(0x7fc00000);                       // NaN: equal to no key
+        asm("" : "+v"(kkey));                                          // opaque, or the first evaluation is threaded past the loop header
+        uint64_t keptm = 0ull;                                         // lanes whose pairs are those of kkey (not the safe offset's)
+        uint64_t lostm = 0ull;                                         // lanes whose window left the image while they iterated
+        for (int j = 0; j < A.max_count && ~dm != 0ull; ++j) {
+            const float fx = floorf(nx), fy = floorf(ny);
+            const float key = KLT_WINDOW_KEY(fx, fy);
+            if ((__builtin_amdgcn_ballot_w64(key != kkey) & ~dm) != 0ull) {      // wave-uniform: some lane that iterates is on new pixels
+                const int inx = (int)fx, iny = (int)fy;
+                // one ballot per compare: each is the compare's own lane mask, and the rest is scalar
+                const uint64_t oobm = __builtin_amdgcn_ballot_w64(inx < -win) | __builtin_amdgcn_ballot_w64(inx >= w)
+                                    | __builtin_amdgcn_ballot_w64(iny < -win) | __builtin_amdgcn_ballot_w64(iny >= h);
+                const bool oob = __builtin_amdgcn_inverse_ballot_w64(oobm);
+                lostm |= oobm & ~dm;
+                dm |= oobm;
+                klt_window_load(Jr, oob ? (uint32_t)lo : (uint32_t)(__mul24(iny, pw) + inx + lo), pj);
+                asm("v_mov_b32 %0, %1" : "=v"(kkey) : "v"(key));    // by hand: the compiler keeps the key in the register of kkey and copies it back and forth on the other path
+                keptm = ~oobm;
             }
-            const bool act = !done;
-            a = __fsub_rn(nx, floorf(nx)); b = __fsub_rn(ny, floorf(ny));
+            const bool act = __builtin_amdgcn_inverse_ballot_w64(~dm);
+            a = __fsub_rn(nx, fx); b = __fsub_rn(ny, fy);
             KLT_WEIGHTS_P(a, b);
             if (act) {
-                const uint32_t o = (uint32_t)(__mul24(iny, pw) + inx + lo), oa = o & ~3u;
-                uint32_t jl[4], jh[4];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) klt_load8_row(Jr[r], oa, o, jl[r], jh[r]);
                 int a1, a2;                                          // 21 terms, |diff * I| < 2^26: exact in int32
                 int df[22];                                          // S + c, the >> 9 happens in klt_diff_pair
                 df[21] = 0;
 #pragma unroll
                 for (int r = 0; r < 3; ++r) {
 #pragma unroll
-                    for (int kk = 0; kk < 7; ++kk) df[7 * r + kk] = KLT_SUM9P(jl[r], jh[r], jl[r + 1], jh[r + 1], kk, cI[7 * r + kk]);
+                    for (int kk = 0; kk < 7; ++kk) df[7 * r + kk] = KLT_SUM9Q(pj[r][kk], pj[r + 1][kk], cI[7 * r + kk]);
                 }
 #pragma unroll
                 for (int kk = 0; kk < 11; ++kk) {                    // (diff_2k, diff_2k+1) . (dx_2k, dx_2k+1): |diff| < 2^14 fits int16
@@ -586,37 +633,40 @@ __global__ __launch_bounds__(64 * KLT3_WPB) __attribute__((amdgpu_waves_per_eu(4
             float t1 = sb1, t2 = sb2;
             klt_seg21_sum2(t1, t2, six);
             const float b1 = __fmul_rn(t1, FLT_SCALE), b2 = __fmul_rn(t2, FLT_SCALE);
+            // the step and its exit tests on every lane (a lane that is done computes on what it kept and is masked out below)
+            const float dx = __fmul_rn(__fsub_rn(__fmul_rn(A12, b2), __fmul_rn(A22, b1)), Dd);
+            const float dy = __fmul_rn(__fsub_rn(__fmul_rn(A12, b1), __fmul_rn(A11, b2)), Dd);
+            const uint64_t conv = __builtin_amdgcn_ballot_w64(klt_norm2_d(dx, dy) <= A.epsilon);
+            const uint64_t osc = __builtin_amdgcn_ballot_w64(KLT_ABS_LT_001(__fadd_rn(dx, pdx))) & __builtin_amdgcn_ballot_w64(KLT_ABS_LT_001(__fadd_rn(dy, pdy))) & ~conv;
             if (act) {
-                const float dx = __fmul_rn(__fsub_rn(__fmul_rn(A12, b2), __fmul_rn(A22, b1)), Dd);
-                const float dy = __fmul_rn(__fsub_rn(__fmul_rn(A12, b1), __fmul_rn(A11, b2)), Dd);
                 nx = __fadd_rn(nx, dx); ny = __fadd_rn(ny, dy);
                 outx = __fadd_rn(nx, half); outy = __fadd_rn(ny, half);
-                if (klt_norm2_d(dx, dy) <= A.epsilon) done = true;
-                else if (j > 0 && KLT_ABS_LT_001(__fadd_rn(dx, pdx)) && KLT_ABS_LT_001(__fadd_rn(dy, pdy))) {
+                if (__builtin_amdgcn_inverse_ballot_w64(osc)) {
+                    asm volatile("");                                // stays a branch on the lane mask (as two selects it costs two VALU more)
                     outx = __fsub_rn(outx, __fmul_rn(dx, 0.5f)); outy = __fsub_rn(outy, __fmul_rn(dy, 0.5f));
-                    done = true;
                 }
                 pdx = dx; pdy = dy;
             }
+            dm |= conv | osc;
         }
         if (level == 0) {
+            if (__builtin_amdgcn_inverse_ballot_w64(lostm)) status = false;
             bool want = it_ok && status;
             const float qx = __fsub_rn(outx, half), qy = __fsub_rn(outy, half);
             const int inx = (int)floorf(qx), iny = (int)floorf(qy);
             if (want && (inx < -win || inx >= w || iny < -win || iny >= h)) { status = false; want = false; }
             const float aa = __fsub_rn(qx, floorf(qx)), bb = __fsub_rn(qy, floorf(qy));
             KLT_WEIGHTS_P(aa, bb);
+            // the kept window serves when every lane that wants the error ended on the pixels it last loaded
+            if (__builtin_amdgcn_ballot_w64(want && !(__builtin_amdgcn_inverse_ballot_w64(keptm) && KLT_WINDOW_KEY(floorf(qx), floorf(qy)) == kkey)) != 0ull)
+                klt_window_load(Jr, want ? (uint32_t)(__mul24(iny, pw) + inx + lo) : (uint32_t)lo, pj);
             float se = 0.f;
             if (want) {
-                const uint32_t o = (uint32_t)(__mul24(iny, pw) + inx + lo), oa = o & ~3u;
-                uint32_t jl[4], jh[4];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) klt_load8_row(Jr[r], oa, o, jl[r], jh[r]);
 #pragma unroll
                 for (int r = 0; r < 3; ++r) {
 #pragma unroll
                     for (int kk = 0; kk < 7; ++kk) {
-                        const int diff = KLT_DIFF9P(jl[r], jh[r], jl[r + 1], jh[r + 1], kk, cI[7 * r + kk]);
+                        const int diff = KLT_DIFF9Q(pj[r][kk], pj[r + 1][kk], cI[7 * r + kk]);
                         se = __fadd_rn(se, fabsf((float)diff));
                     }
                 }
