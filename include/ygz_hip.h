@@ -69,7 +69,9 @@ extern "C" {
  * Still 6: stereo rectification added (ygz_rectify_params, ygz_hip_stereo_rectify, ygz_hip_default_rectify_params, ygz_hip_set_rectification,
  * ygz_hip_rectify_map, ygz_hip_build_pyramid_rectified) -- no existing argument list changed.
  * Still 6: stereo map-point creation added (ygz_smap_params, ygz_smap_problem, ygz_hip_default_smap_params, ygz_hip_stereo_create_map_points,
- * ygz_hip_stereo_keyframe_points) -- no existing argument list changed. */
+ * ygz_hip_stereo_keyframe_points) -- no existing argument list changed.
+ * Still 6: local-map fusion search added (ygz_lfuse_params, ygz_lfuse_points, ygz_lfuse_problem, ygz_hip_default_lfuse_params,
+ * ygz_hip_local_fuse_search) -- no existing argument list changed. */
 #define YGZ_HIP_ABI_VERSION 6
 
 typedef struct ygz_hip_ctx ygz_hip_ctx;
@@ -1268,6 +1270,64 @@ int  ygz_hip_stereo_create_map_points(ygz_hip_ctx *ctx, int n_problems, const yg
 int  ygz_hip_stereo_keyframe_points(ygz_hip_ctx *ctx, const double T[7], int n, const double *px, const double *depth, const uint8_t *has_point,
                                     const double K4[4], const ygz_smap_params *params, int32_t *rank, uint8_t *selected, double *pos_world,
                                     int *n_depth, int *n_close, int *n_selected);
+
+/* ---- local-map fusion search -- nothing in the reference; the search of ORB-SLAM2's ORBmatcher::Fuse(pKF, vpMapPoints, th) as
+ * LocalMapping::SearchInNeighbors calls it: many target keyframes look at the SAME points, and a keypoint is accepted only when the projection
+ * lies within chi2 of it, the right column included on a stereo keypoint.  The arithmetic is that of tests/lfuse_ref.c (DESIGN.md section
+ * 25); every output is bit-identical to it.
+ *
+ * A point set: pw [n_pt][3], pt_desc [n_pt][32], pt_dmax [n_pt], pt_normal [n_pt][3] (NULL: no viewing-angle test).  A problem is one target
+ * keyframe: pose T = qx qy qz qw tx ty tz, world -> camera; keypoints kp_px [n_kp][2] (level-0 pixels), kp_level, kp_desc [n_kp][32], kp_ur
+ * [n_kp] (< 0: a mono keypoint; NULL: all mono), kp_taken [n_kp] (optional); `set`, the point set it reads, and pt_skip [n_pt of that set]
+ * (optional).  Per (problem, point), the first failing step sets the reason (0 searched, 1 skip, 2 behind, 3 outside, 4 range, 5 angle):
+ *   steps 1-6 of ygz_hip_search_by_projection with s = 1 (bit-equal to it): skip flag, z > 0, u, v inside [0, w) x [0, h), the distance inside
+ *   [0.8 dmin, 1.2 dmax], the viewing angle, the predicted level; ur = u - bf / z with bf = fx baseline;
+ *   the window: keypoints that are not taken, of level pred-1 .. pred, with |kx - u| < r and |ky - v| < r, r = th 2^pred;
+ *   the gate: e2 = (u - kx)^2 + (v - ky)^2; a mono keypoint is rejected when e2 > chi2_mono 4^level, a stereo keypoint when
+ *   e2 + (ur - kp_ur)^2 > chi2_stereo 4^level; n_gated counts the keypoints of the window that the gate rejected;
+ *   the match: the smallest (Hamming distance, keypoint index) of the survivors when its distance is <= th_dist, else match = dist = -1. */
+#define YGZ_LFUSE_MAX_PROBLEMS 64
+#define YGZ_LFUSE_MAX_SETS     8
+#define YGZ_LFUSE_MAX_PAIRS    1048576    /* per call: the sum over the problems of their set's n_pt */
+typedef struct {
+    double  th;                           /* 3.0: the window is th 2^pred pixels; > 0 */
+    double  baseline;                     /* 0.1: metres between the rig's cameras, > 0 */
+    double  chi2_mono, chi2_stereo;       /* 5.99, 7.8: ORB-SLAM2's constants in this function (not 5.991 and 7.815); > 0 */
+    int32_t th_dist;                      /* 50: the largest Hamming distance of a match, 0 .. 256 */
+    int32_t pad;
+} ygz_lfuse_params;
+typedef struct {
+    const double  *pw;
+    const uint8_t *pt_desc;
+    const double  *pt_dmax;
+    const double  *pt_normal;
+    int            n_pt;
+} ygz_lfuse_points;
+typedef struct {
+    double         T[7];
+    const double  *kp_px;
+    const int32_t *kp_level;
+    const uint8_t *kp_desc;
+    const double  *kp_ur;
+    const uint8_t *kp_taken;
+    const uint8_t *pt_skip;
+    int            n_kp;
+    int            set;
+} ygz_lfuse_problem;
+void ygz_hip_default_lfuse_params(ygz_lfuse_params *p);
+/* all problems in one launch, every point set uploaded once.  The outputs are concatenated in problem order, a problem contributing n_pt
+ * entries of its set: match, dist, pred_level, reason, n_gated [N]; counts [n_problems][2] = matches, points searched (reason 0).  Every
+ * output may be NULL.  params NULL: defaults.  One packed upload, one launch, one copy back and one wait.  Checked in this order, all before
+ * the device is touched: YGZ_E_INVALID for null sets, problems or K4, n_sets < 1 or n_problems < 1; YGZ_E_CAPACITY above
+ * YGZ_LFUSE_MAX_SETS or YGZ_LFUSE_MAX_PROBLEMS; YGZ_E_INVALID for a set's n_pt < 0 or a null pw, pt_desc or pt_dmax of a set with points, for
+ * a problem's set index out of range, n_kp < 1 or a null kp_px, kp_level or kp_desc; YGZ_E_CAPACITY for n_kp above 2^20 or more than
+ * YGZ_LFUSE_MAX_PAIRS pairs; YGZ_E_INVALID for th <= 0 or not finite, th_dist outside [0, 256], baseline <= 0, a chi2 <= 0 (or one of them
+ * not finite), a non-finite K4, a focal length <= 0, a non-finite pose, point, dmax or kp_ur; last, YGZ_E_INVALID for a null context,
+ * YGZ_E_CAPACITY for n_kp above ygz_hip_max_keypoints and YGZ_E_INVALID for a keypoint level outside the context's pyramid.  A set with n_pt
+ * = 0 is allowed: a problem that reads it contributes nothing. */
+int  ygz_hip_local_fuse_search(ygz_hip_ctx *ctx, int n_sets, const ygz_lfuse_points *sets, int n_problems, const ygz_lfuse_problem *problems,
+                               const double K4[4], const ygz_lfuse_params *params, int32_t *match, int32_t *dist, int32_t *pred_level,
+                               int32_t *reason, int32_t *n_gated, int32_t *counts);
 
 #ifdef __cplusplus
 }

@@ -562,6 +562,33 @@ def smap_argtypes(lib):
     lib.ygz_hip_stereo_keyframe_points.argtypes = [C.c_void_p, dp, C.c_int, dp, dp, bp, dp, pp, ip, bp, dp, cp, cp, cp]
 
 
+class LfuseParams(C.Structure):
+    """ygz_lfuse_params (include/ygz_hip.h)"""
+    _fields_ = [("th", C.c_double), ("baseline", C.c_double), ("chi2_mono", C.c_double), ("chi2_stereo", C.c_double), ("th_dist", C.c_int32),
+                ("pad", C.c_int32)]
+
+
+class LfusePoints(C.Structure):
+    """ygz_lfuse_points (include/ygz_hip.h)"""
+    _fields_ = [("pw", C.POINTER(C.c_double)), ("pt_desc", C.POINTER(C.c_uint8)), ("pt_dmax", C.POINTER(C.c_double)),
+                ("pt_normal", C.POINTER(C.c_double)), ("n_pt", C.c_int)]
+
+
+class LfuseProblem(C.Structure):
+    """ygz_lfuse_problem (include/ygz_hip.h)"""
+    _fields_ = [("T", C.c_double * 7), ("kp_px", C.POINTER(C.c_double)), ("kp_level", C.POINTER(C.c_int32)), ("kp_desc", C.POINTER(C.c_uint8)),
+                ("kp_ur", C.POINTER(C.c_double)), ("kp_taken", C.POINTER(C.c_uint8)), ("pt_skip", C.POINTER(C.c_uint8)), ("n_kp", C.c_int),
+                ("set", C.c_int)]
+
+
+def lfuse_argtypes(lib):
+    ip, dp, pp = C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(LfuseParams)
+    lib.ygz_hip_default_lfuse_params.argtypes = [pp]
+    lib.ygz_hip_default_lfuse_params.restype = None
+    lib.ygz_hip_local_fuse_search.argtypes = [C.c_void_p, C.c_int, C.POINTER(LfusePoints), C.c_int, C.POINTER(LfuseProblem), dp, pp,
+                                              ip, ip, ip, ip, ip, ip]
+
+
 # every symbol include/ygz_hip.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
     "ygz_hip_default_params", "ygz_hip_create", "ygz_hip_destroy", "ygz_hip_synchronize", "ygz_hip_join", "ygz_hip_set_overlap", "ygz_hip_error_string",
@@ -599,6 +626,7 @@ ABI_SYMBOLS = [
     "ygz_hip_default_pose_opt_params", "ygz_hip_optimize_pose_stereo",
     "ygz_hip_stereo_rectify", "ygz_hip_default_rectify_params", "ygz_hip_set_rectification", "ygz_hip_rectify_map", "ygz_hip_build_pyramid_rectified",
     "ygz_hip_default_smap_params", "ygz_hip_stereo_create_map_points", "ygz_hip_stereo_keyframe_points",
+    "ygz_hip_default_lfuse_params", "ygz_hip_local_fuse_search",
 ]
 INIT_SYMBOLS = ["ygz_hip_default_init_params", "ygz_hip_initialize", "ygz_hip_init_sample_sets", "ygz_hip_init_hypotheses", "ygz_hip_init_reconstruct"]
 INIT_NONE, INIT_H, INIT_F = 0, 1, 2
@@ -642,6 +670,10 @@ STEREO_N_STATUS, STEREO_COLUMNS = 7, 11
 
 SMAP_SYMBOLS = ["ygz_hip_default_smap_params", "ygz_hip_stereo_create_map_points", "ygz_hip_stereo_keyframe_points"]
 SMAP_MAX_PROBLEMS, SMAP_MAX_PAIRS = 32, 65536
+
+LFUSE_SYMBOLS = ["ygz_hip_default_lfuse_params", "ygz_hip_local_fuse_search"]
+LFUSE_MAX_PROBLEMS, LFUSE_MAX_SETS, LFUSE_MAX_PAIRS = 64, 8, 1048576
+LFUSE_SEARCHED, LFUSE_SKIP, LFUSE_BEHIND, LFUSE_OUTSIDE, LFUSE_RANGE, LFUSE_ANGLE = range(6)
 
 POPT_SYMBOLS = ["ygz_hip_default_pose_opt_params", "ygz_hip_optimize_pose_stereo"]
 POPT_FAILED, POPT_CONVERGED, POPT_MAX_ITERATIONS, POPT_STALLED = range(4)
@@ -1030,6 +1062,66 @@ class HipContext:
                                                           _p(k, C.c_double), C.byref(p), _p(rank, C.c_int32), _p(sel, C.c_uint8), _p(pos, C.c_double),
                                                           C.byref(nd), C.byref(nc), C.byref(ns)), "stereo_keyframe_points")
         return dict(rank=rank[:n], selected=sel[:n], pos_world=pos[:n], n_depth=nd.value, n_close=nc.value, n_selected=ns.value)
+
+    # ---- local-map fusion search
+    def default_lfuse_params(self, **fields):
+        """ygz_hip_default_lfuse_params, with the given fields overwritten"""
+        lfuse_argtypes(self.lib)
+        p = LfuseParams()
+        self.lib.ygz_hip_default_lfuse_params(C.byref(p))
+        for k, v in fields.items():
+            getattr(p, k)                   # AttributeError for a field the struct does not have
+            setattr(p, k, v)
+        return p
+
+    def local_fuse_search(self, sets, problems, K4, params=None, **fields):
+        """the search of ORB-SLAM2's Fuse for many target keyframes over shared point sets, one call.  sets: dicts of pw [n, 3], pt_desc
+        [n, 32], pt_dmax [n], pt_normal [n, 3] (optional); problems: dicts of T [7], kp_px [m, 2], kp_level [m], kp_desc [m, 32], kp_ur [m]
+        (optional, < 0: mono), kp_taken [m], pt_skip [n of its set] (optional) and set (default 0).  Dict of match, dist, pred_level,
+        reason, n_gated [N] concatenated in problem order, counts [n_problems, 2] (matches, searched) and offsets [n_problems + 1]."""
+        p = params if params is not None else self.default_lfuse_params(**fields)
+        lfuse_argtypes(self.lib)
+        keep = []
+
+        def put(d, name, t, ct, n):
+            a = d.get(name)
+            if a is None:
+                return C.POINTER(ct)()
+            a = np.ascontiguousarray(a, t).reshape(-1)
+            if len(a) != n:
+                raise ValueError("%s has the wrong length" % name)
+            keep.append(a)
+            return _p(a, ct)
+        sa = (LfusePoints * max(len(sets), 1))()
+        for s, d in enumerate(sets):
+            n = len(np.asarray(d["pt_dmax"]).reshape(-1))
+            sa[s].pw, sa[s].pt_desc = put(d, "pw", np.float64, C.c_double, 3 * n), put(d, "pt_desc", np.uint8, C.c_uint8, 32 * n)
+            sa[s].pt_dmax, sa[s].pt_normal = put(d, "pt_dmax", np.float64, C.c_double, n), put(d, "pt_normal", np.float64, C.c_double, 3 * n)
+            sa[s].n_pt = n
+        pa = (LfuseProblem * max(len(problems), 1))()
+        off = [0]
+        for q, d in enumerate(problems):
+            T = np.ascontiguousarray(d["T"], np.float64).reshape(7)
+            for k in range(7):
+                pa[q].T[k] = T[k]
+            m, st = len(np.asarray(d["kp_level"]).reshape(-1)), int(d.get("set", 0))
+            n = int(sa[st].n_pt) if 0 <= st < len(sets) else 0
+            pa[q].kp_px, pa[q].kp_level = put(d, "kp_px", np.float64, C.c_double, 2 * m), put(d, "kp_level", np.int32, C.c_int32, m)
+            pa[q].kp_desc, pa[q].kp_ur = put(d, "kp_desc", np.uint8, C.c_uint8, 32 * m), put(d, "kp_ur", np.float64, C.c_double, m)
+            pa[q].kp_taken, pa[q].pt_skip = put(d, "kp_taken", np.uint8, C.c_uint8, m), put(d, "pt_skip", np.uint8, C.c_uint8, n)
+            pa[q].n_kp, pa[q].set = m, st
+            off.append(off[-1] + n)
+        N = off[-1]
+        names = ("match", "dist", "pred_level", "reason", "n_gated")
+        o = {k: np.full(max(N, 1), -7, np.int32) for k in names}
+        counts = np.zeros((max(len(problems), 1), 2), np.int32)
+        k4 = np.ascontiguousarray(K4, np.float64).reshape(4)
+        self._chk(self.lib.ygz_hip_local_fuse_search(self._ctx, len(sets), sa, len(problems), pa, _p(k4, C.c_double), C.byref(p),
+                                                     *[_p(o[k], C.c_int32) for k in names], _p(counts, C.c_int32)), "local_fuse_search")
+        del keep
+        o = {k: v[:N] for k, v in o.items()}
+        o["counts"], o["offsets"] = counts[:len(problems)], np.array(off, np.int64)
+        return o
 
     # ---- keyframe store / device-built BA windows (configs[4])
     def stream_wait(self, signaler):

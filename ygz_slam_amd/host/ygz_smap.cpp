@@ -1,7 +1,7 @@
 // ygz::StereoMapper (include/ygz/Algorithm/StereoMapper.h): nothing in the reference.  ORB-SLAM2's two map-point creation paths for a stereo
 // or RGB-D keyframe as synchronous calls: the keyframe's features (or its matches with the covisible neighbours, all neighbours together) go
 // through ONE device call (ygz_slam_amd/csrc/smap.hip), and the map is written from its result.  Every order goes by index.  Not part of it:
-// covisibility upkeep, distinctive descriptors, SearchInNeighbors, MapPointCulling.
+// covisibility upkeep, distinctive descriptors; SearchInNeighbors and MapPointCulling are in ygz_lfuse.cpp.
 // Error conventions of the other surfaces: a failed call logs and returns 0 and leaves the map unchanged, only a missing device throws.
 #include "ygz/Algorithm/StereoMapper.h"
 #include "ygz/Algorithm/Matcher.h"
@@ -70,6 +70,7 @@ int StereoMapper::CreateKeyframePoints(Frame *kf)
         f->_mappoint = mp;
         f->_bad = false;
         _created.push_back(mp);
+        _recent.push_back(mp);
     }
     return (int)_created.size();
 }
@@ -148,6 +149,7 @@ int StereoMapper::CreateNewMapPoints(Frame *kf)
         if (URight(f2, (size_t)_pairs[i].second) < 0) fb->_depth = (f2->_TCW * mp->_pos_world)[2];
         fa->_bad = fb->_bad = false;
         _created.push_back(mp);
+        _recent.push_back(mp);
     }
     return (int)_created.size();
 }
