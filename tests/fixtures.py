@@ -5,6 +5,20 @@ import numpy as np
 from ygz_slam_amd.synth import (FX, FY, CX, CY, make_texture, trajectory, render, se3_exp, se3_log_t, project, quat_to_R, ba_window)  # noqa: F401
 
 
+def surface_binary():
+    """tests/cpp/test_surface, the driver of the class surfaces' host-only modes.  __graft_entry__.build() makes it; where it is absent (a tree
+    that was not built, or a tests/ directory laid over a built tree) it is made here by the same rule, so a test that needs it neither fails
+    for a missing file nor skips."""
+    import os
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = os.path.join(root, "tests", "cpp", "test_surface")
+    if not os.path.exists(exe):
+        subprocess.check_call(["make", "-C", os.path.join(root, "ygz_slam_amd", "host"), "../../tests/cpp/test_surface"], stdout=subprocess.DEVNULL)
+    assert os.path.exists(exe), "tests/cpp/test_surface could not be built"
+    return exe
+
+
 def frame_sequence(n, w=640, h=480, seed=1, noise_sigma=1.0, step=0.02):
     tex, margin = make_texture(seed, w, h)
     poses = trajectory(n, seed + 10, step)

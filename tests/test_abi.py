@@ -118,8 +118,8 @@ def test_frame_covisibility_members():
     """ygz::Frame::UpdateConnections / GetBestCovisibilityKeyframes / AddConnection / UpdateBestCovisibles (src/Basic/Frame.cpp:73-176; what
     src/Module/LocalMapping.cpp:256,345,378,586 reads) on a hand-made map -- host bookkeeping, no device (tests/cpp/test_surface covis)."""
     import subprocess
-    exe = os.path.join(ROOT, "tests", "cpp", "test_surface")
-    assert os.path.exists(exe), "tests/cpp/test_surface is not built (run __graft_entry__.build())"
+    import fixtures
+    exe = fixtures.surface_binary()
     out = subprocess.check_output([exe, "covis"], timeout=60).decode().strip().split("\n")
     # keyframe 3 shares 20 / 16 / 5 good map points with keyframes 0 / 1 / 2 (7 bad ones with keyframe 2 do not count): threshold 15, heaviest first
     assert out[0] == "kf3 cov 0:20 1:16 | connected 0:20 1:16 2:5 | best1 1:0 best10 2"

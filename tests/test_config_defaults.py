@@ -7,16 +7,15 @@ which touches no device."""
 import json
 import os
 import subprocess
-import pytest
 from conftest import ROOT
 
+import fixtures
 BIN = os.path.join(ROOT, "tests", "cpp", "test_surface")
 FIX = json.load(open(os.path.join(ROOT, "tests", "golden", "reference_default_config.json")))["keys"]
 
 
 def _run(args):
-    if not os.path.exists(BIN):
-        pytest.skip("tests/cpp/test_surface not built (python -c 'import __graft_entry__ as g; g.build()')")
+    assert fixtures.surface_binary() == BIN                    # built here if the tree's build has not left it: never a skip
     out = subprocess.run([BIN, "config"] + args, capture_output=True, text=True, check=True).stdout
     got = {}
     for line in out.splitlines():

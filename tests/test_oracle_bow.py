@@ -26,16 +26,21 @@ def _parse(blob):
     return k, L, nodes
 
 
-def _descend(nodes, L, d, levelsup):
+def _descend(nodes, L, d, levelsup, tie_last=False, shallow_leaf_id=False):
+    """word, weight, node of one descriptor; the tree may be ragged (a leaf above level L - levelsup leaves the node at the root) or empty.
+    tie_last / shallow_leaf_id: two WRONG variants (the last of equal minima; the leaf's own id for such a shallow leaf) that
+    tests/test_bow_cases.py holds its cases against."""
     cur, level, nid = 0, 0, 0
     while nodes[cur]["children"]:
         level += 1
         ch = nodes[cur]["children"]
         dist = [int(LUT[d ^ nodes[c]["desc"]].sum()) for c in ch]
-        cur = ch[int(np.argmin(dist))]                    # first minimum
+        cur = ch[len(dist) - 1 - int(np.argmin(dist[::-1]))] if tie_last else ch[int(np.argmin(dist))]      # first minimum
         if level == L - levelsup:
             nid = cur
-    return nodes[cur]["word"], nodes[cur]["w"], nid
+    if shallow_leaf_id and 0 < level < L - levelsup:
+        nid = cur
+    return nodes[cur].get("word", -1), nodes[cur]["w"], nid
 
 
 def test_vocab_parse_and_transform(oracle):
