@@ -10,7 +10,8 @@ that tiles are gathered from global memory: the test computes the boxes from the
 by 20 degrees leaves whole tiles outside the picture; a lens with k1 = 1e300 leaves everything outside.
 
 Then the pipeline behind level 0 (the oracle's pyrDown, the tracker's framed copies), one camera with R = I against
-ygz_hip_build_pyramid_undistorted, the other pyramid calls untouched by rig maps, YGZ_E_STATE, the validation errors through a live context,
+ygz_hip_build_pyramid_undistorted (at 640 x 480, and at 34 x 32 and 202 x 100, where both kernels take the byte paths of the body they
+share in csrc/remap_dev.h), the other pyramid calls untouched by rig maps, YGZ_E_STATE, the validation errors through a live context,
 and the raw textured pair of the rig through upload -> rectify -> detect -> stereo depths against the stereo restatement."""
 import ctypes
 
@@ -21,6 +22,7 @@ import rect_ref as rr
 import stereo_ref as sr
 import undist_ref as ur
 from conftest import make_ctx
+from test_gpu_undistort import case_fields
 
 pytestmark = pytest.mark.gpu
 
@@ -206,6 +208,43 @@ def test_one_camera_identity_is_the_lens_only_remap(vga, vga_pictures):
             for L in range(3):
                 assert np.array_equal(ctx.download_level(s, L), want[s][L]), (s, L)
     ctx.set_undistortion(drop=True)
+
+
+@pytest.mark.parametrize("shape", [(34, 32, SMALL_CAMERA), (202, 100, MID_CAMERA)], ids=["34x32", "202x100"])
+def test_identity_is_the_lens_only_remap_on_ragged_widths(hip_lib, shape):
+    """The same lens through ygz_hip_set_undistortion and through camera 0 of the rig with R = I, at widths that are no multiple of 4 or 16:
+    k_undistort and k_rectify go through the byte map loads, the byte staging and the byte stores of the one body they share.  tum_fr1: every
+    tile staged; zoom_4_2 at 202 x 100: a tile gathered from global memory."""
+    w, h, cam = shape
+    ctx = make_ctx(hip_lib, width=w, height=h, levels=1, max_frames=2, intrinsics=cam)
+    try:
+        gray, bgr = ur.picture(w, h, 90), ur.picture(w, h, 91, channels=3)
+        for name in ("tum_fr1", "zoom_4_2"):
+            fields = case_fields(name, cam, 200)
+            ctx.set_undistortion(**fields)
+            ctx.set_rectification(0, **fields)
+            rx, ry = ur.build_map(w, h, ur.params(cam, **fields), cam)
+            ux, uy = ctx.undistort_map()
+            qx, qy = ctx.rectify_map(0)
+            assert np.array_equal(ux, rx) and np.array_equal(uy, ry) and np.array_equal(qx, rx) and np.array_equal(qy, ry), name
+            box = rr.tile_boxes(rx, ry)
+            staged, gathered = (box[..., 4] == 1) & (box[..., 3] > 0), (box[..., 4] == 0) & (box[..., 3] > 0)
+            if name == "zoom_4_2" and w == 202:                                        # the whole picture is the box of the tile that sees it
+                assert gathered.sum() == 1 and not staged.any()
+            else:
+                assert staged.any() and not gathered.any(), name
+            for im in (bgr, gray):
+                from_bgr = im.ndim == 3
+                want = ur.remap(im, rx, ry, 200)
+                (ctx.upload_bgr if from_bgr else ctx.upload_gray)(0, im)
+                ctx.build_pyramid_undistorted(0, 1, from_bgr=from_bgr)
+                lens_only = ctx.download_level(0, 0)
+                (ctx.upload_bgr if from_bgr else ctx.upload_gray)(1, im)
+                ctx.build_pyramid_rectified([0], slot_begin=1, from_bgr=from_bgr)
+                rig = ctx.download_level(1, 0)
+                assert np.array_equal(lens_only, rig) and np.array_equal(rig, want), (name, "BGR" if from_bgr else "gray")
+    finally:
+        ctx.close()
 
 
 def test_the_other_pyramid_calls_do_not_see_the_rig(vga, hip_lib):

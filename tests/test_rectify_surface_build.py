@@ -17,7 +17,7 @@ import undist_ref as ur
 from test_rect_ref import random_rigs
 
 PKG = os.path.join(ROOT, "ygz_slam_amd")
-NEW_SOURCES = [os.path.join(PKG, "csrc", "rectify.hip"), os.path.join(PKG, "host", "ygz_rectify.cpp"), os.path.join(ROOT, "tests", "cpp", "rect_surface.cpp"),
+NEW_SOURCES = [os.path.join(PKG, "csrc", "rectify.hip"), os.path.join(PKG, "csrc", "remap_dev.h"), os.path.join(PKG, "host", "ygz_rectify.cpp"), os.path.join(ROOT, "tests", "cpp", "rect_surface.cpp"),
                os.path.join(ROOT, "include", "ygz", "Basic", "StereoRig.h")]
 
 

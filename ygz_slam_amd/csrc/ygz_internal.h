@@ -345,6 +345,11 @@ int ygz_launch_undistort(ygz_hip_ctx *ctx, int slot_begin, int n_slots, int from
 void ygz_undistort_free(ygz_hip_ctx *ctx);
 int ygz_launch_rectify(ygz_hip_ctx *ctx, int slot_begin, int n_slots, int from_bgr, const uint8_t *camera_of_slot);   // rectify.hip: level 0 = the slots' uploads through their cameras' rectifying maps
 void ygz_rectify_free(ygz_hip_ctx *ctx);
+// undistort.hip, for both launchers and their entry points: the source of the slots' remap (the BGR uploads, or their level 0 put aside in undist_plane),
+// the lens validation, and a device map of the context's size copied to the host (YGZ_E_STATE where the map is null)
+int ygz_remap_source(ygz_hip_ctx *ctx, int slot_begin, int n_slots, int from_bgr, const uint8_t **src);
+bool ygz_lens_valid(const ygz_undistort_params &p);
+int ygz_remap_map_to_host(ygz_hip_ctx *ctx, const int32_t *dqx, const int32_t *dqy, int32_t *qx, int32_t *qy);
 int ygz_launch_detect(ygz_hip_ctx *ctx, int slot_begin, int n_slots);
 int ygz_launch_describe(ygz_hip_ctx *ctx, int slot_begin, int n_slots);
 int ygz_track_ensure(ygz_hip_ctx *ctx);                      // allocates the resident tracking state
