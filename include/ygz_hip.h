@@ -71,7 +71,9 @@ extern "C" {
  * Still 6: stereo map-point creation added (ygz_smap_params, ygz_smap_problem, ygz_hip_default_smap_params, ygz_hip_stereo_create_map_points,
  * ygz_hip_stereo_keyframe_points) -- no existing argument list changed.
  * Still 6: local-map fusion search added (ygz_lfuse_params, ygz_lfuse_points, ygz_lfuse_problem, ygz_hip_default_lfuse_params,
- * ygz_hip_local_fuse_search) -- no existing argument list changed. */
+ * ygz_hip_local_fuse_search) -- no existing argument list changed.
+ * Still 6: the stereo tracking search added (ygz_strack_params, ygz_strack_points, ygz_strack_problem, ygz_hip_default_strack_params,
+ * ygz_hip_stereo_track_search) -- no existing argument list changed. */
 #define YGZ_HIP_ABI_VERSION 6
 
 typedef struct ygz_hip_ctx ygz_hip_ctx;
@@ -1328,6 +1330,83 @@ void ygz_hip_default_lfuse_params(ygz_lfuse_params *p);
 int  ygz_hip_local_fuse_search(ygz_hip_ctx *ctx, int n_sets, const ygz_lfuse_points *sets, int n_problems, const ygz_lfuse_problem *problems,
                                const double K4[4], const ygz_lfuse_params *params, int32_t *match, int32_t *dist, int32_t *pred_level,
                                int32_t *reason, int32_t *n_gated, int32_t *counts);
+
+/* ---- stereo tracking search -- nothing in the reference; ORB-SLAM2's two tracking searches on one kernel: ORBmatcher::SearchByProjection(
+ * CurrentFrame, LastFrame, th, bMono) (mode 0, FRAME) and SearchByProjection(F, vpMapPoints, th) (mode 1, LOCAL), each with the right-column
+ * test, the claim and (LOCAL) the ratio test, (FRAME) the rotation histogram.  The arithmetic is that of tests/strack_ref.c (DESIGN.md
+ * section 26); every output is bit-identical to it.
+ *
+ * A point set: pw [n_pt][3], pt_desc [n_pt][32]; for FRAME problems pt_level [n_pt] (the level of the last frame's feature) and pt_angle
+ * [n_pt] (degrees; NULL: no orientation check for the problems that read the set); for LOCAL problems pt_dmax [n_pt] and pt_normal [n_pt][3].
+ * A problem is one current frame: pose T = qx qy qz qw tx ty tz, world -> camera; th; mode; direction (-1, 0, +1; FRAME); keypoints kp_px
+ * [n_kp][2] (level-0 pixels), kp_level, kp_desc [n_kp][32], kp_ur [n_kp] (< 0: a mono keypoint; NULL: all mono), kp_angle [n_kp] (needed
+ * when the set has pt_angle and the mode is FRAME), kp_taken [n_kp] (optional); `set`, and pt_skip [n_pt of that set] (optional).
+ * Per (problem, point), on the device; the first failing step sets the reason (0 searched, 1 skip, 2 behind, 3 outside, 4 range, 5 angle):
+ *   the skip flag; z > 0; u, v inside [0, w) x [0, h); ur = u - bf / z with bf = fx baseline;
+ *   FRAME: lvl = pt_level, r = th 2^lvl, levels [lvl-1, lvl+1] (direction 0), [lvl, L-1] (+1), [0, lvl] (-1);
+ *   LOCAL: the distance range and the viewing angle of ygz_hip_search_by_projection, its predicted level; r = th f 2^pred with f = r_near
+ *   when Xc.(R n) > cos_near |Xc|, else r_wide; levels [pred-1, pred];
+ *   candidates: keypoints not taken, of a level in the range, |kx - u| < r, |ky - v| < r; a stereo keypoint with |ur - kp_ur| > r is rejected
+ *   (n_gated); n_cand counts the survivors; the list is the survivors sorted by (Hamming distance, index), the first YGZ_STRACK_TOPK.
+ * Then on the host, inside the call, per problem and points in index order: e1, e2 the first two entries of the list no earlier point
+ * took; outcome 1 without e1, 2 when dist(e1) > th_dist, 3 (LOCAL) when e2 has e1's level and dist(e1) > ratio dist(e2), else 0: match =
+ * e1, claimed.  outcome -1: reason != 0.  FRAME with angles and check_orientation: the 30-bin histogram of pt_angle - kp_angle[match], its
+ * three maxima; a match of another bin loses match and dist (outcome 4) and keeps its keypoint claimed.
+ * sizeof: ygz_strack_params 48, ygz_strack_points 56, ygz_strack_problem 136. */
+#define YGZ_STRACK_MAX_PROBLEMS 64
+#define YGZ_STRACK_MAX_SETS     8
+#define YGZ_STRACK_MAX_PAIRS    262144     /* per call: the sum over the problems of their set's n_pt */
+#define YGZ_STRACK_TOPK         8
+typedef struct {
+    double  baseline;                     /* 0.1: metres between the rig's cameras, > 0 */
+    double  ratio;                        /* 0.8: LOCAL's best / second-best rule, > 0 */
+    double  r_near, r_wide;               /* 2.5, 4.0: LOCAL's radius factors, > 0 */
+    double  cos_near;                     /* 0.998: the viewing cosine above which r_near applies */
+    int32_t th_dist;                      /* 100: the largest Hamming distance of a match, 0 .. 256 */
+    int32_t check_orientation;            /* 1: FRAME's rotation histogram */
+} ygz_strack_params;
+typedef struct {
+    const double  *pw;
+    const uint8_t *pt_desc;
+    const int32_t *pt_level;
+    const double  *pt_angle;
+    const double  *pt_dmax;
+    const double  *pt_normal;
+    int            n_pt;
+} ygz_strack_points;
+typedef struct {
+    double         T[7];
+    double         th;                    /* the window is th 2^level (FRAME) or th f 2^pred (LOCAL) pixels; > 0 */
+    const double  *kp_px;
+    const int32_t *kp_level;
+    const uint8_t *kp_desc;
+    const double  *kp_ur;
+    const double  *kp_angle;
+    const uint8_t *kp_taken;
+    const uint8_t *pt_skip;
+    int            n_kp;
+    int            set;
+    int            mode;                  /* 0 FRAME, 1 LOCAL */
+    int            direction;             /* FRAME: +1 forward (same or coarser levels), -1 backward, 0 neither */
+} ygz_strack_problem;
+void ygz_hip_default_strack_params(ygz_strack_params *p);
+/* all problems in one launch, every point set uploaded once.  The outputs are concatenated in problem order, a problem contributing n_pt
+ * entries of its set: match, dist, level, reason, outcome, n_cand, n_gated [N]; proj [N][3] = u, v, ur; cand [N][YGZ_STRACK_TOPK] the list
+ * before the claim as keypoint indices, -1 padded; counts [n_problems][4] = matches, points searched, overflowed (n_cand above
+ * YGZ_STRACK_TOPK), removed by the orientation check; rot [n_problems][33] the histogram and the three maxima (-1: none).  Every output may
+ * be NULL.  params NULL: defaults.  One packed upload, one launch, one copy back and one wait.  Checked in this order, all before the device
+ * is touched: YGZ_E_INVALID for null sets, problems or K4, n_sets < 1 or n_problems < 1; YGZ_E_CAPACITY above YGZ_STRACK_MAX_SETS or
+ * YGZ_STRACK_MAX_PROBLEMS; YGZ_E_INVALID for a set's n_pt < 0 or a null pw or pt_desc of a set with points, for a problem's set index out of
+ * range, n_kp < 1, a null kp_px, kp_level or kp_desc, a mode or direction out of range, th <= 0 or not finite, a FRAME problem whose set has
+ * points and no pt_level or has pt_angle while the problem has no kp_angle, a LOCAL problem whose set has points and no pt_dmax or pt_normal;
+ * YGZ_E_CAPACITY for n_kp above 2^20 or more than YGZ_STRACK_MAX_PAIRS pairs; YGZ_E_INVALID for th_dist outside [0, 256], baseline, ratio,
+ * r_near or r_wide <= 0 or a parameter not finite, a non-finite K4, a focal length <= 0, a non-finite pose, point, dmax, normal, angle or
+ * kp_ur; last, YGZ_E_INVALID for a null context, YGZ_E_CAPACITY for n_kp above ygz_hip_max_keypoints and YGZ_E_INVALID for a kp_level or
+ * (FRAME) pt_level outside the context's pyramid.  A call whose every problem reads an empty set launches nothing. */
+int  ygz_hip_stereo_track_search(ygz_hip_ctx *ctx, int n_sets, const ygz_strack_points *sets, int n_problems, const ygz_strack_problem *problems,
+                                 const double K4[4], const ygz_strack_params *params, int32_t *match, int32_t *dist, int32_t *level,
+                                 int32_t *reason, int32_t *outcome, int32_t *n_cand, int32_t *n_gated, double *proj, int32_t *cand,
+                                 int32_t *counts, int32_t *rot);
 
 #ifdef __cplusplus
 }

@@ -589,6 +589,34 @@ def lfuse_argtypes(lib):
                                               ip, ip, ip, ip, ip, ip]
 
 
+class StrackParams(C.Structure):
+    """ygz_strack_params (include/ygz_hip.h)"""
+    _fields_ = [("baseline", C.c_double), ("ratio", C.c_double), ("r_near", C.c_double), ("r_wide", C.c_double), ("cos_near", C.c_double),
+                ("th_dist", C.c_int32), ("check_orientation", C.c_int32)]
+
+
+class StrackPoints(C.Structure):
+    """ygz_strack_points (include/ygz_hip.h)"""
+    _fields_ = [("pw", C.POINTER(C.c_double)), ("pt_desc", C.POINTER(C.c_uint8)), ("pt_level", C.POINTER(C.c_int32)),
+                ("pt_angle", C.POINTER(C.c_double)), ("pt_dmax", C.POINTER(C.c_double)), ("pt_normal", C.POINTER(C.c_double)), ("n_pt", C.c_int)]
+
+
+class StrackProblem(C.Structure):
+    """ygz_strack_problem (include/ygz_hip.h)"""
+    _fields_ = [("T", C.c_double * 7), ("th", C.c_double), ("kp_px", C.POINTER(C.c_double)), ("kp_level", C.POINTER(C.c_int32)),
+                ("kp_desc", C.POINTER(C.c_uint8)), ("kp_ur", C.POINTER(C.c_double)), ("kp_angle", C.POINTER(C.c_double)),
+                ("kp_taken", C.POINTER(C.c_uint8)), ("pt_skip", C.POINTER(C.c_uint8)), ("n_kp", C.c_int), ("set", C.c_int), ("mode", C.c_int),
+                ("direction", C.c_int)]
+
+
+def strack_argtypes(lib):
+    ip, dp, pp = C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(StrackParams)
+    lib.ygz_hip_default_strack_params.argtypes = [pp]
+    lib.ygz_hip_default_strack_params.restype = None
+    lib.ygz_hip_stereo_track_search.argtypes = [C.c_void_p, C.c_int, C.POINTER(StrackPoints), C.c_int, C.POINTER(StrackProblem), dp, pp,
+                                                ip, ip, ip, ip, ip, ip, ip, dp, ip, ip, ip]
+
+
 # every symbol include/ygz_hip.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
     "ygz_hip_default_params", "ygz_hip_create", "ygz_hip_destroy", "ygz_hip_synchronize", "ygz_hip_join", "ygz_hip_set_overlap", "ygz_hip_error_string",
@@ -627,6 +655,7 @@ ABI_SYMBOLS = [
     "ygz_hip_stereo_rectify", "ygz_hip_default_rectify_params", "ygz_hip_set_rectification", "ygz_hip_rectify_map", "ygz_hip_build_pyramid_rectified",
     "ygz_hip_default_smap_params", "ygz_hip_stereo_create_map_points", "ygz_hip_stereo_keyframe_points",
     "ygz_hip_default_lfuse_params", "ygz_hip_local_fuse_search",
+    "ygz_hip_default_strack_params", "ygz_hip_stereo_track_search",
 ]
 INIT_SYMBOLS = ["ygz_hip_default_init_params", "ygz_hip_initialize", "ygz_hip_init_sample_sets", "ygz_hip_init_hypotheses", "ygz_hip_init_reconstruct"]
 INIT_NONE, INIT_H, INIT_F = 0, 1, 2
@@ -674,6 +703,12 @@ SMAP_MAX_PROBLEMS, SMAP_MAX_PAIRS = 32, 65536
 LFUSE_SYMBOLS = ["ygz_hip_default_lfuse_params", "ygz_hip_local_fuse_search"]
 LFUSE_MAX_PROBLEMS, LFUSE_MAX_SETS, LFUSE_MAX_PAIRS = 64, 8, 1048576
 LFUSE_SEARCHED, LFUSE_SKIP, LFUSE_BEHIND, LFUSE_OUTSIDE, LFUSE_RANGE, LFUSE_ANGLE = range(6)
+
+STRACK_SYMBOLS = ["ygz_hip_default_strack_params", "ygz_hip_stereo_track_search"]
+STRACK_MAX_PROBLEMS, STRACK_MAX_SETS, STRACK_MAX_PAIRS, STRACK_TOPK = 64, 8, 262144, 8
+STRACK_FRAME, STRACK_LOCAL = 0, 1
+STRACK_SEARCHED, STRACK_SKIP, STRACK_BEHIND, STRACK_OUTSIDE, STRACK_RANGE, STRACK_ANGLE = range(6)
+STRACK_MATCHED, STRACK_NO_CANDIDATE, STRACK_DISTANCE, STRACK_RATIO, STRACK_ORIENTATION = range(5)
 
 POPT_SYMBOLS = ["ygz_hip_default_pose_opt_params", "ygz_hip_optimize_pose_stereo"]
 POPT_FAILED, POPT_CONVERGED, POPT_MAX_ITERATIONS, POPT_STALLED = range(4)
@@ -1121,6 +1156,73 @@ class HipContext:
         del keep
         o = {k: v[:N] for k, v in o.items()}
         o["counts"], o["offsets"] = counts[:len(problems)], np.array(off, np.int64)
+        return o
+
+    # ---- stereo tracking search
+    def default_strack_params(self, **fields):
+        """ygz_hip_default_strack_params, with the given fields overwritten"""
+        strack_argtypes(self.lib)
+        p = StrackParams()
+        self.lib.ygz_hip_default_strack_params(C.byref(p))
+        for k, v in fields.items():
+            getattr(p, k)                   # AttributeError for a field the struct does not have
+            setattr(p, k, v)
+        return p
+
+    def stereo_track_search(self, sets, problems, K4, params=None, **fields):
+        """ORB-SLAM2's two tracking searches (frame to frame, local map) with the right-column gate, one call.  sets: dicts of pw [n, 3],
+        pt_desc [n, 32] and pt_level [n], pt_angle [n] (optional) for FRAME or pt_dmax [n], pt_normal [n, 3] for LOCAL problems; problems:
+        dicts of T [7], th, mode (0 FRAME, 1 LOCAL), direction, kp_px [m, 2], kp_level [m], kp_desc [m, 32], kp_ur [m] (optional, < 0:
+        mono), kp_angle [m], kp_taken [m], pt_skip [n of its set] (optional) and set (default 0).  Dict of match, dist, level, reason,
+        outcome, n_cand, n_gated [N], proj [N, 3], cand [N, 8] concatenated in problem order, counts [n_problems, 4] (matches, searched,
+        overflowed, removed by orientation), rot [n_problems, 33] and offsets [n_problems + 1]."""
+        p = params if params is not None else self.default_strack_params(**fields)
+        strack_argtypes(self.lib)
+        keep = []
+
+        def put(d, name, t, ct, n):
+            a = d.get(name)
+            if a is None:
+                return C.POINTER(ct)()
+            a = np.ascontiguousarray(a, t).reshape(-1)
+            if len(a) != n:
+                raise ValueError("%s has the wrong length" % name)
+            keep.append(a)
+            return _p(a, ct)
+        sa = (StrackPoints * max(len(sets), 1))()
+        for s, d in enumerate(sets):
+            n = len(np.asarray(d["pt_desc"]).reshape(-1)) // 32
+            sa[s].pw, sa[s].pt_desc = put(d, "pw", np.float64, C.c_double, 3 * n), put(d, "pt_desc", np.uint8, C.c_uint8, 32 * n)
+            sa[s].pt_level, sa[s].pt_angle = put(d, "pt_level", np.int32, C.c_int32, n), put(d, "pt_angle", np.float64, C.c_double, n)
+            sa[s].pt_dmax, sa[s].pt_normal = put(d, "pt_dmax", np.float64, C.c_double, n), put(d, "pt_normal", np.float64, C.c_double, 3 * n)
+            sa[s].n_pt = n
+        pa = (StrackProblem * max(len(problems), 1))()
+        off = [0]
+        for q, d in enumerate(problems):
+            T = np.ascontiguousarray(d["T"], np.float64).reshape(7)
+            for k in range(7):
+                pa[q].T[k] = T[k]
+            m, st = len(np.asarray(d["kp_level"]).reshape(-1)), int(d.get("set", 0))
+            n = int(sa[st].n_pt) if 0 <= st < len(sets) else 0
+            pa[q].th, pa[q].mode, pa[q].direction = float(d["th"]), int(d.get("mode", 0)), int(d.get("direction", 0))
+            pa[q].kp_px, pa[q].kp_level = put(d, "kp_px", np.float64, C.c_double, 2 * m), put(d, "kp_level", np.int32, C.c_int32, m)
+            pa[q].kp_desc, pa[q].kp_ur = put(d, "kp_desc", np.uint8, C.c_uint8, 32 * m), put(d, "kp_ur", np.float64, C.c_double, m)
+            pa[q].kp_angle = put(d, "kp_angle", np.float64, C.c_double, m)
+            pa[q].kp_taken, pa[q].pt_skip = put(d, "kp_taken", np.uint8, C.c_uint8, m), put(d, "pt_skip", np.uint8, C.c_uint8, n)
+            pa[q].n_kp, pa[q].set = m, st
+            off.append(off[-1] + n)
+        N, Q = off[-1], len(problems)
+        names = ("match", "dist", "level", "reason", "outcome", "n_cand", "n_gated")
+        o = {k: np.full(max(N, 1), -7, np.int32) for k in names}
+        proj, cand = np.zeros((max(N, 1), 3), np.float64), np.full((max(N, 1), STRACK_TOPK), -7, np.int32)
+        counts, rot = np.zeros((max(Q, 1), 4), np.int32), np.zeros((max(Q, 1), 33), np.int32)
+        k4 = np.ascontiguousarray(K4, np.float64).reshape(4)
+        self._chk(self.lib.ygz_hip_stereo_track_search(self._ctx, len(sets), sa, Q, pa, _p(k4, C.c_double), C.byref(p),
+                                                       *[_p(o[k], C.c_int32) for k in names], _p(proj, C.c_double), _p(cand, C.c_int32),
+                                                       _p(counts, C.c_int32), _p(rot, C.c_int32)), "stereo_track_search")
+        del keep
+        o = {k: v[:N] for k, v in o.items()}
+        o["proj"], o["cand"], o["counts"], o["rot"], o["offsets"] = proj[:N], cand[:N], counts[:Q], rot[:Q], np.array(off, np.int64)
         return o
 
     # ---- keyframe store / device-built BA windows (configs[4])
