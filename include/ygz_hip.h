@@ -73,7 +73,9 @@ extern "C" {
  * Still 6: local-map fusion search added (ygz_lfuse_params, ygz_lfuse_points, ygz_lfuse_problem, ygz_hip_default_lfuse_params,
  * ygz_hip_local_fuse_search) -- no existing argument list changed.
  * Still 6: the stereo tracking search added (ygz_strack_params, ygz_strack_points, ygz_strack_problem, ygz_hip_default_strack_params,
- * ygz_hip_stereo_track_search) -- no existing argument list changed. */
+ * ygz_hip_stereo_track_search) -- no existing argument list changed.
+ * Still 6: stereo odometry on resident slots added (ygz_svo_params, ygz_hip_default_svo_params, ygz_hip_stereo_odometry_slots) -- no existing
+ * argument list changed. */
 #define YGZ_HIP_ABI_VERSION 6
 
 typedef struct ygz_hip_ctx ygz_hip_ctx;
@@ -1407,6 +1409,56 @@ int  ygz_hip_stereo_track_search(ygz_hip_ctx *ctx, int n_sets, const ygz_strack_
                                  const double K4[4], const ygz_strack_params *params, int32_t *match, int32_t *dist, int32_t *level,
                                  int32_t *reason, int32_t *outcome, int32_t *n_cand, int32_t *n_gated, double *proj, int32_t *cand,
                                  int32_t *counts, int32_t *rot);
+
+/* ---- stereo odometry on resident slots -- nothing in the reference; ORB-SLAM2's TrackWithMotionModel on the last frame's own depths (the
+ * visual-odometry points of UpdateLastFrame), for any number of (last, current) slot pairs in one call.  The result is the composition of two
+ * frozen specifications, tests/strack_ref.c and tests/popt_ref.c, joined by three formulas (tests/svo_ref.py restates it),
+ * and every output is bit-identical to that composition.  Per pair p, L = last_slot[p], C = cur_slot[p], K = the context's float intrinsics as
+ * doubles, bf = fx baseline, T_init[p] = qx qy qz qw tx ty tz the guess of the pose that takes last-camera to current-camera coordinates:
+ *   points: all of L's keypoints in keypoint order; point i has a depth z when kp_has_mp[i] != 0 and kp_depth[i] > 0 (a NaN does not count);
+ *   without one it is skipped, with one pw = (((u - cx) / fx) z, ((v - cy) / fy) z, z); its level, angle and descriptor are the keypoint's;
+ *   problem: C's keypoints, kp_ur[j] = u_j - bf / depth_j with a depth, else -1 (negative: a mono keypoint), mode FRAME, nothing taken,
+ *   direction[p], pose T_init[p], window params.th;
+ *   search, claim walk and orientation rule of ygz_hip_stereo_track_search; with fewer than min_matches matches all of it again from scratch
+ *   with th doubled (retried = 1), and the second pass's outputs are the pair's; still fewer: status = 1;
+ *   status 0: the matched points in point order are the edges (pw_i; kx_j, ky_j, kp_ur[j]; kp_level[j]; kind 2 when kp_ur[j] >= 0, else 1) of
+ *   ygz_hip_optimize_pose_stereo from the entry pose T_init[p] with params.pose (its baseline is the call's); status 1: no edge, so the pair is
+ *   FAILED in round 0 and keeps its pose.  T_rel[p] is the pose returned; current = T_rel last.
+ * Every pair works in its last camera's frame, so pairs are independent and a slot may be the current frame of one and the last of another.
+ * The keypoints and depths are read where ygz_hip_detect / ygz_hip_describe_given_angle and ygz_hip_set_keypoint_depths /
+ * ygz_hip_stereo_depths_slots (write_depths) left them; the host reads no count before the launches.  One packed upload, the launches
+ * (k_svo_gather, k_strack_search, k_svo_resolve, both again for the retry, k_pose_opt, k_svo_scatter), one copy back, one wait.
+ * sizeof: ygz_svo_params 88. */
+#define YGZ_SVO_MAX_PAIRS 1024
+typedef struct {
+    double  baseline;                     /* 0.1: metres between the rig's cameras, > 0 */
+    double  th;                           /* 7.0: the window is th 2^level pixels, > 0; doubled for the retry */
+    int32_t th_dist;                      /* 100: the largest Hamming distance of a match, 0 .. 256 */
+    int32_t check_orientation;            /* 1: the rotation histogram */
+    int32_t min_matches;                  /* 20: fewer matches retry, then fail; >= 0 */
+    int32_t pad;
+    ygz_pose_opt_params pose;             /* ygz_hip_default_pose_opt_params; its baseline is ignored: the call's is used */
+} ygz_svo_params;
+void ygz_hip_default_svo_params(ygz_svo_params *p);
+/* T_init [n_pairs][7] (NULL: identity), direction [n_pairs] in {-1, 0, 1} (NULL: derived per pair on the host from T_init and the baseline:
+ * +1 when the current camera is more than a baseline in front of the last one, -1 behind, else 0), params NULL: defaults.  Outputs, with cells =
+ * ygz_hip_max_keypoints, any of them may be NULL except T_rel: T_rel [n][7]; status [n] (0 tracked, 1 too few matches); counts [n][8] = last
+ * keypoints, points with a depth, current keypoints, matches, points searched, overflowed, removed by orientation, retried; match, dist,
+ * level, reason, outcome, n_cand, n_gated [n][cells] indexed by L's keypoint (-1 past its last keypoint), proj [n][cells][3] (0 past it),
+ * rot [n][33], as ygz_hip_stereo_track_search defines them; outlier [n][cells] (0 where there is no edge) and chi2 [n][cells] (-1.0 there) of
+ * the pose optimiser in point order; inliers, rounds_run [n] and round_status, round_iterations, round_cost_initial, round_cost_final,
+ * round_lambda [n][8].  Checked in this order, all before the device is touched: YGZ_E_INVALID for a null last_slot, cur_slot or T_rel or
+ * n_pairs < 1; YGZ_E_CAPACITY above YGZ_SVO_MAX_PAIRS; YGZ_E_INVALID for a non-finite parameter, baseline <= 0, th <= 0, th_dist outside
+ * [0, 256], min_matches < 0, the rules of ygz_hip_optimize_pose_stereo for params.pose (a chi2 <= 0, rounds outside 1 .. 8, iterations or
+ * max_trials outside 1 .. 64), a non-finite T_init, a direction outside {-1, 0, 1}, a negative slot, last == cur in a pair; last,
+ * YGZ_E_INVALID for a null context or a slot past the context's frames, YGZ_E_CAPACITY for a context of more than 32768 cells, YGZ_E_STATE for
+ * a slot without keypoints (no pyramid was ever built for it) or a context whose keypoint depths were never written. */
+int  ygz_hip_stereo_odometry_slots(ygz_hip_ctx *ctx, int n_pairs, const int32_t *last_slot, const int32_t *cur_slot, const double *T_init,
+                                   const int32_t *direction, const ygz_svo_params *params, double *T_rel, int32_t *status, int32_t *counts,
+                                   int32_t *match, int32_t *dist, int32_t *level, int32_t *reason, int32_t *outcome, int32_t *n_cand,
+                                   int32_t *n_gated, double *proj, int32_t *rot, uint8_t *outlier, double *chi2, int32_t *inliers,
+                                   int32_t *rounds_run, int32_t *round_status, int32_t *round_iterations, double *round_cost_initial,
+                                   double *round_cost_final, double *round_lambda);
 
 #ifdef __cplusplus
 }

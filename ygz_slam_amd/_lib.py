@@ -617,6 +617,20 @@ def strack_argtypes(lib):
                                                 ip, ip, ip, ip, ip, ip, ip, dp, ip, ip, ip]
 
 
+class SvoParams(C.Structure):
+    """ygz_svo_params (include/ygz_hip.h)"""
+    _fields_ = [("baseline", C.c_double), ("th", C.c_double), ("th_dist", C.c_int32), ("check_orientation", C.c_int32),
+                ("min_matches", C.c_int32), ("pad", C.c_int32), ("pose", PoseOptParams)]
+
+
+def svo_argtypes(lib):
+    ip, dp, bp, pp = C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.POINTER(SvoParams)
+    lib.ygz_hip_default_svo_params.argtypes = [pp]
+    lib.ygz_hip_default_svo_params.restype = None
+    lib.ygz_hip_stereo_odometry_slots.argtypes = [C.c_void_p, C.c_int, ip, ip, dp, ip, pp, dp, ip, ip, ip, ip, ip, ip, ip, ip, ip, dp, ip, bp, dp,
+                                                  ip, ip, ip, ip, dp, dp, dp]
+
+
 # every symbol include/ygz_hip.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
     "ygz_hip_default_params", "ygz_hip_create", "ygz_hip_destroy", "ygz_hip_synchronize", "ygz_hip_join", "ygz_hip_set_overlap", "ygz_hip_error_string",
@@ -656,6 +670,7 @@ ABI_SYMBOLS = [
     "ygz_hip_default_smap_params", "ygz_hip_stereo_create_map_points", "ygz_hip_stereo_keyframe_points",
     "ygz_hip_default_lfuse_params", "ygz_hip_local_fuse_search",
     "ygz_hip_default_strack_params", "ygz_hip_stereo_track_search",
+    "ygz_hip_default_svo_params", "ygz_hip_stereo_odometry_slots",
 ]
 INIT_SYMBOLS = ["ygz_hip_default_init_params", "ygz_hip_initialize", "ygz_hip_init_sample_sets", "ygz_hip_init_hypotheses", "ygz_hip_init_reconstruct"]
 INIT_NONE, INIT_H, INIT_F = 0, 1, 2
@@ -709,6 +724,11 @@ STRACK_MAX_PROBLEMS, STRACK_MAX_SETS, STRACK_MAX_PAIRS, STRACK_TOPK = 64, 8, 262
 STRACK_FRAME, STRACK_LOCAL = 0, 1
 STRACK_SEARCHED, STRACK_SKIP, STRACK_BEHIND, STRACK_OUTSIDE, STRACK_RANGE, STRACK_ANGLE = range(6)
 STRACK_MATCHED, STRACK_NO_CANDIDATE, STRACK_DISTANCE, STRACK_RATIO, STRACK_ORIENTATION = range(5)
+
+SVO_SYMBOLS = ["ygz_hip_default_svo_params", "ygz_hip_stereo_odometry_slots"]
+SVO_MAX_PAIRS = 1024
+SVO_INT_OUTPUTS = ("match", "dist", "level", "reason", "outcome", "n_cand", "n_gated")
+SVO_COUNTS = ("last_keypoints", "with_depth", "cur_keypoints", "matches", "searched", "overflowed", "removed_by_orientation", "retried")
 
 POPT_SYMBOLS = ["ygz_hip_default_pose_opt_params", "ygz_hip_optimize_pose_stereo"]
 POPT_FAILED, POPT_CONVERGED, POPT_MAX_ITERATIONS, POPT_STALLED = range(4)
@@ -1224,6 +1244,52 @@ class HipContext:
         o = {k: v[:N] for k, v in o.items()}
         o["proj"], o["cand"], o["counts"], o["rot"], o["offsets"] = proj[:N], cand[:N], counts[:Q], rot[:Q], np.array(off, np.int64)
         return o
+
+    # ---- stereo odometry on resident slots
+    def default_svo_params(self, **fields):
+        """ygz_hip_default_svo_params, with the given fields overwritten; a field of the embedded ygz_pose_opt_params is given as pose_<name>"""
+        svo_argtypes(self.lib)
+        p = SvoParams()
+        self.lib.ygz_hip_default_svo_params(C.byref(p))
+        for k, v in fields.items():
+            tgt, name = (p.pose, k[5:]) if k.startswith("pose_") else (p, k)
+            getattr(tgt, name)              # AttributeError for a field the struct does not have
+            setattr(tgt, name, v)
+        return p
+
+    def stereo_odometry_slots(self, last_slots, cur_slots, T_init=None, direction=None, params=None, outputs=True, **fields):
+        """frame-to-frame stereo odometry for the resident pairs (last_slots[p], cur_slots[p]) in one call: the FRAME search with the
+        right-column gate on the last frame's own depths, the claim walk, the orientation rule, the retry at twice the window and the u, v, uR
+        pose optimisation.  T_init [n, 7] (None: identity), direction [n] (None: derived).  Dict of T_rel [n, 7], status [n], counts [n, 8],
+        match, dist, level, reason, outcome, n_cand, n_gated [n, cells] by the last frame's keypoint, proj [n, cells, 3], rot [n, 33],
+        outlier, chi2 [n, cells], inliers, rounds_run [n] and round_status, lm_iterations, cost_initial, cost_final, lambda [n, 8];
+        outputs=False passes NULL for everything but T_rel and status."""
+        p = params if params is not None else self.default_svo_params(**fields)
+        svo_argtypes(self.lib)
+        ls, cs = np.ascontiguousarray(last_slots, np.int32).reshape(-1), np.ascontiguousarray(cur_slots, np.int32).reshape(-1)
+        if len(ls) != len(cs):
+            raise ValueError("last_slots and cur_slots differ in length")
+        n, c, R = len(ls), self.cells, POPT_MAX_ROUNDS
+        T0 = None if T_init is None else np.ascontiguousarray(T_init, np.float64).reshape(n, 7)
+        dr = None if direction is None else np.ascontiguousarray(direction, np.int32).reshape(n)
+        m = max(n, 1)
+        o = dict(T_rel=np.zeros((m, 7)), status=np.full(m, -7, np.int32))
+        names = ("counts",) + SVO_INT_OUTPUTS + ("proj", "rot", "outlier", "chi2", "inliers", "rounds_run", "round_status", "lm_iterations",
+                                                 "cost_initial", "cost_final", "lambda")
+        if outputs:
+            o.update(counts=np.full((m, 8), -7, np.int32), proj=np.zeros((m, c, 3)), rot=np.full((m, 33), -7, np.int32),
+                     outlier=np.full((m, c), 7, np.uint8), chi2=np.zeros((m, c)), inliers=np.full(m, -7, np.int32),
+                     rounds_run=np.full(m, -7, np.int32), round_status=np.full((m, R), -7, np.int32),
+                     lm_iterations=np.full((m, R), -7, np.int32), cost_initial=np.zeros((m, R)), cost_final=np.zeros((m, R)))
+            o["lambda"] = np.zeros((m, R))
+            for k in SVO_INT_OUTPUTS:
+                o[k] = np.full((m, c), -7, np.int32)
+        types = {np.dtype(np.int32): C.c_int32, np.dtype(np.float64): C.c_double, np.dtype(np.uint8): C.c_uint8}
+        f = lambda k: _p(o[k], types[o[k].dtype]) if k in o else None
+        self._chk(self.lib.ygz_hip_stereo_odometry_slots(
+            self._ctx, n, _p(ls, C.c_int32), _p(cs, C.c_int32), None if T0 is None else _p(T0, C.c_double),
+            None if dr is None else _p(dr, C.c_int32), C.byref(p), f("T_rel"), f("status"), *[f(k) for k in names]), "stereo_odometry_slots")
+        return {k: v[:n] for k, v in o.items()}
 
     # ---- keyframe store / device-built BA windows (configs[4])
     def stream_wait(self, signaler):

@@ -11,6 +11,7 @@
 // for another workgroup, no scratch, no environment switch.  The edges are fetched per pass (no register cache): a frame of any length takes the
 // same path.
 #include "ygz_internal.h"
+#include "popt_dev.h"                   // PoptArgs and the kernel's prototype: svo.hip launches it too
 #include <math.h>
 #include <string.h>
 #pragma clang fp contract(off)
@@ -19,22 +20,7 @@
 #define PT_NV 28
 #define PT_DMAX 1.7976931348623157e308
 
-struct PoptArgs {
-    const int32_t *off;                 // [n_frames + 1]
-    const double *pw, *obs;             // [n][3], [n][3]
-    const int32_t *level;
-    const uint8_t *kind;
-    double *poses;                      // [n_frames][7] in and out
-    double *chi2;                       // [n]
-    double *cost_initial, *cost_final, *lambda;    // [n_frames][8]
-    int32_t *status, *iterations;       // [n_frames][8]
-    int32_t *inliers, *rounds_run;      // [n_frames]
-    uint8_t *outlier;                   // [n]: the flags of the last classification, read by the passes of the next round
-    double K[5];                        // fx fy cx cy bf
-    double d2m, d2s, dm, ds;            // chi2_mono, chi2_stereo and their square roots
-    double min_rel_decrease;
-    int rounds, iters, max_trials, robust_rounds, min_edges, min_inliers;
-};
+static_assert(PT_THREADS == PT_DEV_THREADS, "popt_dev.h states this file's block size");
 
 enum { PT_PH_LIN = 0, PT_PH_TRIAL = 1, PT_PH_DONE = 2 };
 
@@ -286,7 +272,7 @@ __global__ __launch_bounds__(PT_THREADS) void k_pose_opt(PoptArgs A)
     __shared__ double sum[PT_NV];
     __shared__ PoptState S;
     const int f = blockIdx.x, tid = threadIdx.x;
-    const int beg = A.off[f], n = A.off[f + 1] - beg;
+    const int beg = A.off[f], n = (A.end ? A.end[f] : A.off[f + 1]) - beg;
     const size_t fr = (size_t)f * YGZ_POPT_MAX_ROUNDS;
     if (tid < 7) { const double v = A.poses[7 * (size_t)f + tid]; S.entry[tid] = v; S.T[tid] = v; }
     if (tid == 0) {
@@ -455,7 +441,7 @@ extern "C" int ygz_hip_optimize_pose_stereo(ygz_hip_ctx *ctx, int n_frames, cons
     if ((rc = ygz_kcopy(ctx, db, hb, o_pose + b_pose, hipMemcpyHostToDevice)) != YGZ_OK) return rc;
 
     PoptArgs A;
-    A.off = (const int32_t *)(db + o_off); A.pw = (const double *)(db + o_pw); A.obs = (const double *)(db + o_obs);
+    A.off = (const int32_t *)(db + o_off); A.end = nullptr; A.pw = (const double *)(db + o_pw); A.obs = (const double *)(db + o_obs);
     A.level = (const int32_t *)(db + o_level); A.kind = db + o_kind;
     A.poses = (double *)(db + o_pose); A.chi2 = (double *)(db + o_chi2);
     A.cost_initial = (double *)(db + o_ci); A.cost_final = (double *)(db + o_cf); A.lambda = (double *)(db + o_lam);

@@ -16,6 +16,7 @@
 // No atomic, no wait for another workgroup, no scratch, no environment switch.  One packed upload, one launch, one copy back, one wait.
 #include "ygz_internal.h"
 #include "se3_dev.h"
+#include "strack_dev.h"                 // StIn, StSetDev, StProbDev and the kernel's prototype: svo.hip launches it too
 #include <math.h>
 #include <string.h>
 #pragma clang fp contract(off)
@@ -27,16 +28,7 @@
 #define ST_TAKEN     0x40000000         // the level a taken keypoint, or an entry past the end, is given in LDS: in no level range
 #define ST_NO_KEY    0xFFFFFFFFu
 
-struct StIn { double K4[4]; double bf, r_near, r_wide, cos_near; int32_t w, h, L, pad_; };
-
-struct StSetDev { const double *pw; const uint32_t *pt_desc; const int32_t *pt_level; const double *pt_dmax; const double *pt_normal; int32_t n_pt, pad_; };
-
-struct StProbDev {
-    const double *kp_px; const int32_t *kp_level; const uint32_t *kp_desc; const double *kp_ur; const uint8_t *kp_taken; const uint8_t *pt_skip;
-    int32_t n_kp, set, pt_off, mode, direction, pad_;
-    double th;
-    double T[7];
-};
+static_assert(ST_LANES == ST_DEV_LANES && ST_IDX_BITS == ST_DEV_IDX_BITS && ST_NO_KEY == ST_DEV_NO_KEY, "strack_dev.h states this file's constants");
 
 struct StKp { double kx, ky, ur; int32_t level, pad_; };     // 32 bytes; the descriptor is another 32
 

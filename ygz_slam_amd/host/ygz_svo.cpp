@@ -1,0 +1,110 @@
+// ygz::StereoOdometry (include/ygz/Algorithm/StereoOdometry.h): nothing in the reference.  Frame-to-frame stereo odometry for any number of
+// (current, last) pairs: the frames' feature lists and depths are put into their slots the way ygz_host.cpp describes feature lists, then ONE
+// entry point (ygz_hip_stereo_odometry_slots, ygz_slam_amd/csrc/svo.hip) searches, claims, retries and optimises on the device.  The spec is
+// DESIGN.md section 27.  No map, no point and no _mappoint is touched.  Error conventions of the other surfaces: a failed call logs and returns
+// 0, only a missing device throws.
+#include "ygz/Algorithm/StereoOdometry.h"
+#include "ygz/hip/Runtime.h"
+#include "ygz_hip.h"
+#include <algorithm>
+#include <map>
+
+namespace ygz {
+
+int StereoOdometry::TrackPairs(const std::vector<std::pair<Frame *, Frame *>> &pairs, const std::vector<SE3> *guesses, std::vector<Result> *results)
+{
+    if (results) results->clear();
+    const size_t n = pairs.size();
+    if (n == 0 || (guesses && guesses->size() != n)) {
+        LOG(ERROR) << "StereoOdometry::TrackPairs: no pair, or guesses of another length" << endl;
+        return 0;
+    }
+    hip::Runtime &rt = hip::Runtime::Get();
+    ygz_hip_ctx *c = rt.ctx();
+    const int cells = rt.cells();
+    // 1: the distinct frames in the order they first appear, each in a slot
+    std::vector<Frame *> frames;
+    for (const auto &pr : pairs) {
+        if (!pr.first || !pr.second || pr.first == pr.second) {
+            LOG(ERROR) << "StereoOdometry::TrackPairs: a pair without a frame, or of one frame" << endl;
+            return 0;
+        }
+        for (Frame *f : { pr.second, pr.first })
+            if (std::find(frames.begin(), frames.end(), f) == frames.end()) frames.push_back(f);
+    }
+    std::map<Frame *, int> slot;
+    for (Frame *f : frames) {
+        if ((int)f->_features.size() > cells) {
+            LOG(ERROR) << "StereoOdometry::TrackPairs: a frame with more features than the context has cells" << endl;
+            return 0;
+        }
+        slot[f] = rt.Resident(f);
+    }
+    for (Frame *f : frames)                                              // a later frame may have taken an earlier one's slot
+        if (slot[f] < 0 || rt.Resident(f) != slot[f]) {
+            LOG(ERROR) << "StereoOdometry::TrackPairs: more distinct frames than the runtime keeps resident" << endl;
+            return 0;
+        }
+    // 2: the feature lists and their depths
+    for (Frame *f : frames) {
+        const int m = (int)f->_features.size();
+        std::vector<double> px(2 * (size_t)m), depth((size_t)m);
+        std::vector<int32_t> lvl((size_t)m);
+        std::vector<float> ang((size_t)m);
+        std::vector<uint8_t> has((size_t)m);
+        for (int i = 0; i < m; ++i) {
+            const Feature *ft = f->_features[i];
+            if (!ft) { LOG(ERROR) << "StereoOdometry::TrackPairs: a null feature" << endl; return 0; }
+            px[2 * (size_t)i] = ft->_pixel[0]; px[2 * (size_t)i + 1] = ft->_pixel[1];
+            lvl[(size_t)i] = std::max(ft->_level, 0);
+            ang[(size_t)i] = (float)ft->_angle;
+            depth[(size_t)i] = ft->_depth;
+            has[(size_t)i] = ft->_depth > 0 ? 1 : 0;
+        }
+        if (!hip::check(ygz_hip_describe_given_angle(c, slot[f], px.data(), lvl.data(), ang.data(), m), "describe_given_angle")) return 0;
+        if (!hip::check(ygz_hip_set_keypoint_depths(c, slot[f], depth.data(), has.data(), m), "set_keypoint_depths")) return 0;
+    }
+    // 3: one call
+    std::vector<int32_t> last_slot(n), cur_slot(n), status(n), counts(8 * n), inliers(n), match(n * (size_t)cells);
+    std::vector<double> T_init(7 * n), T_rel(7 * n);
+    for (size_t p = 0; p < n; ++p) {
+        cur_slot[p] = slot[pairs[p].first]; last_slot[p] = slot[pairs[p].second];
+        (guesses ? (*guesses)[p] : SE3()).to7(&T_init[7 * p]);
+    }
+    ygz_svo_params prm;
+    ygz_hip_default_svo_params(&prm);
+    prm.baseline = _options._baseline; prm.th = _options._th; prm.th_dist = _options._th_dist;
+    prm.check_orientation = _options._check_orientation ? 1 : 0; prm.min_matches = _options._min_matches;
+    if (!hip::check(ygz_hip_stereo_odometry_slots(c, (int)n, last_slot.data(), cur_slot.data(), T_init.data(), nullptr, &prm, T_rel.data(),
+                                                  status.data(), counts.data(), match.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                                  nullptr, nullptr, nullptr, nullptr, inliers.data(), nullptr, nullptr, nullptr, nullptr, nullptr,
+                                                  nullptr), "stereo_odometry_slots"))
+        return 0;
+    // 4: the poses, in pair order
+    int written = 0;
+    if (results) results->resize(n);
+    for (size_t p = 0; p < n; ++p) {
+        Frame *current = pairs[p].first, *last = pairs[p].second;
+        const SE3 T = SE3::from7(&T_rel[7 * p]);
+        const bool ok = status[p] == 0 && inliers[p] >= _options._min_tracked;
+        if (ok) { current->_TCW = T * last->_TCW; ++written; }
+        if (!results) continue;
+        Result &r = (*results)[p];
+        r.status = status[p]; r.matches = counts[8 * p + 3]; r.inliers = inliers[p]; r.retried = counts[8 * p + 7];
+        r.pose_written = ok; r.T_rel = T;
+        r.match.assign(match.begin() + (long)(p * (size_t)cells), match.begin() + (long)(p * (size_t)cells + last->_features.size()));
+    }
+    return written;
+}
+
+bool StereoOdometry::Track(Frame *current, Frame *last, const SE3 &guess, Result *result)
+{
+    const std::vector<std::pair<Frame *, Frame *>> pairs(1, std::make_pair(current, last));
+    const std::vector<SE3> guesses(1, guess);
+    std::vector<Result> res;
+    const int written = TrackPairs(pairs, &guesses, &res);
+    if (result) *result = res.empty() ? Result() : res[0];
+    return written == 1;
+}
+
+}  // namespace ygz
