@@ -75,7 +75,9 @@ extern "C" {
  * Still 6: the stereo tracking search added (ygz_strack_params, ygz_strack_points, ygz_strack_problem, ygz_hip_default_strack_params,
  * ygz_hip_stereo_track_search) -- no existing argument list changed.
  * Still 6: stereo odometry on resident slots added (ygz_svo_params, ygz_hip_default_svo_params, ygz_hip_stereo_odometry_slots) -- no existing
- * argument list changed. */
+ * argument list changed.
+ * Still 6: stereo local-map tracking on resident slots added (ygz_slm_params, ygz_hip_default_slm_params, ygz_hip_stereo_local_map_slots) --
+ * no existing argument list changed. */
 #define YGZ_HIP_ABI_VERSION 6
 
 typedef struct ygz_hip_ctx ygz_hip_ctx;
@@ -1459,6 +1461,61 @@ int  ygz_hip_stereo_odometry_slots(ygz_hip_ctx *ctx, int n_pairs, const int32_t 
                                    int32_t *n_gated, double *proj, int32_t *rot, uint8_t *outlier, double *chi2, int32_t *inliers,
                                    int32_t *rounds_run, int32_t *round_status, int32_t *round_iterations, double *round_cost_initial,
                                    double *round_cost_final, double *round_lambda);
+
+/* ---- stereo local-map tracking on resident slots -- nothing in the reference; ORB-SLAM2's TrackLocalMap (SearchByProjection(F, vpMapPoints,
+ * th) and the pose optimisation on the frame's associations) for any number of resident frames in one call.  The result is the composition of
+ * two frozen specifications, tests/strack_ref.c in mode LOCAL and tests/popt_ref.c, joined by four formulas (DESIGN.md section 28;
+ * tests/slm_ref.py restates it), and every output is bit-identical to that composition.  The point sets (pw, pt_desc, pt_dmax, pt_normal of
+ * ygz_strack_points; pt_level and pt_angle are not read) are shared between frames and go up once.  Per frame f, K = the context's float
+ * intrinsics as doubles, bf = fx baseline formed once, T[f] = qx qy qz qw tx ty tz the entry pose from world to camera:
+ *   keypoints: those of slot[f]; kp_ur[j] = u_j - bf / depth_j when kp_has_mp[j] != 0 and kp_depth[j] > 0 (a NaN does not count), else -1
+ *   (negative: a mono keypoint);
+ *   prior: prior[f][j] = i >= 0 says keypoint j already holds point i of set[f] (what a motion-model stage left on the frame), -1 free, a NULL
+ *   array all free; kp_taken[j] = (prior[j] >= 0), pt_skip[i] = 1 for every i the prior names; two keypoints may name one point;
+ *   search and claim walk of ygz_hip_stereo_track_search in mode LOCAL with th, r_near, r_wide, cos_near, ratio, th_dist and the entry pose;
+ *   no rotation histogram, no retry;
+ *   edges in KEYPOINT order: keypoint j with i = prior[j] >= 0, or else the point that claimed j, gives pw_i; kx_j, ky_j, kp_ur[j];
+ *   kp_level[j]; kind 2 when kp_ur[j] >= 0, else 1 -- the order in which ygz::PoseOptimizer builds its edges from a frame's features;
+ *   pose: with fewer than min_edges edges status = 1, the optimiser is given no edge, so the frame is FAILED in round 0 and T_out[f] is T[f]
+ *   bitwise; otherwise ygz_hip_optimize_pose_stereo from T[f] with params.pose (its baseline is the call's).
+ * The same slot may appear in several frame entries (two hypotheses of one frame); a set of 0 points is allowed: nothing is searched and the
+ * frame's edges are its prior.  The host reads no count before the launches.  One packed upload, five launches (k_slm_gather,
+ * k_strack_search, k_slm_resolve, k_pose_opt, k_slm_scatter), one copy back, one wait.
+ * sizeof: ygz_slm_params 112. */
+#define YGZ_SLM_MAX_FRAMES 1024
+#define YGZ_SLM_MAX_SETS   64
+#define YGZ_SLM_MAX_PAIRS  4194304        /* per call: the sum over the frames of their set's n_pt */
+typedef struct {
+    double  baseline;                     /* 0.1: metres between the rig's cameras, > 0 */
+    double  th;                           /* 1.0: the window is th f 2^pred pixels, > 0 */
+    double  ratio;                        /* 0.8: the best / second-best rule, > 0 */
+    double  r_near, r_wide;               /* 2.5, 4.0: the radius factors, > 0 */
+    double  cos_near;                     /* 0.998: the viewing cosine above which r_near applies */
+    int32_t th_dist;                      /* 100: the largest Hamming distance of a match, 0 .. 256 */
+    int32_t min_edges;                    /* 3: a frame with fewer edges is not optimised (status 1); >= 0 */
+    ygz_pose_opt_params pose;             /* ygz_hip_default_pose_opt_params; its baseline is ignored: the call's is used */
+} ygz_slm_params;
+void ygz_hip_default_slm_params(ygz_slm_params *p);
+/* slot, set [n_frames]; T [n_frames][7]; prior [n_frames][cells] with cells = ygz_hip_max_keypoints, or NULL; params NULL: defaults.
+ * Outputs, any of them may be NULL except T_out: T_out [n][7]; status [n] (0 optimised, 1 too few edges); counts [n][8] = keypoints,
+ * keypoints with a right column, prior edges, points, points searched, overflowed, new matches, edges; kp_point [n][cells] the point each
+ * keypoint ends with (-1 without one and past the last keypoint); outlier [n][cells] (0 where there is no edge) and chi2 [n][cells] (-1.0
+ * there) of the pose optimiser in keypoint order; inliers, rounds_run [n] and round_status, round_iterations, round_cost_initial,
+ * round_cost_final, round_lambda [n][8]; match, dist, level, reason, outcome, n_cand, n_gated [N] and proj [N][3] as
+ * ygz_hip_stereo_track_search defines them, concatenated in frame order, frame f contributing the n_pt entries of its set.  Checked in this
+ * order, all before the device is touched: YGZ_E_INVALID for a null sets, slot, set, T or T_out, n_frames < 1 or n_sets < 1; YGZ_E_CAPACITY
+ * above YGZ_SLM_MAX_FRAMES or YGZ_SLM_MAX_SETS; YGZ_E_INVALID for a non-finite parameter, baseline, th, ratio, r_near or r_wide <= 0, th_dist
+ * outside [0, 256], min_edges < 0, the rules of ygz_hip_optimize_pose_stereo for params.pose, a set's n_pt < 0 or a null pw, pt_desc, pt_dmax
+ * or pt_normal of a set with points, a negative slot, a set index out of range; YGZ_E_CAPACITY for more than YGZ_SLM_MAX_PAIRS pairs;
+ * YGZ_E_INVALID for a non-finite T, point, dmax or normal; last, YGZ_E_INVALID for a null context or a slot past the context's frames,
+ * YGZ_E_CAPACITY for a context of more than 32768 cells, YGZ_E_INVALID for a prior entry below -1 or not below its set's n_pt, YGZ_E_STATE
+ * for a slot without keypoints (no pyramid was ever built for it) or a context whose keypoint depths were never written. */
+int  ygz_hip_stereo_local_map_slots(ygz_hip_ctx *ctx, int n_sets, const ygz_strack_points *sets, int n_frames, const int32_t *slot,
+                                    const int32_t *set, const double *T, const int32_t *prior, const ygz_slm_params *params, double *T_out,
+                                    int32_t *status, int32_t *counts, int32_t *kp_point, uint8_t *outlier, double *chi2, int32_t *inliers,
+                                    int32_t *rounds_run, int32_t *round_status, int32_t *round_iterations, double *round_cost_initial,
+                                    double *round_cost_final, double *round_lambda, int32_t *match, int32_t *dist, int32_t *level,
+                                    int32_t *reason, int32_t *outcome, int32_t *n_cand, int32_t *n_gated, double *proj);
 
 #ifdef __cplusplus
 }

@@ -631,6 +631,20 @@ def svo_argtypes(lib):
                                                   ip, ip, ip, ip, dp, dp, dp]
 
 
+class SlmParams(C.Structure):
+    """ygz_slm_params (include/ygz_hip.h)"""
+    _fields_ = [("baseline", C.c_double), ("th", C.c_double), ("ratio", C.c_double), ("r_near", C.c_double), ("r_wide", C.c_double),
+                ("cos_near", C.c_double), ("th_dist", C.c_int32), ("min_edges", C.c_int32), ("pose", PoseOptParams)]
+
+
+def slm_argtypes(lib):
+    ip, dp, bp, pp = C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.POINTER(SlmParams)
+    lib.ygz_hip_default_slm_params.argtypes = [pp]
+    lib.ygz_hip_default_slm_params.restype = None
+    lib.ygz_hip_stereo_local_map_slots.argtypes = [C.c_void_p, C.c_int, C.POINTER(StrackPoints), C.c_int, ip, ip, dp, ip, pp, dp, ip, ip, ip, bp, dp,
+                                                   ip, ip, ip, ip, dp, dp, dp, ip, ip, ip, ip, ip, ip, ip, dp]
+
+
 # every symbol include/ygz_hip.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
     "ygz_hip_default_params", "ygz_hip_create", "ygz_hip_destroy", "ygz_hip_synchronize", "ygz_hip_join", "ygz_hip_set_overlap", "ygz_hip_error_string",
@@ -671,6 +685,7 @@ ABI_SYMBOLS = [
     "ygz_hip_default_lfuse_params", "ygz_hip_local_fuse_search",
     "ygz_hip_default_strack_params", "ygz_hip_stereo_track_search",
     "ygz_hip_default_svo_params", "ygz_hip_stereo_odometry_slots",
+    "ygz_hip_default_slm_params", "ygz_hip_stereo_local_map_slots",
 ]
 INIT_SYMBOLS = ["ygz_hip_default_init_params", "ygz_hip_initialize", "ygz_hip_init_sample_sets", "ygz_hip_init_hypotheses", "ygz_hip_init_reconstruct"]
 INIT_NONE, INIT_H, INIT_F = 0, 1, 2
@@ -729,6 +744,11 @@ SVO_SYMBOLS = ["ygz_hip_default_svo_params", "ygz_hip_stereo_odometry_slots"]
 SVO_MAX_PAIRS = 1024
 SVO_INT_OUTPUTS = ("match", "dist", "level", "reason", "outcome", "n_cand", "n_gated")
 SVO_COUNTS = ("last_keypoints", "with_depth", "cur_keypoints", "matches", "searched", "overflowed", "removed_by_orientation", "retried")
+
+SLM_SYMBOLS = ["ygz_hip_default_slm_params", "ygz_hip_stereo_local_map_slots"]
+SLM_MAX_FRAMES, SLM_MAX_SETS, SLM_MAX_PAIRS = 1024, 64, 4194304
+SLM_INT_OUTPUTS = ("match", "dist", "level", "reason", "outcome", "n_cand", "n_gated")
+SLM_COUNTS = ("keypoints", "with_right_column", "prior_edges", "points", "searched", "overflowed", "new_matches", "edges")
 
 POPT_SYMBOLS = ["ygz_hip_default_pose_opt_params", "ygz_hip_optimize_pose_stereo"]
 POPT_FAILED, POPT_CONVERGED, POPT_MAX_ITERATIONS, POPT_STALLED = range(4)
@@ -1290,6 +1310,76 @@ class HipContext:
             self._ctx, n, _p(ls, C.c_int32), _p(cs, C.c_int32), None if T0 is None else _p(T0, C.c_double),
             None if dr is None else _p(dr, C.c_int32), C.byref(p), f("T_rel"), f("status"), *[f(k) for k in names]), "stereo_odometry_slots")
         return {k: v[:n] for k, v in o.items()}
+
+    # ---- stereo local-map tracking on resident slots
+    def default_slm_params(self, **fields):
+        """ygz_hip_default_slm_params, with the given fields overwritten; a field of the embedded ygz_pose_opt_params is given as pose_<name>"""
+        slm_argtypes(self.lib)
+        p = SlmParams()
+        self.lib.ygz_hip_default_slm_params(C.byref(p))
+        for k, v in fields.items():
+            tgt, name = (p.pose, k[5:]) if k.startswith("pose_") else (p, k)
+            getattr(tgt, name)              # AttributeError for a field the struct does not have
+            setattr(tgt, name, v)
+        return p
+
+    def stereo_local_map_slots(self, sets, slots, set_index, T, prior=None, params=None, outputs=True, **fields):
+        """local-map tracking for the resident frames (slots[f], sets[set_index[f]]) in one call: the LOCAL search with the right-column gate,
+        the claim walk and the u, v, uR pose optimisation on the prior and the new associations.  sets: dicts of pw [n, 3], pt_desc [n, 32],
+        pt_dmax [n], pt_normal [n, 3] (an empty dict: a set of 0 points); T [n, 7]; prior [n, cells] (None: all free).  Dict of T_out [n, 7],
+        status [n], counts [n, 8], kp_point, outlier, chi2 [n, cells], inliers, rounds_run [n], round_status, lm_iterations, cost_initial,
+        cost_final, lambda [n, 8], match, dist, level, reason, outcome, n_cand, n_gated [N], proj [N, 3] concatenated in frame order and
+        offsets [n + 1]; outputs=False passes NULL for everything but T_out and status."""
+        p = params if params is not None else self.default_slm_params(**fields)
+        slm_argtypes(self.lib)
+        keep = []
+
+        def put(d, name, t, ct, n):
+            a = d.get(name)
+            if a is None:
+                return C.POINTER(ct)()
+            a = np.ascontiguousarray(a, t).reshape(-1)
+            if len(a) != n:
+                raise ValueError("%s has the wrong length" % name)
+            keep.append(a)
+            return _p(a, ct)
+        sa = (StrackPoints * max(len(sets), 1))()
+        for s, d in enumerate(sets):
+            n = len(np.asarray(d["pt_desc"]).reshape(-1)) // 32 if d.get("pt_desc") is not None else 0
+            sa[s].pw, sa[s].pt_desc = put(d, "pw", np.float64, C.c_double, 3 * n), put(d, "pt_desc", np.uint8, C.c_uint8, 32 * n)
+            sa[s].pt_dmax, sa[s].pt_normal = put(d, "pt_dmax", np.float64, C.c_double, n), put(d, "pt_normal", np.float64, C.c_double, 3 * n)
+            sa[s].n_pt = n
+        sl, st = np.ascontiguousarray(slots, np.int32).reshape(-1), np.ascontiguousarray(set_index, np.int32).reshape(-1)
+        if len(sl) != len(st):
+            raise ValueError("slots and set_index differ in length")
+        n, c, R = len(sl), self.cells, POPT_MAX_ROUNDS
+        T0 = np.ascontiguousarray(T, np.float64).reshape(n, 7)
+        pr = None if prior is None else np.ascontiguousarray(prior, np.int32).reshape(n, c)
+        off = [0]
+        for f in range(n):
+            off.append(off[-1] + (int(sa[int(st[f])].n_pt) if 0 <= st[f] < len(sets) else 0))
+        N, m = off[-1], max(n, 1)
+        o = dict(T_out=np.zeros((m, 7)), status=np.full(m, -7, np.int32))
+        names = ("counts", "kp_point", "outlier", "chi2", "inliers", "rounds_run", "round_status", "lm_iterations", "cost_initial", "cost_final",
+                 "lambda") + SLM_INT_OUTPUTS + ("proj",)
+        if outputs:
+            o.update(counts=np.full((m, 8), -7, np.int32), kp_point=np.full((m, c), -7, np.int32), outlier=np.full((m, c), 7, np.uint8),
+                     chi2=np.zeros((m, c)), inliers=np.full(m, -7, np.int32), rounds_run=np.full(m, -7, np.int32),
+                     round_status=np.full((m, R), -7, np.int32), lm_iterations=np.full((m, R), -7, np.int32), cost_initial=np.zeros((m, R)),
+                     cost_final=np.zeros((m, R)), proj=np.zeros((max(N, 1), 3)))
+            o["lambda"] = np.zeros((m, R))
+            for k in SLM_INT_OUTPUTS:
+                o[k] = np.full(max(N, 1), -7, np.int32)
+        types = {np.dtype(np.int32): C.c_int32, np.dtype(np.float64): C.c_double, np.dtype(np.uint8): C.c_uint8}
+        f_ = lambda k: _p(o[k], types[o[k].dtype]) if k in o else None
+        self._chk(self.lib.ygz_hip_stereo_local_map_slots(
+            self._ctx, len(sets), sa, n, _p(sl, C.c_int32), _p(st, C.c_int32), _p(T0, C.c_double), None if pr is None else _p(pr, C.c_int32),
+            C.byref(p), f_("T_out"), f_("status"), *[f_(k) for k in names]), "stereo_local_map_slots")
+        del keep
+        per_point = SLM_INT_OUTPUTS + ("proj",)
+        out = {k: (v[:N] if k in per_point else v[:n]) for k, v in o.items()}
+        out["offsets"] = np.array(off, np.int64)
+        return out
 
     # ---- keyframe store / device-built BA windows (configs[4])
     def stream_wait(self, signaler):

@@ -23,6 +23,7 @@
 #include <math.h>
 #include <string.h>
 #pragma clang fp contract(off)
+#include "ur_dev.h"                     // the right column of a resident keypoint: slm.hip gathers the same way
 
 #define SV_LANES      256
 #define SV_MAX_CELLS  32768              // the taken bitmap of a pair: 4 KiB of LDS
@@ -58,13 +59,13 @@ __global__ __launch_bounds__(SV_LANES) void k_svo_gather(SvoDev A)
     if (i < sv_count(A, s)) {
         const size_t g = (size_t)s * A.cells + i, o = (size_t)d * A.cells + i;
         const double u = A.kp_px[2 * g], v = A.kp_px[2 * g + 1], z = A.kp_depth[g];
-        const bool has = A.kp_has_mp[g] != 0 && z > 0;                 // a NaN depth compares false
+        const bool has = ygz_kp_has_depth(A.kp_has_mp[g], z);          // a NaN depth compares false
         double x = 0, y = 0, zz = 0, ur = -1.0;
         if (has) {
             x = ((u - A.K4[2]) / A.K4[0]) * z;
             y = ((v - A.K4[3]) / A.K4[1]) * z;
             zz = z;
-            ur = u - A.bf / z;
+            ur = ygz_kp_right_column(u, z, A.bf);
         }
         A.g_pw[3 * o] = x; A.g_pw[3 * o + 1] = y; A.g_pw[3 * o + 2] = zz;
         A.g_ur[o] = ur;
