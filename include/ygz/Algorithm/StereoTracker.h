@@ -10,7 +10,7 @@
 //   TrackLocalMap         Tracking::SearchLocalPoints + TrackLocalMap: the visible / found counters that StereoMapper::MapPointCulling
 //                         reads, ORBmatcher::SearchByProjection(F, vpMapPoints, th), PoseOptimizer.
 // After it a caller can run rectify -> stereo match -> track -> pose optimise -> keyframe -> create / fuse / BA / cull.  Not here:
-// UpdateLastFrame's temporary points, NeedNewKeyFrame, TrackReferenceKeyFrame (Matcher::SearchByBoW + PoseOptimizer serve).
+// UpdateLastFrame's temporary points, NeedNewKeyFrame, TrackReferenceKeyFrame (StereoRefTracker, ygz/Algorithm/StereoRefTracker.h, serves).
 //
 // Error conventions of the other surfaces: a failed call logs and returns 0, only a missing device throws.  One thread at a time.  Feature,
 // Frame and MapPoint keep their layouts; every order goes by index, list position or id, never by address.

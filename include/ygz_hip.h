@@ -77,7 +77,9 @@ extern "C" {
  * Still 6: stereo odometry on resident slots added (ygz_svo_params, ygz_hip_default_svo_params, ygz_hip_stereo_odometry_slots) -- no existing
  * argument list changed.
  * Still 6: stereo local-map tracking on resident slots added (ygz_slm_params, ygz_hip_default_slm_params, ygz_hip_stereo_local_map_slots) --
- * no existing argument list changed. */
+ * no existing argument list changed.
+ * Still 6: stereo reference-keyframe tracking on resident slots added (ygz_srk_params, ygz_hip_default_srk_params,
+ * ygz_hip_stereo_ref_keyframe_slots) -- no existing argument list changed. */
 #define YGZ_HIP_ABI_VERSION 6
 
 typedef struct ygz_hip_ctx ygz_hip_ctx;
@@ -1516,6 +1518,68 @@ int  ygz_hip_stereo_local_map_slots(ygz_hip_ctx *ctx, int n_sets, const ygz_stra
                                     int32_t *rounds_run, int32_t *round_status, int32_t *round_iterations, double *round_cost_initial,
                                     double *round_cost_final, double *round_lambda, int32_t *match, int32_t *dist, int32_t *level,
                                     int32_t *reason, int32_t *outcome, int32_t *n_cand, int32_t *n_gated, double *proj);
+
+/* ---- stereo reference-keyframe tracking on resident slots -- nothing in the reference; ORB-SLAM2's TrackReferenceKeyFrame (SearchByBoW between
+ * the reference keyframe and the frame, then the pose optimisation on the associations) for any number of resident frames in one call.  The
+ * result is the composition of frozen specifications, yo_search_by_bow and yo_bow_orientation of oracle/bow.c and tests/popt_ref.c, joined by
+ * the formulas below (tests/srk_ref.py restates it), and every output is bit-identical to that composition.  Only n_pt
+ * and pw of a point set are read, so the same set objects serve ygz_hip_stereo_local_map_slots afterwards; the sets are shared and go up once.
+ * Keyframe k is slot kf_slot[k] with set kf_set[k]; kf_point[k][i] = p >= 0 says keypoint i of that slot carries point p of the set, -1 none;
+ * two keypoints may name one point.  Frame f is slot[f], tracked against keyframe kf[f] from the entry pose T[f] (world to camera, qx qy qz qw
+ * tx ty tz; ORB-SLAM2 uses the last frame's pose); several frames may name one keyframe and a slot may appear in several frame entries.
+ *   1 BoW: ygz_hip_compute_bow with params.levelsup for every distinct slot the call names, frames and keyframes, once each -- the call needs no
+ *     earlier ygz_hip_compute_bow and overwrites what one left;
+ *   2 right columns: kp_ur[j] = u_j - bf / depth_j when kp_has_mp[j] != 0 and kp_depth[j] > 0 (a NaN does not count), else -1;
+ *   3 search: yo_search_by_bow with the keyframe's keypoints as frame 1, node1[i] replaced by -1 where kf_point[i] < 0, the frame's keypoints
+ *     as frame 2: best < th_low and (float)best < knn_ratio (float)second;
+ *   4 claim: a frame keypoint j named by several keyframe features goes to the smallest i; the others get match -1, outcome 2;
+ *   5 orientation (check_orientation != 0) over the claimed matches: the histogram and the three maxima of yo_bow_orientation (bin =
+ *     round(rot / 30), the reference's factor) on the slots' float angles; a claimed match in another bin gets match -1, outcome 4, and j ends
+ *     without a point;
+ *   6 edges in keypoint order of the frame, j ascending: pw of kf_point[i] for the i that holds j; kx_j, ky_j, kp_ur[j]; kp_level[j]; kind 2
+ *     when kp_ur[j] >= 0, else 1;
+ *   7 pose: with fewer than min_matches edges status = 1, the optimiser is given no edge and T_out[f] is T[f] bitwise; otherwise
+ *     ygz_hip_optimize_pose_stereo from T[f] with params.pose (its baseline is the call's); status = 2 when the inliers are fewer than
+ *     min_inliers (the pose is still returned).
+ * The host reads no count before the launches.  One packed upload, seven launches (k_srk_gather, k_bow_transform, k_srk_gather for the masked
+ * node rows, k_bow_match<0>, k_srk_resolve, k_pose_opt, k_srk_scatter), one copy back, one wait.
+ * sizeof: ygz_srk_params 88. */
+#define YGZ_SRK_MAX_FRAMES    1024
+#define YGZ_SRK_MAX_KEYFRAMES 256
+#define YGZ_SRK_MAX_SETS      64
+typedef struct {
+    double  baseline;                     /* 0.1: metres between the rig's cameras, > 0 */
+    int32_t th_low;                       /* 50: a match's Hamming distance is below it, 0 .. 256 */
+    float   knn_ratio;                    /* 0.7: best against second best of the same node, > 0 */
+    int32_t levelsup;                     /* 4: the FeatureVector's node is this many levels above the leaves, >= 0 */
+    int32_t check_orientation;            /* 1: the rotation histogram removes matches */
+    int32_t min_matches;                  /* 15: a frame with fewer edges is not optimised (status 1); >= 0 */
+    int32_t min_inliers;                  /* 10: fewer inliers after the optimisation: status 2; >= 0 */
+    ygz_pose_opt_params pose;             /* ygz_hip_default_pose_opt_params; its baseline is ignored: the call's is used */
+} ygz_srk_params;
+void ygz_hip_default_srk_params(ygz_srk_params *p);
+/* sets [n_sets]; kf_slot, kf_set [n_keyframes]; kf_point [n_keyframes][cells] with cells = ygz_hip_max_keypoints; slot, kf [n_frames];
+ * T [n_frames][7]; params NULL: defaults.  Outputs, any of them may be NULL except T_out: T_out [n][7]; status [n] (0 optimised, 1 too few
+ * edges, 2 too few inliers); counts [n][8] = keyframe keypoints, those with a point, frame keypoints, those with a right column, search
+ * matches, lost to the claim, removed by orientation, edges; kp_point [n][cells] the set index behind every frame keypoint after step 5 (-1
+ * without one and past the last keypoint); prior [n][cells] = kp_point with the optimiser's outliers set to -1, in the layout and index space
+ * ygz_hip_stereo_local_map_slots takes; outlier [n][cells] (0 where there is no edge) and chi2 [n][cells] (-1.0 there) in keypoint order;
+ * inliers, rounds_run [n] and round_status, round_iterations, round_cost_initial, round_cost_final, round_lambda [n][8]; by keyframe keypoint,
+ * match12 [n][cells] (the frame keypoint or -1) and outcome [n][cells] (0 matched, 1 no match, 2 lost the claim, 4 orientation, -1 no point
+ * or past the last keypoint); rot [n][33] the histogram and its three maxima (zeros and -1 without the check).  Checked in this order, all
+ * before the device is touched: YGZ_E_INVALID for a null sets, kf_slot, kf_set, kf_point, slot, kf, T or T_out, n_sets, n_keyframes or
+ * n_frames < 1; YGZ_E_CAPACITY above YGZ_SRK_MAX_SETS, YGZ_SRK_MAX_KEYFRAMES or YGZ_SRK_MAX_FRAMES; YGZ_E_INVALID for a non-finite baseline
+ * or knn_ratio, baseline <= 0, th_low outside [0, 256], knn_ratio <= 0, levelsup < 0, min_matches or min_inliers < 0, the rules of
+ * ygz_hip_optimize_pose_stereo for params.pose; a set's n_pt < 0 or a null pw of a set with points, a negative slot, a set or keyframe index
+ * out of range; a non-finite T or pw; last, YGZ_E_INVALID for a null context or a slot past the context's frames, YGZ_E_CAPACITY for a context
+ * of more than 32768 cells, YGZ_E_INVALID for a kf_point entry below -1 or not below its set's n_pt, YGZ_E_STATE for a context without a
+ * vocabulary, a slot without keypoints (no pyramid was ever built for it) or a context whose keypoint depths were never written. */
+int  ygz_hip_stereo_ref_keyframe_slots(ygz_hip_ctx *ctx, int n_sets, const ygz_strack_points *sets, int n_keyframes, const int32_t *kf_slot,
+                                       const int32_t *kf_set, const int32_t *kf_point, int n_frames, const int32_t *slot, const int32_t *kf,
+                                       const double *T, const ygz_srk_params *params, double *T_out, int32_t *status, int32_t *counts,
+                                       int32_t *kp_point, int32_t *prior, uint8_t *outlier, double *chi2, int32_t *inliers, int32_t *rounds_run,
+                                       int32_t *round_status, int32_t *round_iterations, double *round_cost_initial, double *round_cost_final,
+                                       double *round_lambda, int32_t *match12, int32_t *outcome, int32_t *rot);
 
 #ifdef __cplusplus
 }

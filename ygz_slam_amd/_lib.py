@@ -645,6 +645,20 @@ def slm_argtypes(lib):
                                                    ip, ip, ip, ip, dp, dp, dp, ip, ip, ip, ip, ip, ip, ip, dp]
 
 
+class SrkParams(C.Structure):
+    """ygz_srk_params (include/ygz_hip.h)"""
+    _fields_ = [("baseline", C.c_double), ("th_low", C.c_int32), ("knn_ratio", C.c_float), ("levelsup", C.c_int32),
+                ("check_orientation", C.c_int32), ("min_matches", C.c_int32), ("min_inliers", C.c_int32), ("pose", PoseOptParams)]
+
+
+def srk_argtypes(lib):
+    ip, dp, bp, pp = C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.POINTER(SrkParams)
+    lib.ygz_hip_default_srk_params.argtypes = [pp]
+    lib.ygz_hip_default_srk_params.restype = None
+    lib.ygz_hip_stereo_ref_keyframe_slots.argtypes = [C.c_void_p, C.c_int, C.POINTER(StrackPoints), C.c_int, ip, ip, ip, C.c_int, ip, ip, dp, pp,
+                                                      dp, ip, ip, ip, ip, bp, dp, ip, ip, ip, ip, dp, dp, dp, ip, ip, ip]
+
+
 # every symbol include/ygz_hip.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
     "ygz_hip_default_params", "ygz_hip_create", "ygz_hip_destroy", "ygz_hip_synchronize", "ygz_hip_join", "ygz_hip_set_overlap", "ygz_hip_error_string",
@@ -686,6 +700,7 @@ ABI_SYMBOLS = [
     "ygz_hip_default_strack_params", "ygz_hip_stereo_track_search",
     "ygz_hip_default_svo_params", "ygz_hip_stereo_odometry_slots",
     "ygz_hip_default_slm_params", "ygz_hip_stereo_local_map_slots",
+    "ygz_hip_default_srk_params", "ygz_hip_stereo_ref_keyframe_slots",
 ]
 INIT_SYMBOLS = ["ygz_hip_default_init_params", "ygz_hip_initialize", "ygz_hip_init_sample_sets", "ygz_hip_init_hypotheses", "ygz_hip_init_reconstruct"]
 INIT_NONE, INIT_H, INIT_F = 0, 1, 2
@@ -749,6 +764,11 @@ SLM_SYMBOLS = ["ygz_hip_default_slm_params", "ygz_hip_stereo_local_map_slots"]
 SLM_MAX_FRAMES, SLM_MAX_SETS, SLM_MAX_PAIRS = 1024, 64, 4194304
 SLM_INT_OUTPUTS = ("match", "dist", "level", "reason", "outcome", "n_cand", "n_gated")
 SLM_COUNTS = ("keypoints", "with_right_column", "prior_edges", "points", "searched", "overflowed", "new_matches", "edges")
+
+SRK_SYMBOLS = ["ygz_hip_default_srk_params", "ygz_hip_stereo_ref_keyframe_slots"]
+SRK_MAX_FRAMES, SRK_MAX_KEYFRAMES, SRK_MAX_SETS = 1024, 256, 64
+SRK_COUNTS = ("keyframe_keypoints", "with_point", "keypoints", "with_right_column", "search_matches", "lost_claim", "removed_by_orientation", "edges")
+SRK_MATCHED, SRK_NO_MATCH, SRK_LOST_CLAIM, SRK_ORIENTATION = 0, 1, 2, 4
 
 POPT_SYMBOLS = ["ygz_hip_default_pose_opt_params", "ygz_hip_optimize_pose_stereo"]
 POPT_FAILED, POPT_CONVERGED, POPT_MAX_ITERATIONS, POPT_STALLED = range(4)
@@ -1380,6 +1400,60 @@ class HipContext:
         out = {k: (v[:N] if k in per_point else v[:n]) for k, v in o.items()}
         out["offsets"] = np.array(off, np.int64)
         return out
+
+    # ---- stereo reference-keyframe tracking on resident slots
+    def default_srk_params(self, **fields):
+        """ygz_hip_default_srk_params, with the given fields overwritten; a field of the embedded ygz_pose_opt_params is given as pose_<name>"""
+        srk_argtypes(self.lib)
+        p = SrkParams()
+        self.lib.ygz_hip_default_srk_params(C.byref(p))
+        for k, v in fields.items():
+            tgt, name = (p.pose, k[5:]) if k.startswith("pose_") else (p, k)
+            getattr(tgt, name)              # AttributeError for a field the struct does not have
+            setattr(tgt, name, v)
+        return p
+
+    def stereo_ref_keyframe_slots(self, sets, kf_slot, kf_set, kf_point, slots, kf, T, params=None, outputs=True, **fields):
+        """reference-keyframe tracking for the resident frames slots[f] against keyframe kf[f] (slot kf_slot[k], set sets[kf_set[k]], kf_point
+        [n_kf, cells] the set index behind every keyframe keypoint or -1) in one call: BoW of every named slot, SearchByBoW, the claim, the
+        rotation histogram and the u, v, uR pose optimisation from T [n, 7].  sets: dicts with pw [n_pt, 3] (an empty dict: a set of 0
+        points; the other fields of a ygz_strack_points are not read).  Dict of T_out [n, 7], status [n], counts [n, 8], kp_point, prior,
+        outlier, chi2 [n, cells], inliers, rounds_run [n], round_status, lm_iterations, cost_initial, cost_final, lambda [n, 8], match12,
+        outcome [n, cells], rot [n, 33]; outputs=False passes NULL for everything but T_out, status and prior."""
+        p = params if params is not None else self.default_srk_params(**fields)
+        srk_argtypes(self.lib)
+        keep = []
+        sa = (StrackPoints * max(len(sets), 1))()
+        for s, d in enumerate(sets):
+            a = d.get("pw")
+            a = np.zeros((0, 3)) if a is None else np.ascontiguousarray(a, np.float64).reshape(-1, 3)
+            keep.append(a)
+            sa[s].pw, sa[s].n_pt = (_p(a, C.c_double) if len(a) else C.POINTER(C.c_double)()), len(a)
+        ks, kt = np.ascontiguousarray(kf_slot, np.int32).reshape(-1), np.ascontiguousarray(kf_set, np.int32).reshape(-1)
+        sl, kk = np.ascontiguousarray(slots, np.int32).reshape(-1), np.ascontiguousarray(kf, np.int32).reshape(-1)
+        if len(ks) != len(kt) or len(sl) != len(kk):
+            raise ValueError("kf_slot and kf_set, or slots and kf, differ in length")
+        n, c, R = len(sl), self.cells, POPT_MAX_ROUNDS
+        kp = np.ascontiguousarray(kf_point, np.int32).reshape(len(ks), c)
+        T0 = np.ascontiguousarray(T, np.float64).reshape(n, 7)
+        m = max(n, 1)
+        o = dict(T_out=np.zeros((m, 7)), status=np.full(m, -7, np.int32), prior=np.full((m, c), -7, np.int32))
+        names = ("counts", "kp_point", "prior", "outlier", "chi2", "inliers", "rounds_run", "round_status", "lm_iterations", "cost_initial",
+                 "cost_final", "lambda", "match12", "outcome", "rot")
+        if outputs:
+            o.update(counts=np.full((m, 8), -7, np.int32), kp_point=np.full((m, c), -7, np.int32), outlier=np.full((m, c), 7, np.uint8),
+                     chi2=np.zeros((m, c)), inliers=np.full(m, -7, np.int32), rounds_run=np.full(m, -7, np.int32),
+                     round_status=np.full((m, R), -7, np.int32), lm_iterations=np.full((m, R), -7, np.int32), cost_initial=np.zeros((m, R)),
+                     cost_final=np.zeros((m, R)), match12=np.full((m, c), -7, np.int32), outcome=np.full((m, c), -7, np.int32),
+                     rot=np.full((m, 33), -7, np.int32))
+            o["lambda"] = np.zeros((m, R))
+        types = {np.dtype(np.int32): C.c_int32, np.dtype(np.float64): C.c_double, np.dtype(np.uint8): C.c_uint8}
+        f_ = lambda k: _p(o[k], types[o[k].dtype]) if k in o else None
+        self._chk(self.lib.ygz_hip_stereo_ref_keyframe_slots(
+            self._ctx, len(sets), sa, len(ks), _p(ks, C.c_int32), _p(kt, C.c_int32), _p(kp, C.c_int32), n, _p(sl, C.c_int32), _p(kk, C.c_int32),
+            _p(T0, C.c_double), C.byref(p), f_("T_out"), f_("status"), *[f_(k) for k in names]), "stereo_ref_keyframe_slots")
+        del keep
+        return {k: v[:n] for k, v in o.items()}
 
     # ---- keyframe store / device-built BA windows (configs[4])
     def stream_wait(self, signaler):

@@ -8,17 +8,9 @@
 //     search the reference performs by walking two std::map<NodeId, vector<idx>> in lockstep.  Integer work: bit-exact.
 // The vocabulary is DBoW3's binary file (Vocabulary::loadFromBinaryFile layout); the reference does not ship vocab/ORBvoc.bin.
 #include "ygz_internal.h"
+#include "bow_dev.h"
 #include <vector>
 #include <string.h>
-
-struct ygz_hip_ctx::Vocab {
-    int k = 0, L = 0, n_nodes = 0, n_words = 0;
-    void *blob = nullptr;
-    int32_t *child_off, *child, *word_id; uint32_t *desc; double *weight;
-    int32_t *kp_word = nullptr, *kp_node = nullptr; double *kp_weight = nullptr;       // [F][cells] per resident keypoint
-};
-
-struct VocDev { int L; const int32_t *child_off, *child, *word_id; const uint32_t *desc; const double *weight; };
 
 __device__ __forceinline__ int bow_dist(const uint32_t a[8], const uint32_t *__restrict__ b)
 {
@@ -60,8 +52,6 @@ __global__ __launch_bounds__(256) void k_bow_transform(VocDev V, const uint32_t 
     word[g] = w; weight[g] = wt;
     node[g] = (wt > 0 && w >= 0) ? nid : -1;                 // stopped words stay out of the FeatureVector
 }
-
-struct BowPair { const uint32_t *d1, *d2; const int32_t *n1, *n2; const double *p1, *p2; int c1, c2; double E[9]; };
 
 // MODE 0: SearchByBoW (best + second best, th_low, knn ratio).  MODE 1: SearchForTriangulation (last candidate with
 // dist <= th_low, dist <= best and the epipolar constraint).
@@ -130,6 +120,9 @@ __global__ __launch_bounds__(256) void k_bow_match(const BowPair *__restrict__ p
     match12[(size_t)blockIdx.y * match_stride + i] = m;
     if (m >= 0) atomicAdd(&counts[blockIdx.y], 1);
 }
+// the instantiation bow_dev.h declares
+template __global__ void k_bow_match<0>(const BowPair *__restrict__ pairs, int th_low, float knn_ratio, double eps_dsqr, double fx, double fy,
+                                        double cx, double cy, int32_t *__restrict__ match12, size_t match_stride, int32_t *__restrict__ counts);
 
 extern "C" void ygz_hip_vocab_free(ygz_hip_ctx *ctx)
 {
