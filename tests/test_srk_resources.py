@@ -40,10 +40,16 @@ def test_srk_kernels_do_not_spill():
 def test_kernel_file_keeps_the_constraints():
     hip = open(SRK).read()
     code = re.sub(r"//[^\n]*", "", hip)
-    for word in ["getenv", "hipLaunchCooperativeKernel", "cooperative_groups", "__threadfence", "for (;;)", "fma", "hipStreamSynchronize",
-                 "hipMemcpy", "atomicAdd_system", "atomicCAS", "atomicExch", "atomicOr", "atomicMax"]:
+    words = ["getenv", "hipLaunchCooperativeKernel", "cooperative_groups", "__threadfence", "for (;;)", "fma", "hipStreamSynchronize",
+             "hipMemcpy", "atomicAdd_system", "atomicCAS", "atomicExch", "atomicOr", "atomicMax"]
+    for word in words:
         assert word not in code, word
     assert "while" not in code                                           # every loop is a for over a count known at entry
+    # what the three slot trackers share is in one header, held to the same list: no atomic, no LDS of its own, no unbounded loop
+    dev = re.sub(r"//[^\n]*", "", open(os.path.join(CSRC, "slot_pose_dev.h")).read())
+    for word in words + ["while", "atomic", "__shared__"]:
+        assert word not in dev, word
+    assert '#include "slot_pose_dev.h"' in hip
     # the three reused kernels are declared in the shared headers and defined in their own files: no copy here, and no kernel named after them
     assert '#include "bow_dev.h"' in hip and '#include "popt_dev.h"' in hip and '#include "ur_dev.h"' in hip
     defined = re.findall(r"__global__[^;{]*?void\s+(\w+)\s*\(", code)
@@ -84,7 +90,7 @@ def test_kernel_file_keeps_the_constraints():
     resolve = code[code.index("void k_srk_resolve"):code.index("void k_srk_scatter")]
     assert "has && m >= 0 && m < n2" in resolve and "m < 0 || m >= n2 || holder[m] != i" in resolve and "r < 0 || r >= n2" in resolve
     assert "i >= 0 && i < n1 && A.outcome[kb + i] == 0" in resolve and "p >= 0 && p < n_pt" in resolve
-    gather = code[code.index("void k_srk_gather"):code.index("__device__ __forceinline__ int sr_bin")]
-    assert "atomic" not in gather and "i < sr_count(A, s) && A.kf_point[" in gather
+    gather = code[code.index("void k_srk_gather"):code.index("enum { SR_N_UR")]
+    assert "atomic" not in gather and "i < ygz_slot_count(A.n_kp, s, A.cells) && A.kf_point[" in gather
     # the right column of a resident keypoint is the shared header's
     assert "ygz_kp_right_column(" in code and "bf /" not in code

@@ -36,7 +36,7 @@ def test_strack_kernel_does_not_spill():
 def test_kernel_file_keeps_the_constraints():
     hip = open(os.path.join(ROOT, "ygz_slam_amd", "csrc", "strack.hip")).read()
     code = re.sub(r"//[^\n]*", "", hip)
-    kernel = code[code.index("__global__"):code.index("static bool strack_finite")]
+    kernel = code[code.index("__global__"):code.index("static void strack_resolve")]
     for word in ["getenv", "atomic", "hipLaunchCooperativeKernel", "cooperative_groups", "__threadfence", "while (true)", "fma", "sin(", "cos("]:
         assert word not in code, word
     assert "float" not in kernel                                         # FP64 on the device; the rotation histogram's floats are host code

@@ -38,10 +38,16 @@ def test_svo_kernels_do_not_spill():
 def test_kernel_file_keeps_the_constraints():
     hip = open(SVO).read()
     code = re.sub(r"//[^\n]*", "", hip)
-    for word in ["getenv", "hipLaunchCooperativeKernel", "cooperative_groups", "__threadfence", "while (true)", "while(true)", "for (;;)", "fma",
-                 "hipStreamSynchronize", "hipMemcpy", "atomicAdd_system", "atomicCAS", "atomicExch"]:
+    words = ["getenv", "hipLaunchCooperativeKernel", "cooperative_groups", "__threadfence", "while (true)", "while(true)", "for (;;)", "fma",
+             "hipStreamSynchronize", "hipMemcpy", "atomicAdd_system", "atomicCAS", "atomicExch"]
+    for word in words:
         assert word not in code, word
     assert "while" not in code                                           # every loop is a for over a count known at entry
+    # what the three slot trackers share is in one header, held to the same list: no atomic, no LDS of its own, no unbounded loop
+    dev = re.sub(r"//[^\n]*", "", open(os.path.join(os.path.dirname(SVO), "slot_pose_dev.h")).read())
+    for word in words + ["while", "atomic", "__shared__"]:
+        assert word not in dev, word
+    assert '#include "slot_pose_dev.h"' in hip
     # the two reused kernels are declared in the shared headers and defined in their own files: no copy here, and no kernel named after them
     assert '#include "strack_dev.h"' in hip and '#include "popt_dev.h"' in hip
     defined = re.findall(r"__global__[^;{]*?void\s+(\w+)\s*\(", code)

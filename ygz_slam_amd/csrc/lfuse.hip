@@ -15,6 +15,7 @@
 #include "se3_dev.h"
 #include <math.h>
 #include <string.h>
+#include "pose_block.h"                 // ygz_all_finite
 #pragma clang fp contract(off)
 
 #define LF_LANES     256
@@ -172,12 +173,6 @@ __global__ __launch_bounds__(LF_LANES) void k_lfuse_search(const LfIn *__restric
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------------------
-static bool lfuse_finite(const double *v, size_t n)
-{
-    for (size_t i = 0; i < n; ++i) if (!isfinite(v[i])) return false;
-    return true;
-}
-
 extern "C" {
 
 void ygz_hip_default_lfuse_params(ygz_lfuse_params *p)
@@ -212,15 +207,15 @@ int ygz_hip_local_fuse_search(ygz_hip_ctx *ctx, int n_sets, const ygz_lfuse_poin
     if (params) p = *params; else ygz_hip_default_lfuse_params(&p);
     if (!isfinite(p.th) || !isfinite(p.baseline) || !isfinite(p.chi2_mono) || !isfinite(p.chi2_stereo)) return YGZ_E_INVALID;
     if (!(p.th > 0) || !(p.baseline > 0) || !(p.chi2_mono > 0) || !(p.chi2_stereo > 0) || p.th_dist < 0 || p.th_dist > 256) return YGZ_E_INVALID;
-    if (!lfuse_finite(K4, 4) || !(K4[0] > 0) || !(K4[1] > 0)) return YGZ_E_INVALID;
+    if (!ygz_all_finite(K4, 4) || !(K4[0] > 0) || !(K4[1] > 0)) return YGZ_E_INVALID;
     for (int s = 0; s < n_sets; ++s) {
         const size_t n = (size_t)sets[s].n_pt;
         if (!n) continue;
-        if (!lfuse_finite(sets[s].pw, 3 * n) || !lfuse_finite(sets[s].pt_dmax, n)) return YGZ_E_INVALID;
+        if (!ygz_all_finite(sets[s].pw, 3 * n) || !ygz_all_finite(sets[s].pt_dmax, n)) return YGZ_E_INVALID;
     }
     for (int q = 0; q < n_problems; ++q) {
-        if (!lfuse_finite(problems[q].T, 7)) return YGZ_E_INVALID;
-        if (problems[q].kp_ur && !lfuse_finite(problems[q].kp_ur, (size_t)problems[q].n_kp)) return YGZ_E_INVALID;
+        if (!ygz_all_finite(problems[q].T, 7)) return YGZ_E_INVALID;
+        if (problems[q].kp_ur && !ygz_all_finite(problems[q].kp_ur, (size_t)problems[q].n_kp)) return YGZ_E_INVALID;
     }
     if (!ctx) return YGZ_E_INVALID;
     const int L = ctx->prm.pyramid_levels;

@@ -387,10 +387,7 @@ extern "C" int ygz_hip_optimize_pose_stereo(ygz_hip_ctx *ctx, int n_frames, cons
     // every check before the device is touched; the context last, so that a null context refuses a valid call too
     if (!params || n_frames < 0 || !frame_off) return YGZ_E_INVALID;
     const ygz_pose_opt_params &p = *params;
-    if (!isfinite(p.baseline) || !isfinite(p.chi2_mono) || !isfinite(p.chi2_stereo) || !isfinite(p.min_rel_decrease)) return YGZ_E_INVALID;
-    if (!(p.chi2_mono > 0.0) || !(p.chi2_stereo > 0.0) || p.rounds < 1 || p.rounds > YGZ_POPT_MAX_ROUNDS || p.iterations < 1 || p.iterations > YGZ_POPT_MAX_STEPS ||
-        p.max_trials < 1 || p.max_trials > YGZ_POPT_MAX_STEPS)
-        return YGZ_E_INVALID;
+    if (!isfinite(p.baseline) || !ygz_pose_params_ok(p)) return YGZ_E_INVALID;
     if (frame_off[0] != 0) return YGZ_E_INVALID;
     for (int f = 0; f < n_frames; ++f) if (frame_off[f + 1] < frame_off[f]) return YGZ_E_INVALID;
     const size_t n = (size_t)frame_off[n_frames], nz = n > 0 ? n : 1;
@@ -448,12 +445,8 @@ extern "C" int ygz_hip_optimize_pose_stereo(ygz_hip_ctx *ctx, int n_frames, cons
     A.status = (int32_t *)(db + o_st); A.iterations = (int32_t *)(db + o_it);
     A.inliers = (int32_t *)(db + o_inl); A.rounds_run = (int32_t *)(db + o_run);
     A.outlier = db + o_out;
-    A.K[0] = (double)ctx->prm.fx; A.K[1] = (double)ctx->prm.fy; A.K[2] = (double)ctx->prm.cx; A.K[3] = (double)ctx->prm.cy;
-    A.K[4] = A.K[0] * p.baseline;
-    A.d2m = p.chi2_mono; A.d2s = p.chi2_stereo; A.dm = sqrt(p.chi2_mono); A.ds = sqrt(p.chi2_stereo);
-    A.min_rel_decrease = p.min_rel_decrease;
-    A.rounds = p.rounds; A.iters = p.iterations; A.max_trials = p.max_trials; A.robust_rounds = p.robust_rounds;
-    A.min_edges = p.min_edges; A.min_inliers = p.min_inliers;
+    const double K4[4] = { (double)ctx->prm.fx, (double)ctx->prm.fy, (double)ctx->prm.cx, (double)ctx->prm.cy };
+    ygz_popt_set_params(A, K4, p.baseline, p);
     YGZ_LAUNCH(ctx, KID_POSE_OPT, k_pose_opt, dim3((unsigned)n_frames), dim3(PT_THREADS), A);
     YGZ_HIPCHK(ctx, hipGetLastError());
     if ((rc = ygz_kcopy(ctx, hb + o_pose, db + o_pose, o - o_pose, hipMemcpyDeviceToHost)) != YGZ_OK) return rc;

@@ -23,9 +23,9 @@
 #include <string.h>
 #pragma clang fp contract(off)
 #include "ur_dev.h"
+#include "slot_pose_dev.h"
 
 #define SL_LANES      256
-#define SL_MAX_CELLS  32768              // the taken bitmap of a frame: 4 KiB of LDS
 
 struct SlmSetTab { uint64_t pw, desc, dmax, normal; int32_t n_pt, pad_; };     // byte offsets of a set's arrays in the packed block
 
@@ -44,29 +44,26 @@ struct SlmDev {
     uint32_t *keys; int32_t *n_cand, *n_gated, *level, *reason; double *proj;
     int32_t *match, *dist, *outcome;
     // per (frame, keypoint) [n_frames][cells]
-    int32_t *kp_point, *edge_of; uint8_t *out_outlier; double *out_chi2;
-    // the edges of frame f: [f * cells, edge_end[f])
-    double *e_pw, *e_obs; int32_t *e_level; uint8_t *e_kind; const uint8_t *e_outlier; const double *e_chi2;
-    int32_t *edge_end, *status, *counts;
+    int32_t *kp_point;
+    SlotEdges E;                                     // the edges of frame f: [f * cells, edge_end[f])
+    int32_t *status, *counts;
     double bf, th, ratio;
     int cells, n_frames, n_slots, n_sets, th_dist, min_edges;
 };
-
-__device__ __forceinline__ int sl_count(const SlmDev &A, int slot) { return min(max(A.n_kp[slot], 0), A.cells); }
 
 __global__ __launch_bounds__(SL_LANES) void k_slm_gather(SlmDev A)
 {
     const int y = blockIdx.y, i = blockIdx.x * SL_LANES + threadIdx.x;
     if (y >= A.n_slots) {                                               // a frame's prior: its taken flags and its skip bytes
         const int f = y - A.n_slots;
-        if (i >= sl_count(A, A.fr_slot[f])) return;
+        if (i >= ygz_slot_count(A.n_kp, A.fr_slot[f], A.cells)) return;
         const int pr = A.prior[(size_t)f * A.cells + i];
         A.kp_taken[(size_t)f * A.cells + i] = pr >= 0 ? 1 : 0;
         if (pr >= 0 && pr < A.set_tab[A.fr_set[f]].n_pt) A.pt_skip[(size_t)A.pt_off[f] + pr] = 1;
         return;
     }
     const int s = A.slots[y];
-    if (i < sl_count(A, s)) {
+    if (i < ygz_slot_count(A.n_kp, s, A.cells)) {
         const size_t g = (size_t)s * A.cells + i;
         const double z = A.kp_depth[g];
         A.g_ur[(size_t)y * A.cells + i] = ygz_kp_has_depth(A.kp_has_mp[g], z) ? ygz_kp_right_column(A.kp_px[2 * g], z, A.bf) : -1.0;
@@ -88,7 +85,7 @@ __global__ __launch_bounds__(SL_LANES) void k_slm_gather(SlmDev A)
         P.kp_px = A.kp_px + 2 * o; P.kp_level = A.kp_level + o; P.kp_desc = A.kp_desc + 8 * o; P.kp_ur = A.g_ur + (size_t)A.fr_dslot[i] * A.cells;
         P.kp_taken = A.prior ? A.kp_taken + (size_t)i * A.cells : nullptr;
         P.pt_skip = A.prior ? A.pt_skip + (size_t)A.pt_off[i] : nullptr;
-        P.n_kp = sl_count(A, sl); P.set = A.fr_set[i]; P.pt_off = A.pt_off[i]; P.mode = 1; P.direction = 0; P.pad_ = 0;
+        P.n_kp = ygz_slot_count(A.n_kp, sl, A.cells); P.set = A.fr_set[i]; P.pt_off = A.pt_off[i]; P.mode = 1; P.direction = 0; P.pad_ = 0;
         P.th = A.th;
 #pragma unroll
         for (int k = 0; k < 7; ++k) P.T[k] = A.poses[7 * (size_t)i + k];
@@ -100,7 +97,7 @@ enum { SL_N_UR = 0, SL_N_PRIOR, SL_N_SEARCHED, SL_N_OVER, SL_N_NEW, SL_N_COUNTER
 
 __global__ __launch_bounds__(SL_LANES) void k_slm_resolve(SlmDev A)
 {
-    __shared__ uint32_t s_taken[SL_MAX_CELLS / 32];
+    __shared__ uint32_t s_taken[YGZ_SLOT_MAX_CELLS / 32];
     __shared__ uint4 s_key[SL_LANES][2];
     __shared__ uint2 s_lv[SL_LANES];                                     // the levels of a staged list's eight entries, a byte each
     __shared__ uint32_t s_pick[SL_LANES];
@@ -224,47 +221,25 @@ __global__ __launch_bounds__(SL_LANES) void k_slm_resolve(SlmDev A)
         const int j = j0 + tid;
         const int i = (status == 0 && j < n_kp) ? A.kp_point[kb + j] : -1;
         const bool has = i >= 0 && i < n_pt;
-        const unsigned long long bal = __ballot(has);
-        if (lane == 0) s_wave[wv] = __popcll(bal);
-        __syncthreads();
-        int before = running, total = 0;
-#pragma unroll
-        for (int w = 0; w < SL_LANES / 64; ++w) { const int c = s_wave[w]; if (w < wv) before += c; total += c; }
+        const int e = ygz_edge_slot<SL_LANES>(has, running, s_wave);
         if (has) {
-            const int e = before + __popcll(bal & ((1ull << lane) - 1ull));
-            const size_t ge = kb + e;
-            const double *X = S.pw + 3 * (size_t)i;
-            A.e_pw[3 * ge] = X[0]; A.e_pw[3 * ge + 1] = X[1]; A.e_pw[3 * ge + 2] = X[2];
-            const double ur = P.kp_ur[j];
-            A.e_obs[3 * ge] = P.kp_px[2 * (size_t)j]; A.e_obs[3 * ge + 1] = P.kp_px[2 * (size_t)j + 1]; A.e_obs[3 * ge + 2] = ur;
-            A.e_level[ge] = P.kp_level[j];
-            A.e_kind[ge] = ur >= 0 ? 2 : 1;
-            A.edge_of[kb + j] = e;
-        } else if (j < cells) A.edge_of[kb + j] = -1;
-        running += total;
+            ygz_edge_write(A.E, kb + e, S.pw + 3 * (size_t)i, P.kp_px + 2 * (size_t)j, P.kp_ur[j], P.kp_level[j]);
+            A.E.edge_of[kb + j] = e;
+        } else if (j < cells) A.E.edge_of[kb + j] = -1;
         __syncthreads();
     }
-    if (tid == 0) A.edge_end[f] = (int32_t)kb + running;
+    if (tid == 0) A.E.edge_end[f] = (int32_t)kb + running;
 }
 
 __global__ __launch_bounds__(SL_LANES) void k_slm_scatter(SlmDev A)
 {
     const int f = blockIdx.y, j = blockIdx.x * SL_LANES + threadIdx.x;
     if (j >= A.cells) return;
-    const size_t kb = (size_t)f * A.cells, g = kb + j;
-    const int e = A.edge_of[g];
-    const bool has = e >= 0 && e < A.cells;
-    A.out_outlier[g] = has ? A.e_outlier[kb + e] : 0;
-    A.out_chi2[g] = has ? A.e_chi2[kb + e] : -1.0;
+    const size_t kb = (size_t)f * A.cells;
+    ygz_edge_scatter(A.E, kb, kb + j, A.cells);
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------------------
-static bool slm_finite(const double *v, size_t n)
-{
-    for (size_t i = 0; i < n; ++i) if (!isfinite(v[i])) return false;
-    return true;
-}
-
 extern "C" {
 
 void ygz_hip_default_slm_params(ygz_slm_params *p)
@@ -292,11 +267,7 @@ int ygz_hip_stereo_local_map_slots(ygz_hip_ctx *ctx, int n_sets, const ygz_strac
     if (!(p.baseline > 0) || !(p.th > 0) || !(p.ratio > 0) || !(p.r_near > 0) || !(p.r_wide > 0) || p.th_dist < 0 || p.th_dist > 256 ||
         p.min_edges < 0)
         return YGZ_E_INVALID;
-    const ygz_pose_opt_params &q = p.pose;
-    if (!isfinite(q.chi2_mono) || !isfinite(q.chi2_stereo) || !isfinite(q.min_rel_decrease)) return YGZ_E_INVALID;
-    if (!(q.chi2_mono > 0.0) || !(q.chi2_stereo > 0.0) || q.rounds < 1 || q.rounds > YGZ_POPT_MAX_ROUNDS || q.iterations < 1 ||
-        q.iterations > YGZ_POPT_MAX_STEPS || q.max_trials < 1 || q.max_trials > YGZ_POPT_MAX_STEPS)
-        return YGZ_E_INVALID;
+    if (!ygz_pose_params_ok(p.pose)) return YGZ_E_INVALID;
     for (int s = 0; s < n_sets; ++s) {
         if (sets[s].n_pt < 0) return YGZ_E_INVALID;
         if (sets[s].n_pt > 0 && (!sets[s].pw || !sets[s].pt_desc || !sets[s].pt_dmax || !sets[s].pt_normal)) return YGZ_E_INVALID;
@@ -310,17 +281,17 @@ int ygz_hip_stereo_local_map_slots(ygz_hip_ctx *ctx, int n_sets, const ygz_strac
         if (sets[set[f]].n_pt > max_pt) max_pt = sets[set[f]].n_pt;
     }
     if (N > YGZ_SLM_MAX_PAIRS) return YGZ_E_CAPACITY;
-    if (!slm_finite(T, 7 * F)) return YGZ_E_INVALID;
+    if (!ygz_all_finite(T, 7 * F)) return YGZ_E_INVALID;
     for (int s = 0; s < n_sets; ++s) {
         const size_t n = (size_t)sets[s].n_pt;
-        if (n && (!slm_finite(sets[s].pw, 3 * n) || !slm_finite(sets[s].pt_dmax, n) || !slm_finite(sets[s].pt_normal, 3 * n))) return YGZ_E_INVALID;
+        if (n && (!ygz_all_finite(sets[s].pw, 3 * n) || !ygz_all_finite(sets[s].pt_dmax, n) || !ygz_all_finite(sets[s].pt_normal, 3 * n))) return YGZ_E_INVALID;
     }
     if (!ctx) return YGZ_E_INVALID;
     for (int f = 0; f < n_frames; ++f)
         if (slot[f] >= ctx->prm.max_frames) return YGZ_E_INVALID;
     const int L = ctx->prm.pyramid_levels;
     if (L < 1 || L > YGZ_MAX_LEVELS) return YGZ_E_INVALID;
-    if (ctx->cells > SL_MAX_CELLS) return YGZ_E_CAPACITY;
+    if (ctx->cells > YGZ_SLOT_MAX_CELLS) return YGZ_E_CAPACITY;
     const size_t Cn = (size_t)ctx->cells, NK = F * Cn;
     if (prior)
         for (size_t f = 0; f < F; ++f) {
@@ -338,13 +309,11 @@ int ygz_hip_stereo_local_map_slots(ygz_hip_ctx *ctx, int n_sets, const ygz_strac
     std::vector<int32_t> slots, where((size_t)ctx->prm.max_frames, -1), ds(F), pt_off(F), e_off(F);
     size_t run = 0;
     for (size_t f = 0; f < F; ++f) {
-        const int32_t s = slot[f];
-        if (where[(size_t)s] < 0) { where[(size_t)s] = (int32_t)slots.size(); slots.push_back(s); }
-        ds[f] = where[(size_t)s];
+        ds[f] = ygz_distinct_slot(slots, where, slot[f]);
         pt_off[f] = (int32_t)run; run += (size_t)sets[set[f]].n_pt;
         e_off[f] = (int32_t)(f * Cn);
     }
-    const size_t D = slots.size(), R8 = F * YGZ_POPT_MAX_ROUNDS;
+    const size_t D = slots.size();
 
     // up: [in | the frames' tables | the sets | prior | the skip rows, zero | poses), back: [poses | the small outputs | the per-keypoint
     // outputs | the per-point outputs), then what stays on the device
@@ -363,9 +332,9 @@ int ygz_hip_stereo_local_map_slots(ygz_hip_ctx *ctx, int n_sets, const ygz_strac
     }
     const size_t o_prior = B.add_n<int32_t>(prior ? NK : 0), o_skip = B.add_n<uint8_t>(prior ? N : 0);
     const size_t o_pose = B.add_n<double>(F * 7), in_end = B.end;
-    const size_t o_status = B.add_n<int32_t>(F), o_counts = B.add_n<int32_t>(F * 8), o_inl = B.add_n<int32_t>(F), o_run = B.add_n<int32_t>(F);
-    const size_t o_rst = B.add_n<int32_t>(R8), o_rit = B.add_n<int32_t>(R8);
-    const size_t o_rci = B.add_n<double>(R8), o_rcf = B.add_n<double>(R8), o_rlam = B.add_n<double>(R8);
+    const size_t o_status = B.add_n<int32_t>(F), o_counts = B.add_n<int32_t>(F * 8);
+    YgzPoseBlock PB;
+    PB.add_results(B, F);
     size_t back_end = B.end;
     // the per-keypoint and per-point outputs, fetched up to the last one the caller asked for
     const size_t o_kpt = B.add_n<int32_t>(NK); if (kp_point) back_end = B.end;
@@ -379,9 +348,8 @@ int ygz_hip_stereo_local_map_slots(ygz_hip_ctx *ctx, int n_sets, const ygz_strac
     const size_t o_nc = B.add_n<int32_t>(N); if (n_cand && N) back_end = B.end;
     const size_t o_ng = B.add_n<int32_t>(N); if (n_gated && N) back_end = B.end;
     const size_t o_proj = B.add_n<double>(N * 3); if (proj && N) back_end = B.end;
-    const size_t o_keys = B.add_n<uint4>(N * 2), o_eof = B.add_n<int32_t>(NK);
-    const size_t o_epw = B.add_n<double>(NK * 3), o_eobs = B.add_n<double>(NK * 3), o_elvl = B.add_n<int32_t>(NK), o_ekind = B.add_n<uint8_t>(NK);
-    const size_t o_eout = B.add_n<uint8_t>(NK), o_echi = B.add_n<double>(NK), o_end = B.add_n<int32_t>(F);
+    const size_t o_keys = B.add_n<uint4>(N * 2);
+    PB.add_edges(B, F, Cn);
     const size_t o_sets = B.add_n<StSetDev>((size_t)n_sets), o_probs = B.add_n<StProbDev>(F);
     const size_t o_gur = B.add_n<double>(D * Cn), o_taken = B.add_n<uint8_t>(prior ? NK : 0), total = B.end;
     YgzBlob blob;
@@ -422,27 +390,16 @@ int ygz_hip_stereo_local_map_slots(ygz_hip_ctx *ctx, int n_sets, const ygz_strac
     A.keys = ygz_at<uint32_t>(dev, o_keys); A.n_cand = ygz_at<int32_t>(dev, o_nc); A.n_gated = ygz_at<int32_t>(dev, o_ng);
     A.level = ygz_at<int32_t>(dev, o_lvl); A.reason = ygz_at<int32_t>(dev, o_why); A.proj = ygz_at<double>(dev, o_proj);
     A.match = ygz_at<int32_t>(dev, o_match); A.dist = ygz_at<int32_t>(dev, o_dist); A.outcome = ygz_at<int32_t>(dev, o_oc);
-    A.kp_point = ygz_at<int32_t>(dev, o_kpt); A.edge_of = ygz_at<int32_t>(dev, o_eof); A.out_outlier = dev + o_out;
-    A.out_chi2 = ygz_at<double>(dev, o_chi2);
-    A.e_pw = ygz_at<double>(dev, o_epw); A.e_obs = ygz_at<double>(dev, o_eobs); A.e_level = ygz_at<int32_t>(dev, o_elvl); A.e_kind = dev + o_ekind;
-    A.e_outlier = dev + o_eout; A.e_chi2 = ygz_at<const double>(dev, o_echi);
-    A.edge_end = ygz_at<int32_t>(dev, o_end); A.status = ygz_at<int32_t>(dev, o_status); A.counts = ygz_at<int32_t>(dev, o_counts);
+    A.kp_point = ygz_at<int32_t>(dev, o_kpt);
+    ygz_slot_edges_bind(A.E, dev, PB, o_out, o_chi2);
+    A.status = ygz_at<int32_t>(dev, o_status); A.counts = ygz_at<int32_t>(dev, o_counts);
     A.bf = in.bf; A.th = p.th; A.ratio = p.ratio;
     A.cells = ctx->cells; A.n_frames = n_frames; A.n_slots = (int)D; A.n_sets = n_sets; A.th_dist = p.th_dist; A.min_edges = p.min_edges;
 
     PoptArgs G;
     memset(&G, 0, sizeof G);
-    G.off = ygz_at<const int32_t>(dev, o_off); G.end = A.edge_end; G.pw = A.e_pw; G.obs = A.e_obs; G.level = A.e_level; G.kind = A.e_kind;
-    G.poses = A.poses; G.chi2 = ygz_at<double>(dev, o_echi);
-    G.cost_initial = ygz_at<double>(dev, o_rci); G.cost_final = ygz_at<double>(dev, o_rcf); G.lambda = ygz_at<double>(dev, o_rlam);
-    G.status = ygz_at<int32_t>(dev, o_rst); G.iterations = ygz_at<int32_t>(dev, o_rit);
-    G.inliers = ygz_at<int32_t>(dev, o_inl); G.rounds_run = ygz_at<int32_t>(dev, o_run); G.outlier = dev + o_eout;
-    for (int k = 0; k < 4; ++k) G.K[k] = in.K4[k];
-    G.K[4] = in.K4[0] * p.baseline;
-    G.d2m = q.chi2_mono; G.d2s = q.chi2_stereo; G.dm = sqrt(q.chi2_mono); G.ds = sqrt(q.chi2_stereo);
-    G.min_rel_decrease = q.min_rel_decrease;
-    G.rounds = q.rounds; G.iters = q.iterations; G.max_trials = q.max_trials; G.robust_rounds = q.robust_rounds;
-    G.min_edges = q.min_edges; G.min_inliers = q.min_inliers;
+    ygz_popt_bind(G, dev, PB, o_off, o_pose);
+    ygz_popt_set_params(G, in.K4, p.baseline, p.pose);
 
     int widest = ctx->cells > n_frames ? ctx->cells : n_frames;
     if (n_sets > widest) widest = n_sets;
@@ -458,13 +415,7 @@ int ygz_hip_stereo_local_map_slots(ygz_hip_ctx *ctx, int n_sets, const ygz_strac
     memcpy(T_out, up + o_pose, F * 56);
     if (status) memcpy(status, up + o_status, F * 4);
     if (counts) memcpy(counts, up + o_counts, F * 32);
-    if (inliers) memcpy(inliers, up + o_inl, F * 4);
-    if (rounds_run) memcpy(rounds_run, up + o_run, F * 4);
-    if (round_status) memcpy(round_status, up + o_rst, R8 * 4);
-    if (round_iterations) memcpy(round_iterations, up + o_rit, R8 * 4);
-    if (round_cost_initial) memcpy(round_cost_initial, up + o_rci, R8 * 8);
-    if (round_cost_final) memcpy(round_cost_final, up + o_rcf, R8 * 8);
-    if (round_lambda) memcpy(round_lambda, up + o_rlam, R8 * 8);
+    PB.copy_results(up, F, inliers, rounds_run, round_status, round_iterations, round_cost_initial, round_cost_final, round_lambda);
     if (kp_point) memcpy(kp_point, up + o_kpt, NK * 4);
     if (outlier) memcpy(outlier, up + o_out, NK);
     if (chi2) memcpy(chi2, up + o_chi2, NK * 8);

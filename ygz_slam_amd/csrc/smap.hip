@@ -12,6 +12,7 @@
 #include "ygz_internal.h"
 #include <math.h>
 #include <string.h>
+#include "pose_block.h"                 // ygz_all_finite
 #pragma clang fp contract(off)
 
 #define SM_PAIR_THREADS 64
@@ -297,12 +298,6 @@ static void smap_camera(const double *T, double *C)
     for (int i = 0; i < 3; ++i) C[12 + i] = -((C[i] * C[9] + C[3 + i] * C[10]) + C[6 + i] * C[11]);
 }
 
-static bool smap_finite(const double *v, size_t n)
-{
-    for (size_t i = 0; i < n; ++i) if (!isfinite(v[i])) return false;
-    return true;
-}
-
 static bool smap_params_ok(const ygz_smap_params &p)
 {
     if (!isfinite(p.baseline) || !isfinite(p.chi2_mono) || !isfinite(p.chi2_stereo) || !isfinite(p.cos_parallax_max) || !isfinite(p.ratio_factor) ||
@@ -312,7 +307,7 @@ static bool smap_params_ok(const ygz_smap_params &p)
            p.min_close >= 0;
 }
 
-static bool smap_k_ok(const double *K4) { return smap_finite(K4, 4) && K4[0] > 0.0 && K4[1] > 0.0; }
+static bool smap_k_ok(const double *K4) { return ygz_all_finite(K4, 4) && K4[0] > 0.0 && K4[1] > 0.0; }
 
 extern "C" {
 
@@ -340,11 +335,11 @@ int ygz_hip_stereo_create_map_points(ygz_hip_ctx *ctx, int n_problems, const ygz
     if (!smap_params_ok(p) || !smap_k_ok(K4)) return YGZ_E_INVALID;
     for (int q = 0; q < n_problems; ++q) {
         const ygz_smap_problem &b = problems[q];
-        if (!smap_finite(b.T1, 7) || !smap_finite(b.T2, 7)) return YGZ_E_INVALID;
+        if (!ygz_all_finite(b.T1, 7) || !ygz_all_finite(b.T2, 7)) return YGZ_E_INVALID;
         const size_t n = (size_t)b.n;
         if (!n) continue;
         if (!b.px1 || !b.px2 || !b.ur1 || !b.ur2 || !b.level1 || !b.level2) return YGZ_E_INVALID;
-        if (!smap_finite(b.px1, 2 * n) || !smap_finite(b.px2, 2 * n) || !smap_finite(b.ur1, n) || !smap_finite(b.ur2, n)) return YGZ_E_INVALID;
+        if (!ygz_all_finite(b.px1, 2 * n) || !ygz_all_finite(b.px2, 2 * n) || !ygz_all_finite(b.ur1, n) || !ygz_all_finite(b.ur2, n)) return YGZ_E_INVALID;
         for (size_t i = 0; i < n; ++i) {
             if (b.ur1[i] >= 0 && (!b.depth1 || !isfinite(b.depth1[i]))) return YGZ_E_INVALID;
             if (b.ur2[i] >= 0 && (!b.depth2 || !isfinite(b.depth2[i]))) return YGZ_E_INVALID;
@@ -420,8 +415,8 @@ int ygz_hip_stereo_keyframe_points(ygz_hip_ctx *ctx, const double T[7], int n, c
     if (n > 0 && (!px || !depth || !has_point || !rank || !selected || !pos_world)) return YGZ_E_INVALID;
     ygz_smap_params p;
     if (params) p = *params; else ygz_hip_default_smap_params(&p);
-    if (!smap_params_ok(p) || !smap_k_ok(K4) || !smap_finite(T, 7)) return YGZ_E_INVALID;
-    if (n > 0 && (!smap_finite(px, 2 * (size_t)n) || !smap_finite(depth, (size_t)n))) return YGZ_E_INVALID;
+    if (!smap_params_ok(p) || !smap_k_ok(K4) || !ygz_all_finite(T, 7)) return YGZ_E_INVALID;
+    if (n > 0 && (!ygz_all_finite(px, 2 * (size_t)n) || !ygz_all_finite(depth, (size_t)n))) return YGZ_E_INVALID;
     if (!ctx) return YGZ_E_INVALID;
     if (n > ctx->cells) return YGZ_E_CAPACITY;
     YgzDeviceGuard dg_(ctx);

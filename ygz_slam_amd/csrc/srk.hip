@@ -23,9 +23,9 @@
 #include <string.h>
 #pragma clang fp contract(off)
 #include "ur_dev.h"
+#include "slot_pose_dev.h"
 
 #define SR_LANES      256
-#define SR_MAX_CELLS  32768
 #define SR_FREE       0x7fffffff         // a frame keypoint that no keyframe feature names
 
 struct SrkSetTab { uint64_t pw; int32_t n_pt, pad_; };                  // byte offset of a set's points in the packed block
@@ -45,15 +45,12 @@ struct SrkDev {
     // per (frame, keyframe keypoint) [n_frames][cells]
     int32_t *match12, *outcome;
     // per (frame, frame keypoint) [n_frames][cells]
-    int32_t *holder, *kp_point, *prior, *edge_of; uint8_t *out_outlier; double *out_chi2;
-    // the edges of frame f: [f * cells, edge_end[f])
-    double *e_pw, *e_obs; int32_t *e_level; uint8_t *e_kind; const uint8_t *e_outlier; const double *e_chi2;
-    int32_t *edge_end, *status, *counts, *rot; const int32_t *inliers;
+    int32_t *holder, *kp_point, *prior;
+    SlotEdges E;                                     // the edges of frame f: [f * cells, edge_end[f])
+    int32_t *status, *counts, *rot; const int32_t *inliers;
     double bf;
     int cells, n_frames, n_slots, n_kf, slot_min, span, check_orientation, min_matches, min_inliers;
 };
-
-__device__ __forceinline__ int sr_count(const SrkDev &A, int slot) { return min(max(A.n_kp[slot], 0), A.cells); }
 
 __global__ __launch_bounds__(SR_LANES) void k_srk_gather(SrkDev A, int pass)
 {
@@ -61,24 +58,24 @@ __global__ __launch_bounds__(SR_LANES) void k_srk_gather(SrkDev A, int pass)
     if (pass == 1) {                                                    // a keyframe's nodes, as k_bow_transform left them
         if (i >= A.cells) return;
         const int s = A.kf_slot[y];
-        const bool has = i < sr_count(A, s) && A.kf_point[(size_t)y * A.cells + i] >= 0;
+        const bool has = i < ygz_slot_count(A.n_kp, s, A.cells) && A.kf_point[(size_t)y * A.cells + i] >= 0;
         A.node1[(size_t)y * A.cells + i] = has ? A.kp_node[(size_t)s * A.cells + i] : -1;
         return;
     }
     const int s = A.slots[y];
-    if (i < sr_count(A, s)) {
+    if (i < ygz_slot_count(A.n_kp, s, A.cells)) {
         const size_t g = (size_t)s * A.cells + i;
         const double z = A.kp_depth[g];
         A.g_ur[(size_t)y * A.cells + i] = ygz_kp_has_depth(A.kp_has_mp[g], z) ? ygz_kp_right_column(A.kp_px[2 * g], z, A.bf) : -1.0;
     }
     if (y != 0) return;
-    if (i < A.span) A.bow_n[i] = A.named[i] ? sr_count(A, A.slot_min + i) : 0;
+    if (i < A.span) A.bow_n[i] = A.named[i] ? ygz_slot_count(A.n_kp, A.slot_min + i, A.cells) : 0;
     if (i < A.n_frames) {
         const int k = A.fr_kf[i], s1 = A.kf_slot[k], s2 = A.fr_slot[i];
         const size_t o1 = (size_t)s1 * A.cells, o2 = (size_t)s2 * A.cells;
         BowPair P;
         P.d1 = A.kp_desc + 8 * o1; P.d2 = A.kp_desc + 8 * o2; P.n1 = A.node1 + (size_t)k * A.cells; P.n2 = A.kp_node + o2;
-        P.p1 = A.kp_px + 2 * o1; P.p2 = A.kp_px + 2 * o2; P.c1 = sr_count(A, s1); P.c2 = sr_count(A, s2);
+        P.p1 = A.kp_px + 2 * o1; P.p2 = A.kp_px + 2 * o2; P.c1 = ygz_slot_count(A.n_kp, s1, A.cells); P.c2 = ygz_slot_count(A.n_kp, s2, A.cells);
 #pragma unroll
         for (int e = 0; e < 9; ++e) P.E[e] = 0.0;
         A.pairs[i] = P;
@@ -86,26 +83,14 @@ __global__ __launch_bounds__(SR_LANES) void k_srk_gather(SrkDev A, int pass)
     }
 }
 
-// the bin of a match's rotation (yo_bow_orientation: round(rot / 30) with the reference's factor, 30 -> 0), or -1 outside the histogram
-__device__ __forceinline__ int sr_bin(float a1, float a2)
-{
-    float r = (float)((double)a1 - (double)a2);
-    if (r < 0) r += 360;
-    const float fb = r * (1.0f / 30);
-    if (!(fb >= 0) || !(fb < 64.0f)) return -1;                          // a bin past 29 has no counter; nothing is converted that an int cannot hold
-    int bin = (int)((double)fb + 0.5);                                   // round of a value >= 0: half away from zero
-    if (bin == 30) bin = 0;
-    return bin < 30 ? bin : -1;
-}
-
 enum { SR_N_UR = 0, SR_N_POINT, SR_N_MATCH, SR_N_LOST, SR_N_ROT, SR_N_COUNTERS };
 
 __global__ __launch_bounds__(SR_LANES) void k_srk_resolve(SrkDev A)
 {
     __shared__ int s_hist[30], s_ind[3], s_cnt[SR_N_COUNTERS], s_wave[SR_LANES / 64];
-    const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int f = blockIdx.x, tid = threadIdx.x;
     const int k = A.fr_kf[f], s1 = A.kf_slot[k], s2 = A.fr_slot[f];
-    const int cells = A.cells, n1 = sr_count(A, s1), n2 = sr_count(A, s2);
+    const int cells = A.cells, n1 = ygz_slot_count(A.n_kp, s1, A.cells), n2 = ygz_slot_count(A.n_kp, s2, A.cells);
     const SrkSetTab S = A.set_tab[A.kf_set[k]];
     const int n_pt = S.n_pt;
     const double *pw = reinterpret_cast<const double *>(A.block + S.pw);
@@ -145,22 +130,11 @@ __global__ __launch_bounds__(SR_LANES) void k_srk_resolve(SrkDev A)
             if (i >= n1 || kfp[i] < 0) continue;
             const int m = m12[i];
             if (m < 0 || m >= n2 || holder[m] != i) continue;
-            const int bin = sr_bin(A.kp_angle[o1 + i], A.kp_angle[o2 + m]);
+            const int bin = ygz_rot_bin(A.kp_angle[o1 + i], A.kp_angle[o2 + m]);
             if (bin >= 0) atomicAdd(&s_hist[bin], 1);
         }
         __syncthreads();
-        if (tid == 0) {
-            int max1 = 0, max2 = 0, max3 = 0, i0 = -1, i1 = -1, i2 = -1;
-            for (int b = 0; b < 30; ++b) {
-                const int s = s_hist[b];
-                if (s > max1) { max3 = max2; max2 = max1; max1 = s; i2 = i1; i1 = i0; i0 = b; }
-                else if (s > max2) { max3 = max2; max2 = s; i2 = i1; i1 = b; }
-                else if (s > max3) { max3 = s; i2 = b; }
-            }
-            if ((float)max2 < 0.1f * (float)max1) { i1 = -1; i2 = -1; }
-            else if ((float)max3 < 0.1f * (float)max1) { i2 = -1; }
-            s_ind[0] = i0; s_ind[1] = i1; s_ind[2] = i2;
-        }
+        if (tid == 0) ygz_rot_top3(s_hist, s_ind);
         __syncthreads();
     }
     const int b0 = s_ind[0], b1 = s_ind[1], b2 = s_ind[2];
@@ -176,7 +150,7 @@ __global__ __launch_bounds__(SR_LANES) void k_srk_resolve(SrkDev A)
             if (r < 0 || r >= n2) oc = 1;
             else if (holder[r] != i) { oc = 2; ++c_lost; }
             else {
-                const int bin = A.check_orientation ? sr_bin(A.kp_angle[o1 + i], A.kp_angle[o2 + r]) : 0;
+                const int bin = A.check_orientation ? ygz_rot_bin(A.kp_angle[o1 + i], A.kp_angle[o2 + r]) : 0;
                 if (A.check_orientation && !(bin >= 0 && (bin == b0 || bin == b1 || bin == b2))) { oc = 4; ++c_rot; }
                 else { oc = 0; m = r; }
             }
@@ -210,27 +184,14 @@ __global__ __launch_bounds__(SR_LANES) void k_srk_resolve(SrkDev A)
         }
         if (j < cells) A.kp_point[kb + j] = p;
         const bool has = status == 0 && p >= 0 && p < n_pt;
-        const unsigned long long bal = __ballot(has);
-        if (lane == 0) s_wave[wv] = __popcll(bal);
-        __syncthreads();
-        int before = running, total = 0;
-#pragma unroll
-        for (int w = 0; w < SR_LANES / 64; ++w) { const int c = s_wave[w]; if (w < wv) before += c; total += c; }
+        const int e = ygz_edge_slot<SR_LANES>(has, running, s_wave);
         if (has) {
-            const int e = before + __popcll(bal & ((1ull << lane) - 1ull));
-            const size_t ge = kb + e, gj = o2 + j;
-            const double *X = pw + 3 * (size_t)p;
-            A.e_pw[3 * ge] = X[0]; A.e_pw[3 * ge + 1] = X[1]; A.e_pw[3 * ge + 2] = X[2];
-            const double u = ur[j];
-            A.e_obs[3 * ge] = A.kp_px[2 * gj]; A.e_obs[3 * ge + 1] = A.kp_px[2 * gj + 1]; A.e_obs[3 * ge + 2] = u;
-            A.e_level[ge] = A.kp_level[gj];
-            A.e_kind[ge] = u >= 0 ? 2 : 1;
-            A.edge_of[kb + j] = e;
-        } else if (j < cells) A.edge_of[kb + j] = -1;
-        running += total;
+            ygz_edge_write(A.E, kb + e, pw + 3 * (size_t)p, A.kp_px + 2 * (o2 + j), ur[j], A.kp_level[o2 + j]);
+            A.E.edge_of[kb + j] = e;
+        } else if (j < cells) A.E.edge_of[kb + j] = -1;
         __syncthreads();
     }
-    if (tid == 0) A.edge_end[f] = (int32_t)kb + running;
+    if (tid == 0) A.E.edge_end[f] = (int32_t)kb + running;
 }
 
 __global__ __launch_bounds__(SR_LANES) void k_srk_scatter(SrkDev A)
@@ -238,22 +199,12 @@ __global__ __launch_bounds__(SR_LANES) void k_srk_scatter(SrkDev A)
     const int f = blockIdx.y, j = blockIdx.x * SR_LANES + threadIdx.x;
     if (j >= A.cells) return;
     const size_t kb = (size_t)f * A.cells, g = kb + j;
-    const int e = A.edge_of[g];
-    const bool has = e >= 0 && e < A.cells;
-    const uint8_t out = has ? A.e_outlier[kb + e] : 0;
-    A.out_outlier[g] = out;
-    A.out_chi2[g] = has ? A.e_chi2[kb + e] : -1.0;
+    const uint8_t out = ygz_edge_scatter(A.E, kb, g, A.cells);
     A.prior[g] = out ? -1 : A.kp_point[g];
     if (j == 0 && A.status[f] == 0 && A.inliers[f] < A.min_inliers) A.status[f] = 2;
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------------------
-static bool srk_finite(const double *v, size_t n)
-{
-    for (size_t i = 0; i < n; ++i) if (!isfinite(v[i])) return false;
-    return true;
-}
-
 extern "C" {
 
 void ygz_hip_default_srk_params(ygz_srk_params *p)
@@ -280,11 +231,7 @@ int ygz_hip_stereo_ref_keyframe_slots(ygz_hip_ctx *ctx, int n_sets, const ygz_st
     if (!isfinite(p.baseline) || !isfinite(p.knn_ratio)) return YGZ_E_INVALID;
     if (!(p.baseline > 0) || p.th_low < 0 || p.th_low > 256 || !(p.knn_ratio > 0) || p.levelsup < 0 || p.min_matches < 0 || p.min_inliers < 0)
         return YGZ_E_INVALID;
-    const ygz_pose_opt_params &q = p.pose;
-    if (!isfinite(q.chi2_mono) || !isfinite(q.chi2_stereo) || !isfinite(q.min_rel_decrease)) return YGZ_E_INVALID;
-    if (!(q.chi2_mono > 0.0) || !(q.chi2_stereo > 0.0) || q.rounds < 1 || q.rounds > YGZ_POPT_MAX_ROUNDS || q.iterations < 1 ||
-        q.iterations > YGZ_POPT_MAX_STEPS || q.max_trials < 1 || q.max_trials > YGZ_POPT_MAX_STEPS)
-        return YGZ_E_INVALID;
+    if (!ygz_pose_params_ok(p.pose)) return YGZ_E_INVALID;
     for (int s = 0; s < n_sets; ++s)
         if (sets[s].n_pt < 0 || (sets[s].n_pt > 0 && !sets[s].pw)) return YGZ_E_INVALID;
     for (int k = 0; k < n_keyframes; ++k)
@@ -292,9 +239,9 @@ int ygz_hip_stereo_ref_keyframe_slots(ygz_hip_ctx *ctx, int n_sets, const ygz_st
     for (int f = 0; f < n_frames; ++f)
         if (slot[f] < 0 || kf[f] < 0 || kf[f] >= n_keyframes) return YGZ_E_INVALID;
     const size_t F = (size_t)n_frames, Kn = (size_t)n_keyframes;
-    if (!srk_finite(T, 7 * F)) return YGZ_E_INVALID;
+    if (!ygz_all_finite(T, 7 * F)) return YGZ_E_INVALID;
     for (int s = 0; s < n_sets; ++s)
-        if (sets[s].n_pt > 0 && !srk_finite(sets[s].pw, 3 * (size_t)sets[s].n_pt)) return YGZ_E_INVALID;
+        if (sets[s].n_pt > 0 && !ygz_all_finite(sets[s].pw, 3 * (size_t)sets[s].n_pt)) return YGZ_E_INVALID;
     if (!ctx) return YGZ_E_INVALID;
     for (int k = 0; k < n_keyframes; ++k)
         if (kf_slot[k] >= ctx->prm.max_frames) return YGZ_E_INVALID;
@@ -302,7 +249,7 @@ int ygz_hip_stereo_ref_keyframe_slots(ygz_hip_ctx *ctx, int n_sets, const ygz_st
         if (slot[f] >= ctx->prm.max_frames) return YGZ_E_INVALID;
     const int L = ctx->prm.pyramid_levels;
     if (L < 1 || L > YGZ_MAX_LEVELS) return YGZ_E_INVALID;
-    if (ctx->cells > SR_MAX_CELLS) return YGZ_E_CAPACITY;
+    if (ctx->cells > YGZ_SLOT_MAX_CELLS) return YGZ_E_CAPACITY;
     const size_t Cn = (size_t)ctx->cells, NK = F * Cn;
     for (size_t k = 0; k < Kn; ++k) {
         const int32_t n = sets[kf_set[k]].n_pt, *row = kf_point + k * Cn;
@@ -320,17 +267,14 @@ int ygz_hip_stereo_ref_keyframe_slots(ygz_hip_ctx *ctx, int n_sets, const ygz_st
 
     // the distinct slots of the call, keyframes first, in the order they first appear; the span of slots k_bow_transform is launched over
     std::vector<int32_t> slots, where((size_t)ctx->prm.max_frames, -1), ds(F), e_off(F);
-    for (size_t k = 0; k < Kn; ++k)
-        if (where[(size_t)kf_slot[k]] < 0) { where[(size_t)kf_slot[k]] = (int32_t)slots.size(); slots.push_back(kf_slot[k]); }
+    for (size_t k = 0; k < Kn; ++k) ygz_distinct_slot(slots, where, kf_slot[k]);
     for (size_t f = 0; f < F; ++f) {
-        const int32_t s = slot[f];
-        if (where[(size_t)s] < 0) { where[(size_t)s] = (int32_t)slots.size(); slots.push_back(s); }
-        ds[f] = where[(size_t)s];
+        ds[f] = ygz_distinct_slot(slots, where, slot[f]);
         e_off[f] = (int32_t)(f * Cn);
     }
     int32_t slot_min = slots[0], slot_max = slots[0];
     for (int32_t s : slots) { if (s < slot_min) slot_min = s; if (s > slot_max) slot_max = s; }
-    const size_t D = slots.size(), SP = (size_t)(slot_max - slot_min + 1), R8 = F * YGZ_POPT_MAX_ROUNDS;
+    const size_t D = slots.size(), SP = (size_t)(slot_max - slot_min + 1);
     std::vector<int32_t> named(SP, 0);
     for (int32_t s : slots) named[(size_t)(s - slot_min)] = 1;
 
@@ -346,9 +290,10 @@ int ygz_hip_stereo_ref_keyframe_slots(ygz_hip_ctx *ctx, int n_sets, const ygz_st
     }
     const size_t o_kfp = B.add_n<int32_t>(Kn * Cn);
     const size_t o_pose = B.add_n<double>(F * 7), in_end = B.end;
-    const size_t o_status = B.add_n<int32_t>(F), o_counts = B.add_n<int32_t>(F * 8), o_inl = B.add_n<int32_t>(F), o_run = B.add_n<int32_t>(F);
-    const size_t o_rst = B.add_n<int32_t>(R8), o_rit = B.add_n<int32_t>(R8);
-    const size_t o_rci = B.add_n<double>(R8), o_rcf = B.add_n<double>(R8), o_rlam = B.add_n<double>(R8), o_rot = B.add_n<int32_t>(F * 33);
+    const size_t o_status = B.add_n<int32_t>(F), o_counts = B.add_n<int32_t>(F * 8);
+    YgzPoseBlock PB;
+    PB.add_results(B, F);
+    const size_t o_rot = B.add_n<int32_t>(F * 33);
     size_t back_end = B.end;
     // the per-keypoint outputs, fetched up to the last one the caller asked for
     const size_t o_prior = B.add_n<int32_t>(NK); if (prior) back_end = B.end;
@@ -357,9 +302,8 @@ int ygz_hip_stereo_ref_keyframe_slots(ygz_hip_ctx *ctx, int n_sets, const ygz_st
     const size_t o_chi2 = B.add_n<double>(NK); if (chi2) back_end = B.end;
     const size_t o_m12 = B.add_n<int32_t>(NK); if (match12) back_end = B.end;
     const size_t o_oc = B.add_n<int32_t>(NK); if (outcome) back_end = B.end;
-    const size_t o_hold = B.add_n<int32_t>(NK), o_eof = B.add_n<int32_t>(NK);
-    const size_t o_epw = B.add_n<double>(NK * 3), o_eobs = B.add_n<double>(NK * 3), o_elvl = B.add_n<int32_t>(NK), o_ekind = B.add_n<uint8_t>(NK);
-    const size_t o_eout = B.add_n<uint8_t>(NK), o_echi = B.add_n<double>(NK), o_end = B.add_n<int32_t>(F);
+    const size_t o_hold = B.add_n<int32_t>(NK);
+    PB.add_edges(B, F, Cn);
     const size_t o_gur = B.add_n<double>(D * Cn), o_bown = B.add_n<int32_t>(SP), o_node1 = B.add_n<int32_t>(Kn * Cn);
     const size_t o_pairs = B.add_n<BowPair>(F), o_bcnt = B.add_n<int32_t>(F), total = B.end;
     YgzBlob blob;
@@ -390,11 +334,9 @@ int ygz_hip_stereo_ref_keyframe_slots(ygz_hip_ctx *ctx, int n_sets, const ygz_st
     A.pairs = ygz_at<BowPair>(dev, o_pairs); A.bow_cnt = ygz_at<int32_t>(dev, o_bcnt);
     A.match12 = ygz_at<int32_t>(dev, o_m12); A.outcome = ygz_at<int32_t>(dev, o_oc);
     A.holder = ygz_at<int32_t>(dev, o_hold); A.kp_point = ygz_at<int32_t>(dev, o_kpt); A.prior = ygz_at<int32_t>(dev, o_prior);
-    A.edge_of = ygz_at<int32_t>(dev, o_eof); A.out_outlier = dev + o_out; A.out_chi2 = ygz_at<double>(dev, o_chi2);
-    A.e_pw = ygz_at<double>(dev, o_epw); A.e_obs = ygz_at<double>(dev, o_eobs); A.e_level = ygz_at<int32_t>(dev, o_elvl); A.e_kind = dev + o_ekind;
-    A.e_outlier = dev + o_eout; A.e_chi2 = ygz_at<const double>(dev, o_echi);
-    A.edge_end = ygz_at<int32_t>(dev, o_end); A.status = ygz_at<int32_t>(dev, o_status); A.counts = ygz_at<int32_t>(dev, o_counts);
-    A.rot = ygz_at<int32_t>(dev, o_rot); A.inliers = ygz_at<const int32_t>(dev, o_inl);
+    ygz_slot_edges_bind(A.E, dev, PB, o_out, o_chi2);
+    A.status = ygz_at<int32_t>(dev, o_status); A.counts = ygz_at<int32_t>(dev, o_counts);
+    A.rot = ygz_at<int32_t>(dev, o_rot); A.inliers = ygz_at<const int32_t>(dev, PB.inliers);
     A.bf = K4[0] * p.baseline;
     A.cells = ctx->cells; A.n_frames = n_frames; A.n_slots = (int)D; A.n_kf = n_keyframes; A.slot_min = slot_min; A.span = (int)SP;
     A.check_orientation = p.check_orientation ? 1 : 0; A.min_matches = p.min_matches; A.min_inliers = p.min_inliers;
@@ -404,17 +346,8 @@ int ygz_hip_stereo_ref_keyframe_slots(ygz_hip_ctx *ctx, int n_sets, const ygz_st
 
     PoptArgs G;
     memset(&G, 0, sizeof G);
-    G.off = ygz_at<const int32_t>(dev, o_off); G.end = A.edge_end; G.pw = A.e_pw; G.obs = A.e_obs; G.level = A.e_level; G.kind = A.e_kind;
-    G.poses = ygz_at<double>(dev, o_pose); G.chi2 = ygz_at<double>(dev, o_echi);
-    G.cost_initial = ygz_at<double>(dev, o_rci); G.cost_final = ygz_at<double>(dev, o_rcf); G.lambda = ygz_at<double>(dev, o_rlam);
-    G.status = ygz_at<int32_t>(dev, o_rst); G.iterations = ygz_at<int32_t>(dev, o_rit);
-    G.inliers = ygz_at<int32_t>(dev, o_inl); G.rounds_run = ygz_at<int32_t>(dev, o_run); G.outlier = dev + o_eout;
-    for (int k = 0; k < 4; ++k) G.K[k] = K4[k];
-    G.K[4] = K4[0] * p.baseline;
-    G.d2m = q.chi2_mono; G.d2s = q.chi2_stereo; G.dm = sqrt(q.chi2_mono); G.ds = sqrt(q.chi2_stereo);
-    G.min_rel_decrease = q.min_rel_decrease;
-    G.rounds = q.rounds; G.iters = q.iterations; G.max_trials = q.max_trials; G.robust_rounds = q.robust_rounds;
-    G.min_edges = q.min_edges; G.min_inliers = q.min_inliers;
+    ygz_popt_bind(G, dev, PB, o_off, o_pose);
+    ygz_popt_set_params(G, K4, p.baseline, p.pose);
 
     int widest = ctx->cells > n_frames ? ctx->cells : n_frames;
     if ((int)SP > widest) widest = (int)SP;
@@ -433,13 +366,7 @@ int ygz_hip_stereo_ref_keyframe_slots(ygz_hip_ctx *ctx, int n_sets, const ygz_st
     memcpy(T_out, up + o_pose, F * 56);
     if (status) memcpy(status, up + o_status, F * 4);
     if (counts) memcpy(counts, up + o_counts, F * 32);
-    if (inliers) memcpy(inliers, up + o_inl, F * 4);
-    if (rounds_run) memcpy(rounds_run, up + o_run, F * 4);
-    if (round_status) memcpy(round_status, up + o_rst, R8 * 4);
-    if (round_iterations) memcpy(round_iterations, up + o_rit, R8 * 4);
-    if (round_cost_initial) memcpy(round_cost_initial, up + o_rci, R8 * 8);
-    if (round_cost_final) memcpy(round_cost_final, up + o_rcf, R8 * 8);
-    if (round_lambda) memcpy(round_lambda, up + o_rlam, R8 * 8);
+    PB.copy_results(up, F, inliers, rounds_run, round_status, round_iterations, round_cost_initial, round_cost_final, round_lambda);
     if (rot) memcpy(rot, up + o_rot, F * 132);
     if (prior) memcpy(prior, up + o_prior, NK * 4);
     if (kp_point) memcpy(kp_point, up + o_kpt, NK * 4);

@@ -20,6 +20,7 @@
 #include <math.h>
 #include <string.h>
 #pragma clang fp contract(off)
+#include "slot_pose_dev.h"              // the rotation bin and the three maxima of the histogram: svo.hip and srk.hip apply the same rule
 
 #define ST_LANES     256
 #define ST_TILE      256
@@ -181,12 +182,6 @@ __global__ __launch_bounds__(ST_LANES) void k_strack_search(const StIn *__restri
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------------------
-static bool strack_finite(const double *v, size_t n)
-{
-    for (size_t i = 0; i < n; ++i) if (!isfinite(v[i])) return false;
-    return true;
-}
-
 // steps 8 and 9 of tests/strack_ref.c over one problem's lists: the claim walk, then the rotation histogram.  counts [4], rot [33]
 static void strack_resolve(const ygz_strack_points &S, const ygz_strack_problem &B, const ygz_strack_params &p, const uint32_t *keys,
                            const int32_t *n_cand, const int32_t *why, int32_t *m_, int32_t *d_, int32_t *oc, int32_t *counts, int32_t *rot,
@@ -221,28 +216,15 @@ static void strack_resolve(const ygz_strack_points &S, const ygz_strack_problem 
     int32_t hist[30], ind[3] = { -1, -1, -1 };
     for (int b = 0; b < 30; ++b) hist[b] = 0;
     if (B.mode == 0 && S.pt_angle && p.check_orientation) {
-        const float factor = 1.0f / 30;
         bin_.assign((size_t)n, -1);
         for (int i = 0; i < n; ++i) {
             if (m_[i] < 0) continue;
-            float r = (float)(S.pt_angle[i] - B.kp_angle[m_[i]]);
-            if (r < 0) r += 360;
-            const float fb = r * factor;
-            int bin = (int)((double)fb + 0.5);                      // round of a value >= 0
-            if (bin == 30) bin = 0;
-            if (!(fb >= 0) || bin < 0 || bin >= 30) continue;
+            const int bin = ygz_rot_bin_of((float)(S.pt_angle[i] - B.kp_angle[m_[i]]));      // the host angles are doubles
+            if (bin < 0) continue;
             bin_[(size_t)i] = bin;
             hist[bin]++;
         }
-        int max1 = 0, max2 = 0, max3 = 0;
-        for (int b = 0; b < 30; ++b) {
-            const int s = hist[b];
-            if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind[2] = ind[1]; ind[1] = ind[0]; ind[0] = b; }
-            else if (s > max2) { max3 = max2; max2 = s; ind[2] = ind[1]; ind[1] = b; }
-            else if (s > max3) { max3 = s; ind[2] = b; }
-        }
-        if ((float)max2 < 0.1f * (float)max1) { ind[1] = -1; ind[2] = -1; }
-        else if ((float)max3 < 0.1f * (float)max1) { ind[2] = -1; }
+        ygz_rot_top3(hist, ind);
         for (int i = 0; i < n; ++i) {
             if (m_[i] < 0) continue;
             const int b = bin_[(size_t)i];
@@ -297,20 +279,20 @@ int ygz_hip_stereo_track_search(ygz_hip_ctx *ctx, int n_sets, const ygz_strack_p
     if (params) p = *params; else ygz_hip_default_strack_params(&p);
     if (!isfinite(p.baseline) || !isfinite(p.ratio) || !isfinite(p.r_near) || !isfinite(p.r_wide) || !isfinite(p.cos_near)) return YGZ_E_INVALID;
     if (!(p.baseline > 0) || !(p.ratio > 0) || !(p.r_near > 0) || !(p.r_wide > 0) || p.th_dist < 0 || p.th_dist > 256) return YGZ_E_INVALID;
-    if (!strack_finite(K4, 4) || !(K4[0] > 0) || !(K4[1] > 0)) return YGZ_E_INVALID;
+    if (!ygz_all_finite(K4, 4) || !(K4[0] > 0) || !(K4[1] > 0)) return YGZ_E_INVALID;
     for (int s = 0; s < n_sets; ++s) {
         const size_t n = (size_t)sets[s].n_pt;
         if (!n) continue;
-        if (!strack_finite(sets[s].pw, 3 * n)) return YGZ_E_INVALID;
-        if (sets[s].pt_dmax && !strack_finite(sets[s].pt_dmax, n)) return YGZ_E_INVALID;
-        if (sets[s].pt_normal && !strack_finite(sets[s].pt_normal, 3 * n)) return YGZ_E_INVALID;
-        if (sets[s].pt_angle && !strack_finite(sets[s].pt_angle, n)) return YGZ_E_INVALID;
+        if (!ygz_all_finite(sets[s].pw, 3 * n)) return YGZ_E_INVALID;
+        if (sets[s].pt_dmax && !ygz_all_finite(sets[s].pt_dmax, n)) return YGZ_E_INVALID;
+        if (sets[s].pt_normal && !ygz_all_finite(sets[s].pt_normal, 3 * n)) return YGZ_E_INVALID;
+        if (sets[s].pt_angle && !ygz_all_finite(sets[s].pt_angle, n)) return YGZ_E_INVALID;
     }
     for (int q = 0; q < n_problems; ++q) {
         const ygz_strack_problem &b = problems[q];
-        if (!strack_finite(b.T, 7)) return YGZ_E_INVALID;
-        if (b.kp_ur && !strack_finite(b.kp_ur, (size_t)b.n_kp)) return YGZ_E_INVALID;
-        if (b.kp_angle && !strack_finite(b.kp_angle, (size_t)b.n_kp)) return YGZ_E_INVALID;
+        if (!ygz_all_finite(b.T, 7)) return YGZ_E_INVALID;
+        if (b.kp_ur && !ygz_all_finite(b.kp_ur, (size_t)b.n_kp)) return YGZ_E_INVALID;
+        if (b.kp_angle && !ygz_all_finite(b.kp_angle, (size_t)b.n_kp)) return YGZ_E_INVALID;
     }
     if (!ctx) return YGZ_E_INVALID;
     const int L = ctx->prm.pyramid_levels;

@@ -23,10 +23,10 @@
 #include <math.h>
 #include <string.h>
 #pragma clang fp contract(off)
-#include "ur_dev.h"                     // the right column of a resident keypoint: slm.hip gathers the same way
+#include "ur_dev.h"                     // the right column of a resident keypoint: slm.hip and srk.hip gather the same way
+#include "slot_pose_dev.h"              // the edges of k_pose_opt and the rotation rule: slm.hip and srk.hip compact and scatter the same way
 
 #define SV_LANES      256
-#define SV_MAX_CELLS  32768              // the taken bitmap of a pair: 4 KiB of LDS
 
 struct SvoDev {
     // the resident keypoints [max_frames][cells]
@@ -41,22 +41,18 @@ struct SvoDev {
     StProbDev *probs1, *probs2;                      // [n_pairs]: the first pass, the retry
     // per (pair, point) [n_pairs][cells]
     uint32_t *keys; int32_t *n_cand, *n_gated, *level, *reason; double *proj;
-    int32_t *match, *dist, *outcome, *edge_of;
-    uint8_t *out_outlier; double *out_chi2;
-    // the edges of pair p: [p * cells, edge_end[p])
-    double *e_pw, *e_obs; int32_t *e_level; uint8_t *e_kind; const uint8_t *e_outlier; const double *e_chi2;
-    int32_t *edge_end, *retry, *status, *counts, *rot;
+    int32_t *match, *dist, *outcome;
+    SlotEdges E;                                     // the edges of pair p: [p * cells, edge_end[p])
+    int32_t *retry, *status, *counts, *rot;
     double K4[4], bf, th;
     int cells, n_pairs, n_slots, th_dist, check_orientation, min_matches;
 };
-
-__device__ __forceinline__ int sv_count(const SvoDev &A, int slot) { return min(max(A.n_kp[slot], 0), A.cells); }
 
 __global__ __launch_bounds__(SV_LANES) void k_svo_gather(SvoDev A)
 {
     const int d = blockIdx.y, i = blockIdx.x * SV_LANES + threadIdx.x;
     const int s = A.slots[d];
-    if (i < sv_count(A, s)) {
+    if (i < ygz_slot_count(A.n_kp, s, A.cells)) {
         const size_t g = (size_t)s * A.cells + i, o = (size_t)d * A.cells + i;
         const double u = A.kp_px[2 * g], v = A.kp_px[2 * g + 1], z = A.kp_depth[g];
         const bool has = ygz_kp_has_depth(A.kp_has_mp[g], z);          // a NaN depth compares false
@@ -77,12 +73,12 @@ __global__ __launch_bounds__(SV_LANES) void k_svo_gather(SvoDev A)
         const size_t oL = (size_t)L * A.cells, oC = (size_t)C * A.cells, gL = (size_t)A.pair_dl[i] * A.cells, gC = (size_t)A.pair_dc[i] * A.cells;
         StSetDev S;
         S.pw = A.g_pw + 3 * gL; S.pt_desc = A.kp_desc + 8 * oL; S.pt_level = A.kp_level + oL; S.pt_dmax = nullptr; S.pt_normal = nullptr;
-        S.n_pt = sv_count(A, L); S.pad_ = 0;
+        S.n_pt = ygz_slot_count(A.n_kp, L, A.cells); S.pad_ = 0;
         A.sets[i] = S;
         StProbDev P;
         P.kp_px = A.kp_px + 2 * oC; P.kp_level = A.kp_level + oC; P.kp_desc = A.kp_desc + 8 * oC; P.kp_ur = A.g_ur + gC; P.kp_taken = nullptr;
         P.pt_skip = A.g_skip + gL;
-        P.n_kp = sv_count(A, C); P.set = i; P.pt_off = i * A.cells; P.mode = 0; P.direction = A.direction[i]; P.pad_ = 0;
+        P.n_kp = ygz_slot_count(A.n_kp, C, A.cells); P.set = i; P.pt_off = i * A.cells; P.mode = 0; P.direction = A.direction[i]; P.pad_ = 0;
         P.th = A.th;
 #pragma unroll
         for (int k = 0; k < 7; ++k) P.T[k] = A.poses[7 * (size_t)i + k];
@@ -95,23 +91,11 @@ __global__ __launch_bounds__(SV_LANES) void k_svo_gather(SvoDev A)
     }
 }
 
-// the bin of a match's rotation (step 9 of tests/strack_ref.c), or -1
-__device__ __forceinline__ int sv_bin(float pt_angle, float kp_angle)
-{
-    float r = (float)((double)pt_angle - (double)kp_angle);
-    if (r < 0) r += 360;
-    const float fb = r * (1.0f / 30);
-    if (!(fb >= 0) || !(fb < 64.0f)) return -1;                          // a bin past 29 has no counter; nothing is converted that an int cannot hold
-    int bin = (int)((double)fb + 0.5);                                   // round of a value >= 0
-    if (bin == 30) bin = 0;
-    return bin < 30 ? bin : -1;
-}
-
 enum { SV_N_DEPTH = 0, SV_N_SEARCHED, SV_N_OVER, SV_N_ROT, SV_N_CLAIMED, SV_N_COUNTERS };
 
 __global__ __launch_bounds__(SV_LANES) void k_svo_resolve(SvoDev A, int pass)
 {
-    __shared__ uint32_t s_taken[SV_MAX_CELLS / 32];
+    __shared__ uint32_t s_taken[YGZ_SLOT_MAX_CELLS / 32];
     __shared__ uint4 s_key[SV_LANES][2];
     __shared__ uint32_t s_pick[SV_LANES];
     __shared__ int s_hist[30], s_ind[3], s_cnt[SV_N_COUNTERS], s_wave[SV_LANES / 64];
@@ -185,29 +169,18 @@ __global__ __launch_bounds__(SV_LANES) void k_svo_resolve(SvoDev A, int pass)
         for (int i = tid; i < n_pt; i += SV_LANES) {
             const int m = A.match[base + i];
             if (m < 0 || m >= n_kp) continue;
-            const int bin = sv_bin(A.kp_angle[oL + i], A.kp_angle[oC + m]);
+            const int bin = ygz_rot_bin(A.kp_angle[oL + i], A.kp_angle[oC + m]);
             if (bin >= 0) atomicAdd(&s_hist[bin], 1);
         }
         __syncthreads();
-        if (tid == 0) {
-            int max1 = 0, max2 = 0, max3 = 0, i0 = -1, i1 = -1, i2 = -1;
-            for (int b = 0; b < 30; ++b) {
-                const int s = s_hist[b];
-                if (s > max1) { max3 = max2; max2 = max1; max1 = s; i2 = i1; i1 = i0; i0 = b; }
-                else if (s > max2) { max3 = max2; max2 = s; i2 = i1; i1 = b; }
-                else if (s > max3) { max3 = s; i2 = b; }
-            }
-            if ((float)max2 < 0.1f * (float)max1) { i1 = -1; i2 = -1; }
-            else if ((float)max3 < 0.1f * (float)max1) { i2 = -1; }
-            s_ind[0] = i0; s_ind[1] = i1; s_ind[2] = i2;
-        }
+        if (tid == 0) ygz_rot_top3(s_hist, s_ind);
         __syncthreads();
         const int i0 = s_ind[0], i1 = s_ind[1], i2 = s_ind[2];
         for (int i = tid; i < n_pt; i += SV_LANES) {
             const size_t g = base + i;
             const int m = A.match[g];
             if (m < 0 || m >= n_kp) continue;
-            const int bin = sv_bin(A.kp_angle[oL + i], A.kp_angle[oC + m]);
+            const int bin = ygz_rot_bin(A.kp_angle[oL + i], A.kp_angle[oC + m]);
             if (bin >= 0 && (bin == i0 || bin == i1 || bin == i2)) continue;
             A.match[g] = -1; A.dist[g] = -1; A.outcome[g] = 4; ++c_rot;     // the keypoint stays claimed
         }
@@ -240,52 +213,29 @@ __global__ __launch_bounds__(SV_LANES) void k_svo_resolve(SvoDev A, int pass)
     // ---- the edges: the matched points in point order (none for a pair that retries or has failed)
     const bool edges = !again && status == 0;
     int running = 0;
-    const int lane = tid & 63, wv = tid >> 6;
     for (int c0 = 0; c0 < cells; c0 += SV_LANES) {
         const int i = c0 + tid;
         const int m = (edges && i < n_pt) ? A.match[base + i] : -1;
         const bool has = m >= 0 && m < n_kp;
-        const unsigned long long bal = __ballot(has);
-        if (lane == 0) s_wave[wv] = __popcll(bal);
-        __syncthreads();
-        int before = running, total = 0;
-#pragma unroll
-        for (int w = 0; w < SV_LANES / 64; ++w) { const int c = s_wave[w]; if (w < wv) before += c; total += c; }
+        const int e = ygz_edge_slot<SV_LANES>(has, running, s_wave);
         if (has) {
-            const int e = before + __popcll(bal & ((1ull << lane) - 1ull));
-            const size_t ge = base + e;
-            const double *X = A.sets[p].pw + 3 * (size_t)i;
-            A.e_pw[3 * ge] = X[0]; A.e_pw[3 * ge + 1] = X[1]; A.e_pw[3 * ge + 2] = X[2];
-            const double ur = P.kp_ur[m];
-            A.e_obs[3 * ge] = P.kp_px[2 * (size_t)m]; A.e_obs[3 * ge + 1] = P.kp_px[2 * (size_t)m + 1]; A.e_obs[3 * ge + 2] = ur;
-            A.e_level[ge] = P.kp_level[m];
-            A.e_kind[ge] = ur >= 0 ? 2 : 1;
-            A.edge_of[base + i] = e;
-        } else if (i < cells) A.edge_of[base + i] = -1;
-        running += total;
+            ygz_edge_write(A.E, base + e, A.sets[p].pw + 3 * (size_t)i, P.kp_px + 2 * (size_t)m, P.kp_ur[m], P.kp_level[m]);
+            A.E.edge_of[base + i] = e;
+        } else if (i < cells) A.E.edge_of[base + i] = -1;
         __syncthreads();
     }
-    if (tid == 0) A.edge_end[p] = (int32_t)base + running;
+    if (tid == 0) A.E.edge_end[p] = (int32_t)base + running;
 }
 
 __global__ __launch_bounds__(SV_LANES) void k_svo_scatter(SvoDev A)
 {
     const int p = blockIdx.y, i = blockIdx.x * SV_LANES + threadIdx.x;
     if (i >= A.cells) return;
-    const size_t base = (size_t)p * A.cells, g = base + i;
-    const int e = A.edge_of[g];
-    const bool has = e >= 0 && e < A.cells;
-    A.out_outlier[g] = has ? A.e_outlier[base + e] : 0;
-    A.out_chi2[g] = has ? A.e_chi2[base + e] : -1.0;
+    const size_t base = (size_t)p * A.cells;
+    ygz_edge_scatter(A.E, base, base + i, A.cells);
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------------------
-static bool svo_finite(const double *v, size_t n)
-{
-    for (size_t i = 0; i < n; ++i) if (!isfinite(v[i])) return false;
-    return true;
-}
-
 // StereoTracker's motion direction for the last camera at the identity: t_lc = -R_c^T t_c, +1 when its z is above the baseline, -1 below minus it
 static int svo_direction(const double *T, double baseline)
 {
@@ -319,13 +269,9 @@ int ygz_hip_stereo_odometry_slots(ygz_hip_ctx *ctx, int n_pairs, const int32_t *
     if (params) p = *params; else ygz_hip_default_svo_params(&p);
     if (!isfinite(p.baseline) || !isfinite(p.th) || !(p.baseline > 0) || !(p.th > 0) || p.th_dist < 0 || p.th_dist > 256 || p.min_matches < 0)
         return YGZ_E_INVALID;
-    const ygz_pose_opt_params &q = p.pose;
-    if (!isfinite(q.chi2_mono) || !isfinite(q.chi2_stereo) || !isfinite(q.min_rel_decrease)) return YGZ_E_INVALID;
-    if (!(q.chi2_mono > 0.0) || !(q.chi2_stereo > 0.0) || q.rounds < 1 || q.rounds > YGZ_POPT_MAX_ROUNDS || q.iterations < 1 ||
-        q.iterations > YGZ_POPT_MAX_STEPS || q.max_trials < 1 || q.max_trials > YGZ_POPT_MAX_STEPS)
-        return YGZ_E_INVALID;
+    if (!ygz_pose_params_ok(p.pose)) return YGZ_E_INVALID;
     const size_t Q = (size_t)n_pairs;
-    if (T_init && !svo_finite(T_init, 7 * Q)) return YGZ_E_INVALID;
+    if (T_init && !ygz_all_finite(T_init, 7 * Q)) return YGZ_E_INVALID;
     for (int k = 0; k < n_pairs; ++k) {
         if (direction && (direction[k] < -1 || direction[k] > 1)) return YGZ_E_INVALID;
         if (last_slot[k] < 0 || cur_slot[k] < 0 || last_slot[k] == cur_slot[k]) return YGZ_E_INVALID;
@@ -335,7 +281,7 @@ int ygz_hip_stereo_odometry_slots(ygz_hip_ctx *ctx, int n_pairs, const int32_t *
         if (last_slot[k] >= ctx->prm.max_frames || cur_slot[k] >= ctx->prm.max_frames) return YGZ_E_INVALID;
     const int L = ctx->prm.pyramid_levels;
     if (L < 1 || L > YGZ_MAX_LEVELS) return YGZ_E_INVALID;
-    if (ctx->cells > SV_MAX_CELLS) return YGZ_E_CAPACITY;
+    if (ctx->cells > YGZ_SLOT_MAX_CELLS) return YGZ_E_CAPACITY;
     for (int k = 0; k < n_pairs; ++k)
         if (!ctx->pyr_valid[last_slot[k]] || !ctx->pyr_valid[cur_slot[k]]) return YGZ_E_STATE;
     if (!ctx->kp_depth || !ctx->kp_has_mp) return YGZ_E_STATE;
@@ -345,12 +291,10 @@ int ygz_hip_stereo_odometry_slots(ygz_hip_ctx *ctx, int n_pairs, const int32_t *
     // the distinct slots of the call, in the order they first appear
     std::vector<int32_t> slots, where((size_t)ctx->prm.max_frames, -1), dl(Q), dc(Q), dir(Q);
     for (int k = 0; k < n_pairs; ++k) {
-        const int32_t two[2] = { last_slot[k], cur_slot[k] };
-        for (int e = 0; e < 2; ++e)
-            if (where[(size_t)two[e]] < 0) { where[(size_t)two[e]] = (int32_t)slots.size(); slots.push_back(two[e]); }
-        dl[(size_t)k] = where[(size_t)two[0]]; dc[(size_t)k] = where[(size_t)two[1]];
+        dl[(size_t)k] = ygz_distinct_slot(slots, where, last_slot[k]);
+        dc[(size_t)k] = ygz_distinct_slot(slots, where, cur_slot[k]);
     }
-    const size_t D = slots.size(), Cn = (size_t)ctx->cells, N = Q * Cn, R8 = Q * YGZ_POPT_MAX_ROUNDS;
+    const size_t D = slots.size(), Cn = (size_t)ctx->cells, N = Q * Cn;
 
     // up: [in | slots | the pairs' tables | poses), back: [poses | the small outputs | the per-point outputs), then what stays on the device
     YgzBlobLayout B;
@@ -358,8 +302,8 @@ int ygz_hip_stereo_odometry_slots(ygz_hip_ctx *ctx, int n_pairs, const int32_t *
     const size_t o_pl = B.add_n<int32_t>(Q), o_pc = B.add_n<int32_t>(Q), o_dir = B.add_n<int32_t>(Q), o_off = B.add_n<int32_t>(Q);
     const size_t o_pose = B.add_n<double>(Q * 7), in_end = B.end;
     const size_t o_status = B.add_n<int32_t>(Q), o_counts = B.add_n<int32_t>(Q * 8), o_rot = B.add_n<int32_t>(Q * 33);
-    const size_t o_inl = B.add_n<int32_t>(Q), o_run = B.add_n<int32_t>(Q), o_rst = B.add_n<int32_t>(R8), o_rit = B.add_n<int32_t>(R8);
-    const size_t o_rci = B.add_n<double>(R8), o_rcf = B.add_n<double>(R8), o_rlam = B.add_n<double>(R8);
+    YgzPoseBlock PB;
+    PB.add_results(B, Q);
     size_t back_end = B.end;
     // the per-point outputs, fetched up to the last one the caller asked for
     const size_t o_match = B.add_n<int32_t>(N); if (match) back_end = B.end;
@@ -372,9 +316,9 @@ int ygz_hip_stereo_odometry_slots(ygz_hip_ctx *ctx, int n_pairs, const int32_t *
     const size_t o_nc = B.add_n<int32_t>(N); if (n_cand) back_end = B.end;
     const size_t o_ng = B.add_n<int32_t>(N); if (n_gated) back_end = B.end;
     const size_t o_proj = B.add_n<double>(N * 3); if (proj) back_end = B.end;
-    const size_t o_keys = B.add_n<uint4>(N * 2), o_eof = B.add_n<int32_t>(N);
-    const size_t o_epw = B.add_n<double>(N * 3), o_eobs = B.add_n<double>(N * 3), o_elvl = B.add_n<int32_t>(N), o_ekind = B.add_n<uint8_t>(N);
-    const size_t o_eout = B.add_n<uint8_t>(N), o_echi = B.add_n<double>(N), o_end = B.add_n<int32_t>(Q), o_retry = B.add_n<int32_t>(Q);
+    const size_t o_keys = B.add_n<uint4>(N * 2);
+    PB.add_edges(B, Q, Cn);
+    const size_t o_retry = B.add_n<int32_t>(Q);
     const size_t o_sets = B.add_n<StSetDev>(Q + 1), o_p1 = B.add_n<StProbDev>(Q), o_p2 = B.add_n<StProbDev>(Q);
     const size_t o_gpw = B.add_n<double>(D * Cn * 3), o_gur = B.add_n<double>(D * Cn), o_gskip = B.add_n<uint8_t>(D * Cn), total = B.end;
     YgzBlob blob;
@@ -411,10 +355,8 @@ int ygz_hip_stereo_odometry_slots(ygz_hip_ctx *ctx, int n_pairs, const int32_t *
     A.keys = ygz_at<uint32_t>(dev, o_keys); A.n_cand = ygz_at<int32_t>(dev, o_nc); A.n_gated = ygz_at<int32_t>(dev, o_ng);
     A.level = ygz_at<int32_t>(dev, o_lvl); A.reason = ygz_at<int32_t>(dev, o_why); A.proj = ygz_at<double>(dev, o_proj);
     A.match = ygz_at<int32_t>(dev, o_match); A.dist = ygz_at<int32_t>(dev, o_dist); A.outcome = ygz_at<int32_t>(dev, o_oc);
-    A.edge_of = ygz_at<int32_t>(dev, o_eof); A.out_outlier = dev + o_out; A.out_chi2 = ygz_at<double>(dev, o_chi2);
-    A.e_pw = ygz_at<double>(dev, o_epw); A.e_obs = ygz_at<double>(dev, o_eobs); A.e_level = ygz_at<int32_t>(dev, o_elvl); A.e_kind = dev + o_ekind;
-    A.e_outlier = dev + o_eout; A.e_chi2 = ygz_at<const double>(dev, o_echi);
-    A.edge_end = ygz_at<int32_t>(dev, o_end); A.retry = ygz_at<int32_t>(dev, o_retry); A.status = ygz_at<int32_t>(dev, o_status);
+    ygz_slot_edges_bind(A.E, dev, PB, o_out, o_chi2);
+    A.retry = ygz_at<int32_t>(dev, o_retry); A.status = ygz_at<int32_t>(dev, o_status);
     A.counts = ygz_at<int32_t>(dev, o_counts); A.rot = ygz_at<int32_t>(dev, o_rot);
     for (int k = 0; k < 4; ++k) A.K4[k] = in.K4[k];
     A.bf = in.bf; A.th = p.th;
@@ -423,17 +365,8 @@ int ygz_hip_stereo_odometry_slots(ygz_hip_ctx *ctx, int n_pairs, const int32_t *
 
     PoptArgs G;
     memset(&G, 0, sizeof G);
-    G.off = ygz_at<const int32_t>(dev, o_off); G.end = A.edge_end; G.pw = A.e_pw; G.obs = A.e_obs; G.level = A.e_level; G.kind = A.e_kind;
-    G.poses = A.poses; G.chi2 = ygz_at<double>(dev, o_echi);
-    G.cost_initial = ygz_at<double>(dev, o_rci); G.cost_final = ygz_at<double>(dev, o_rcf); G.lambda = ygz_at<double>(dev, o_rlam);
-    G.status = ygz_at<int32_t>(dev, o_rst); G.iterations = ygz_at<int32_t>(dev, o_rit);
-    G.inliers = ygz_at<int32_t>(dev, o_inl); G.rounds_run = ygz_at<int32_t>(dev, o_run); G.outlier = dev + o_eout;
-    for (int k = 0; k < 4; ++k) G.K[k] = in.K4[k];
-    G.K[4] = in.K4[0] * p.baseline;
-    G.d2m = q.chi2_mono; G.d2s = q.chi2_stereo; G.dm = sqrt(q.chi2_mono); G.ds = sqrt(q.chi2_stereo);
-    G.min_rel_decrease = q.min_rel_decrease;
-    G.rounds = q.rounds; G.iters = q.iterations; G.max_trials = q.max_trials; G.robust_rounds = q.robust_rounds;
-    G.min_edges = q.min_edges; G.min_inliers = q.min_inliers;
+    ygz_popt_bind(G, dev, PB, o_off, o_pose);
+    ygz_popt_set_params(G, in.K4, p.baseline, p.pose);
 
     const unsigned bx = (unsigned)ygz_div_up(ctx->cells, SV_LANES), bt = (unsigned)ygz_div_up(ctx->cells > n_pairs ? ctx->cells : n_pairs, SV_LANES);
     const dim3 search_grid((unsigned)ygz_div_up(ctx->cells, ST_DEV_LANES), (unsigned)n_pairs);
@@ -450,13 +383,7 @@ int ygz_hip_stereo_odometry_slots(ygz_hip_ctx *ctx, int n_pairs, const int32_t *
     if (status) memcpy(status, up + o_status, Q * 4);
     if (counts) memcpy(counts, up + o_counts, Q * 32);
     if (rot) memcpy(rot, up + o_rot, Q * 132);
-    if (inliers) memcpy(inliers, up + o_inl, Q * 4);
-    if (rounds_run) memcpy(rounds_run, up + o_run, Q * 4);
-    if (round_status) memcpy(round_status, up + o_rst, R8 * 4);
-    if (round_iterations) memcpy(round_iterations, up + o_rit, R8 * 4);
-    if (round_cost_initial) memcpy(round_cost_initial, up + o_rci, R8 * 8);
-    if (round_cost_final) memcpy(round_cost_final, up + o_rcf, R8 * 8);
-    if (round_lambda) memcpy(round_lambda, up + o_rlam, R8 * 8);
+    PB.copy_results(up, Q, inliers, rounds_run, round_status, round_iterations, round_cost_initial, round_cost_final, round_lambda);
     if (match) memcpy(match, up + o_match, N * 4);
     if (outlier) memcpy(outlier, up + o_out, N);
     if (chi2) memcpy(chi2, up + o_chi2, N * 8);

@@ -1,4 +1,4 @@
-// The right column of a resident keypoint from its depth, for the translation units that gather resident slots: svo.hip and slm.hip.
+// The right column of a resident keypoint from its depth, for the translation units that gather resident slots: svo.hip, slm.hip and srk.hip.
 // FP64, uncontracted: the including file sets `#pragma clang fp contract(off)` before it uses these.
 #pragma once
 #include "ygz_internal.h"
