@@ -52,10 +52,11 @@ def test_public_surface():
     mk = open(os.path.join(PKG, "host", "Makefile")).read()
     assert mk.count("ygz_slm.cpp") == 2
     host = re.sub(r"//[^\n]*", "", open(os.path.join(PKG, "host", "ygz_slm.cpp")).read())
-    # one entry point, called from one place; the slots are filled the way ygz_svo.cpp does; no point and no keyframe is made, and the
-    # host-array calls are not used
-    assert host.count("ygz_hip_stereo_local_map_slots(") == 1 and host.count("ygz_hip_describe_given_angle(") == 1
-    assert host.count("ygz_hip_set_keypoint_depths(") == 1
+    # one entry point, called from one place; the slots are filled by the shared loader, called from one place (test_svo_surface_build.py
+    # holds the loader itself); the point set goes through the shared append; no point and no keyframe is made, and the host-array calls are
+    # not used
+    assert host.count("ygz_hip_stereo_local_map_slots(") == 1 and host.count("load_slots(") == 1
+    assert host.count("ygz_hip_describe_given_angle(") == 0 and host.count("ygz_hip_set_keypoint_depths(") == 0 and host.count("PointAttributes(") == 0
     for word in ("Memory::", "CreateMapPoint", "RegisterKeyFrame", "ygz_hip_stereo_track_search", "ygz_hip_optimize_pose_stereo", "StereoTracker",
                  "PoseOptimizer"):
         assert word not in host, word

@@ -54,8 +54,15 @@ def test_public_surface():
     mk = open(os.path.join(PKG, "host", "Makefile")).read()
     assert mk.count("ygz_strack.cpp") == 2
     host = re.sub(r"//[^\n]*", "", open(os.path.join(PKG, "host", "ygz_strack.cpp")).read())
-    # one entry point, called from one place; the other classes are used, not changed; _last_seen belongs to the mapper
-    assert host.count("ygz_hip_stereo_track_search(") == 1 and host.count("PointAttributes(") == 1 and host.count("opt.Optimize(") == 2
+    # one entry point, called from one place; the other classes are used, not changed; _last_seen belongs to the mapper; the point sets of
+    # this surface, of ygz_slm.cpp and of ygz_lfuse.cpp go through ONE gather in surface_share.cpp (ygz_proj.cpp defines the function and
+    # keeps its own rule for skipped points)
+    assert host.count("ygz_hip_stereo_track_search(") == 1 and host.count("PointAttributes(") == 0 and host.count("opt.Optimize(") == 2
+    hostdir = os.path.join(PKG, "host")
+    calls = {f: re.sub(r"//[^\n]*", "", open(os.path.join(hostdir, f)).read()).count("PointAttributes(")
+             for f in os.listdir(hostdir) if f.endswith((".cpp", ".h")) and f != "ygz_proj.cpp"}
+    assert calls["surface_share.cpp"] == 1 and sum(calls.values()) == 1, calls
+    assert calls["ygz_slm.cpp"] == 0 and calls["ygz_lfuse.cpp"] == 0
     assert "_last_seen" not in host and "ygz_hip_search_by_projection" not in host and "ygz_hip_local_fuse_search" not in host
     for path in NEW_SOURCES:
         code = re.sub(r"//[^\n]*", "", open(path).read())

@@ -52,9 +52,9 @@ def test_public_surface():
     mk = open(os.path.join(PKG, "host", "Makefile")).read()
     assert mk.count("ygz_svo.cpp") == 2
     host = re.sub(r"//[^\n]*", "", open(os.path.join(PKG, "host", "ygz_svo.cpp")).read())
-    # one entry point, called from one place; the slots are filled the way ygz_host.cpp describes feature lists; no map is touched
-    assert host.count("ygz_hip_stereo_odometry_slots(") == 1 and host.count("ygz_hip_describe_given_angle(") == 1
-    assert host.count("ygz_hip_set_keypoint_depths(") == 1
+    # one entry point, called from one place; the slots are filled by the shared loader, called from one place; no map is touched
+    assert host.count("ygz_hip_stereo_odometry_slots(") == 1 and host.count("load_slots(") == 1
+    assert host.count("ygz_hip_describe_given_angle(") == 0 and host.count("ygz_hip_set_keypoint_depths(") == 0
     for word in ("_mappoint", "Memory::", "ygz_hip_stereo_track_search", "ygz_hip_optimize_pose_stereo", "_obs"):
         assert word not in host, word
     others = [f for f in os.listdir(os.path.join(PKG, "host")) if f.endswith(".cpp") and f != "ygz_svo.cpp"]
@@ -62,6 +62,22 @@ def test_public_surface():
     for path in NEW_SOURCES:
         code = re.sub(r"//[^\n]*", "", open(path).read())
         assert "getenv" not in code and "environ" not in code, path
+
+
+def test_slot_loading_is_written_once():
+    """host/surface_share.cpp alone puts feature lists and depths into slots (ygz_host.cpp keeps its own describe call for the detector); the
+    three slot trackers call its loader once each; good(const MapPoint *) is defined once under host/"""
+    hostdir = os.path.join(PKG, "host")
+    code = {f: re.sub(r"//[^\n]*", "", open(os.path.join(hostdir, f)).read()) for f in os.listdir(hostdir) if f.endswith((".cpp", ".h"))}
+    share = code["surface_share.cpp"] + code["surface_share.h"]
+    for call in ("ygz_hip_describe_given_angle(", "ygz_hip_set_keypoint_depths("):
+        assert share.count(call) == 1 and code["surface_share.cpp"].count(call) == 1, call
+        assert {f for f in code if call in code[f]} <= {"surface_share.cpp", "ygz_host.cpp"}, call
+    for f in ("ygz_svo.cpp", "ygz_slm.cpp", "ygz_srk.cpp"):
+        assert code[f].count("load_slots(") == 1, f
+    assert sum(c.count("good(const MapPoint") for c in code.values()) == 1 and code["surface_share.h"].count("good(const MapPoint") == 1
+    mk = open(os.path.join(hostdir, "Makefile")).read()
+    assert mk.count("surface_share.cpp") == 2 and mk.count("surface_share.h") == 1
 
 
 def test_symbols_are_bound_and_exported(hip_lib):

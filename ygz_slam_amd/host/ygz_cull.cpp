@@ -6,13 +6,14 @@
 #include "ygz/Algorithm/KeyFrameCulling.h"
 #include "ygz/hip/Runtime.h"
 #include "ygz_hip.h"
+#include "surface_share.h"
 #include <algorithm>
 
 namespace ygz {
 
 namespace {
 bool by_id(const Frame *a, const Frame *b) { return a->_keyframe_id < b->_keyframe_id; }
-bool good(const MapPoint *mp) { return mp && !mp->_bad; }
+using hip::good;
 
 void disconnect(Frame *k, const Frame *gone)
 {

@@ -8,6 +8,7 @@
 #include "ygz/Algorithm/LoopClosing.h"
 #include "ygz/hip/Runtime.h"
 #include "ygz_hip.h"
+#include "surface_share.h"
 #include <algorithm>
 #include <cstring>
 
@@ -15,7 +16,7 @@ namespace ygz {
 
 namespace {
 bool by_id(const Frame *a, const Frame *b) { return a->_keyframe_id < b->_keyframe_id; }
-bool good(const MapPoint *mp) { return mp && !mp->_bad; }
+using hip::good;
 
 // not bad, once each, by id
 vector<Frame *> universe_of(const vector<Frame *> &keyframes)

@@ -9,13 +9,14 @@
 #include "ygz/Algorithm/LoopClosing.h"
 #include "ygz/hip/Runtime.h"
 #include "ygz_hip.h"
+#include "surface_share.h"
 #include <algorithm>
 #include <cstring>
 
 namespace ygz {
 
 namespace {
-bool good(const MapPoint *mp) { return mp && !mp->_bad; }
+using hip::good;
 Frame *frame_of(unsigned long id, const Feature *f) { return f && f->_frame ? f->_frame : Memory::GetKeyFrame(id); }
 
 int index_in_frame(const Feature *f)
@@ -134,30 +135,19 @@ int StereoMapper::SearchInNeighbors(Frame *kf, Matcher &matcher)
 
     auto keypoints = [&](const Frame *f, Keypoints &a) -> bool {
         const size_t n = f->_features.size();
-        a.px.resize(2 * n); a.ur.resize(n); a.level.resize(n); a.desc.resize(32 * n);
+        if (n == 0 || !hip::keypoint_arrays(f, a.px, a.level, a.desc)) return false;
+        a.ur.resize(n);
         for (size_t i = 0; i < n; ++i) {
-            const Feature *ft = f->_features[i];
-            if (!ft || !ft->_desc.data || ft->_desc.rows * ft->_desc.cols * (int)ft->_desc.elemSize() < 32) return false;
-            a.px[2 * i] = ft->_pixel[0]; a.px[2 * i + 1] = ft->_pixel[1];
-            a.level[i] = std::max(ft->_level, 0);
             a.ur[i] = URight(f, i);
             if (!(a.ur[i] >= 0)) a.ur[i] = -1.0;
-            memcpy(&a.desc[32 * i], ft->_desc.data, 32);
         }
-        return n > 0;
+        return true;
     };
-    // a point set from candidates in order, each once; a point PointAttributes refuses is skipped
+    // a point set from candidates in order, each once; a point Matcher::PointAttributes refuses is skipped
     auto point_set = [&](const std::vector<MapPoint *> &cand, Search &s) {
         std::set<const MapPoint *> seen;
-        for (MapPoint *mp : cand) {
-            if (!good(mp) || !seen.insert(mp).second) continue;
-            Matcher::PointAttr a;
-            if (!Matcher::PointAttributes(mp, a)) continue;
-            s.points.push_back(mp);
-            for (int k = 0; k < 3; ++k) { s.pw.push_back(mp->_pos_world[k]); s.normal.push_back(a.normal[k]); }
-            s.dmax.push_back(a.dmax);
-            s.desc.insert(s.desc.end(), a.desc, a.desc + 32);
-        }
+        for (MapPoint *mp : cand)
+            if (good(mp) && seen.insert(mp).second) hip::append_point(s, mp);
     };
     ygz_lfuse_params prm;
     ygz_hip_default_lfuse_params(&prm);

@@ -4,6 +4,7 @@
 #include "ygz/Algorithm/PoseOptimizer.h"
 #include "ygz/hip/Runtime.h"
 #include "ygz_hip.h"
+#include "surface_share.h"
 
 namespace ygz {
 
@@ -78,11 +79,7 @@ void PoseOptimizer::OptimizeBatch(const std::vector<Frame *> &frames, const std:
             Feature *fea = f->_features[i];
             if (g >= (size_t)off[fi + 1] || edge[g] != fea) continue;
             _outliers[fi][i] = outlier[g];
-            fea->_bad = outlier[g] != 0;                            // as ba::OptimizeCurrentPoseOnly: _bad for the outliers, _depth for the inliers
-            if (!fea->_bad) {
-                fea->_depth = Frame::_camera->World2Camera(fea->_mappoint->_pos_world, f->_TCW)[2];
-                if (fea->_mappoint->_bad == false) fea->_mappoint->_cnt_found++;
-            }
+            if (hip::apply_verdict(f, fea, outlier[g] != 0) && fea->_mappoint->_bad == false) fea->_mappoint->_cnt_found++;
             ++g;
         }
     }

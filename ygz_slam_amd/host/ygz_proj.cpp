@@ -7,6 +7,7 @@
 #include "ygz/Algorithm/Matcher.h"
 #include "ygz/hip/Runtime.h"
 #include "ygz_hip.h"
+#include "surface_share.h"
 #include <algorithm>
 #include <cstring>
 
@@ -17,7 +18,7 @@ namespace {
 // its BoW searches
 const int kThLow = 50, kThHigh = 100;
 
-bool good(const MapPoint *mp) { return mp && !mp->_bad; }
+using hip::good;
 
 struct Problem {
     vector<double> kp_px, pw, dmax, normal;

@@ -1,13 +1,13 @@
 // ygz::StereoLocalMap (include/ygz/Algorithm/StereoLocalMap.h): nothing in the reference.  ORB-SLAM2's TrackLocalMap for any number of frames:
-// the point sets of the local keyframe lists are built on the host, the frames' feature lists and depths are put into their slots the way
-// ygz_svo.cpp does, then ONE entry point (ygz_hip_stereo_local_map_slots, ygz_slam_amd/csrc/slm.hip) searches, claims and optimises on the
-// device, and the frames and map points are edited from its result in frame order.  The spec is DESIGN.md section 28.  Every order goes by
-// index or list position, never by address.  Error conventions of the other surfaces: a failed call logs and returns 0, only a missing device
-// throws.
+// the point sets of the local keyframe lists are built on the host, the frames' feature lists and depths are put into their slots
+// (hip::load_slots, surface_share.h), then ONE entry point (ygz_hip_stereo_local_map_slots, ygz_slam_amd/csrc/slm.hip) searches, claims and
+// optimises on the device, and the frames and map points are edited from its result in frame order.  The spec is DESIGN.md section 28.
+// Every order goes by index or list position, never by address.  Error conventions of the other surfaces: a failed call logs and returns
+// 0, only a missing device throws.
 #include "ygz/Algorithm/StereoLocalMap.h"
-#include "ygz/Algorithm/Matcher.h"
 #include "ygz/hip/Runtime.h"
 #include "ygz_hip.h"
+#include "surface_share.h"
 #include <algorithm>
 #include <map>
 #include <set>
@@ -15,30 +15,17 @@
 namespace ygz {
 
 namespace {
-bool good(const MapPoint *mp) { return mp && !mp->_bad; }
+using hip::good;
 
-struct PointSet {
-    std::vector<MapPoint *> points;
-    std::map<const MapPoint *, int32_t> index;
-    std::vector<double> pw, dmax, normal;
-    std::vector<uint8_t> desc;
-};
+struct PointSet : hip::PointArrays { std::map<const MapPoint *, int32_t> index; };      // a point of the set -> its position
 
 void build_set(const std::vector<Frame *> &keyframes, PointSet &s)
 {
     std::set<const MapPoint *> seen;
     for (const Frame *kf : keyframes) {
         if (!kf) continue;
-        for (const Feature *f : kf->_features) {
-            if (!f || !good(f->_mappoint) || !seen.insert(f->_mappoint).second) continue;
-            Matcher::PointAttr a;
-            if (!Matcher::PointAttributes(f->_mappoint, a)) continue;
-            s.index[f->_mappoint] = (int32_t)s.points.size();
-            s.points.push_back(f->_mappoint);
-            for (int k = 0; k < 3; ++k) { s.pw.push_back(f->_mappoint->_pos_world[k]); s.normal.push_back(a.normal[k]); }
-            s.dmax.push_back(a.dmax);
-            s.desc.insert(s.desc.end(), a.desc, a.desc + 32);
-        }
+        for (const Feature *f : kf->_features)
+            if (f && good(f->_mappoint) && seen.insert(f->_mappoint).second && s.append(f->_mappoint)) s.index[f->_mappoint] = (int32_t)s.points.size() - 1;
     }
 }
 }
@@ -55,16 +42,12 @@ int StereoLocalMap::TrackLocalMap(const std::vector<Frame *> &frames, const std:
     hip::Runtime &rt = hip::Runtime::Get();
     ygz_hip_ctx *c = rt.ctx();
     const size_t cells = (size_t)rt.cells();
-    for (size_t k = 0; k < n; ++k) {
+    for (size_t k = 0; k < n; ++k)
         if (!frames[k] || !local_keyframes[k] || std::find(frames.begin(), frames.begin() + (long)k, frames[k]) != frames.begin() + (long)k) {
             LOG(ERROR) << "StereoLocalMap::TrackLocalMap: a null or repeated frame, or a frame without a keyframe list" << endl;
             return 0;
         }
-        if (frames[k]->_features.size() > cells) {
-            LOG(ERROR) << "StereoLocalMap::TrackLocalMap: a frame with more features than the context has cells" << endl;
-            return 0;
-        }
-    }
+    if (!hip::loadable("StereoLocalMap::TrackLocalMap", frames, cells)) return 0;      // before prior is indexed by feature
     // 1: one set per distinct list object, in the order the lists first appear
     std::vector<const std::vector<Frame *> *> lists;
     std::vector<int32_t> set_of(n);
@@ -87,7 +70,6 @@ int StereoLocalMap::TrackLocalMap(const std::vector<Frame *> &frames, const std:
         const PointSet &s = sets[(size_t)set_of[k]];
         for (size_t j = 0; j < frames[k]->_features.size(); ++j) {
             const Feature *ft = frames[k]->_features[j];
-            if (!ft) { LOG(ERROR) << "StereoLocalMap::TrackLocalMap: a null feature" << endl; return 0; }
             if (!good(ft->_mappoint)) continue;
             const auto it = s.index.find(ft->_mappoint);
             if (it == s.index.end()) {
@@ -98,31 +80,8 @@ int StereoLocalMap::TrackLocalMap(const std::vector<Frame *> &frames, const std:
         }
     }
     // 2: the frames into their slots, with their feature lists and depths
-    std::vector<int32_t> slot(n);
-    for (size_t k = 0; k < n; ++k) slot[k] = rt.Resident(frames[k]);
-    for (size_t k = 0; k < n; ++k)                                       // a later frame may have taken an earlier one's slot
-        if (slot[k] < 0 || rt.Resident(frames[k]) != slot[k]) {
-            LOG(ERROR) << "StereoLocalMap::TrackLocalMap: more frames than the runtime keeps resident" << endl;
-            return 0;
-        }
-    for (size_t k = 0; k < n; ++k) {
-        const Frame *f = frames[k];
-        const int m = (int)f->_features.size();
-        std::vector<double> px(2 * (size_t)m), depth((size_t)m);
-        std::vector<int32_t> lvl((size_t)m);
-        std::vector<float> ang((size_t)m);
-        std::vector<uint8_t> has((size_t)m);
-        for (int i = 0; i < m; ++i) {
-            const Feature *ft = f->_features[i];
-            px[2 * (size_t)i] = ft->_pixel[0]; px[2 * (size_t)i + 1] = ft->_pixel[1];
-            lvl[(size_t)i] = std::max(ft->_level, 0);
-            ang[(size_t)i] = (float)ft->_angle;
-            depth[(size_t)i] = ft->_depth;
-            has[(size_t)i] = ft->_depth > 0 ? 1 : 0;
-        }
-        if (!hip::check(ygz_hip_describe_given_angle(c, slot[k], px.data(), lvl.data(), ang.data(), m), "describe_given_angle")) return 0;
-        if (!hip::check(ygz_hip_set_keypoint_depths(c, slot[k], depth.data(), has.data(), m), "set_keypoint_depths")) return 0;
-    }
+    std::vector<int32_t> slot;
+    if (!hip::load_slots("StereoLocalMap::TrackLocalMap", frames, cells, slot)) return 0;
     // 3: one call
     size_t pairs = 0;
     std::vector<size_t> off(n + 1, 0);
@@ -143,7 +102,6 @@ int StereoLocalMap::TrackLocalMap(const std::vector<Frame *> &frames, const std:
     // 4: the frames and the map points, in frame order
     int tracked = 0;
     if (results) results->resize(n);
-    PinholeCamera *cam = Frame::_camera;
     for (size_t k = 0; k < n; ++k) {
         Frame *f = frames[k];
         const PointSet &s = sets[(size_t)set_of[k]];
@@ -163,11 +121,7 @@ int StereoLocalMap::TrackLocalMap(const std::vector<Frame *> &frames, const std:
         for (size_t j = 0; j < f->_features.size(); ++j) {
             Feature *ft = f->_features[j];
             if (kp[j] < 0 || !good(ft->_mappoint)) continue;
-            ft->_bad = outlier[k * cells + j] != 0;
-            if (!ft->_bad) {
-                ft->_depth = cam->World2Camera(ft->_mappoint->_pos_world, f->_TCW)[2];
-                ft->_mappoint->_cnt_found++;
-            }
+            if (hip::apply_verdict(f, ft, outlier[k * cells + j] != 0)) ft->_mappoint->_cnt_found++;
         }
         const bool ok = status[k] == 0 && inliers[k] >= _options._min_tracked;
         if (ok) ++tracked;

@@ -1,19 +1,20 @@
 // ygz::StereoRefTracker (include/ygz/Algorithm/StereoRefTracker.h): nothing in the reference.  ORB-SLAM2's TrackReferenceKeyFrame for any number
 // of frames: the point sets of the reference keyframes are built on the host, the frames' and keyframes' feature lists and depths are put into
-// their slots the way ygz_svo.cpp does, then ONE entry point (ygz_hip_stereo_ref_keyframe_slots, ygz_slam_amd/csrc/srk.hip) computes the BoW
+// their slots (hip::load_slots, surface_share.h), then ONE entry point (ygz_hip_stereo_ref_keyframe_slots, ygz_slam_amd/csrc/srk.hip) computes the BoW
 // of every slot, searches, claims, removes by orientation and optimises on the device, and the frames are edited from its result in frame
 // order.  The spec is DESIGN.md section 29.  Every order goes by index or list position, never by address.  Error conventions of the other
 // surfaces: a failed call logs and returns 0, only a missing device throws.
 #include "ygz/Algorithm/StereoRefTracker.h"
 #include "ygz/hip/Runtime.h"
 #include "ygz_hip.h"
+#include "surface_share.h"
 #include <algorithm>
 #include <map>
 
 namespace ygz {
 
 namespace {
-bool good(const MapPoint *mp) { return mp && !mp->_bad; }
+using hip::good;
 
 struct PointSet {
     std::vector<MapPoint *> points;
@@ -49,11 +50,7 @@ int StereoRefTracker::TrackReferenceKeyFrame(const std::vector<Frame *> &frames,
     std::vector<Frame *> all(kfs);                                       // every frame that needs a slot, keyframes first, each once
     for (Frame *f : frames)
         if (std::find(all.begin(), all.end(), f) == all.end()) all.push_back(f);
-    for (const Frame *f : all)
-        if (f->_features.size() > cells) {
-            LOG(ERROR) << "StereoRefTracker::TrackReferenceKeyFrame: a frame with more features than the context has cells" << endl;
-            return 0;
-        }
+    if (!hip::loadable("StereoRefTracker::TrackReferenceKeyFrame", all, cells)) return 0;      // before kf_point is indexed by feature
     std::vector<PointSet> sets(kfs.size());
     std::vector<ygz_strack_points> views(kfs.size());
     std::vector<int32_t> kf_point(kfs.size() * cells, -1), kf_set(kfs.size());
@@ -61,7 +58,6 @@ int StereoRefTracker::TrackReferenceKeyFrame(const std::vector<Frame *> &frames,
         std::map<const MapPoint *, int32_t> index;
         for (size_t i = 0; i < kfs[s]->_features.size(); ++i) {
             const Feature *ft = kfs[s]->_features[i];
-            if (!ft) { LOG(ERROR) << "StereoRefTracker::TrackReferenceKeyFrame: a null feature" << endl; return 0; }
             if (!good(ft->_mappoint)) continue;
             const auto at = index.find(ft->_mappoint);
             if (at != index.end()) { kf_point[s * cells + i] = at->second; continue; }
@@ -75,37 +71,14 @@ int StereoRefTracker::TrackReferenceKeyFrame(const std::vector<Frame *> &frames,
         kf_set[s] = (int32_t)s;
     }
     // 2: the frames into their slots, with their feature lists and depths
-    std::map<const Frame *, int32_t> slot_of;
-    for (Frame *f : all) slot_of[f] = rt.Resident(f);
-    for (Frame *f : all)                                                 // a later frame may have taken an earlier one's slot
-        if (slot_of[f] < 0 || rt.Resident(f) != slot_of[f]) {
-            LOG(ERROR) << "StereoRefTracker::TrackReferenceKeyFrame: more frames than the runtime keeps resident" << endl;
-            return 0;
-        }
-    for (const Frame *f : all) {
-        const int m = (int)f->_features.size();
-        std::vector<double> px(2 * (size_t)m), depth((size_t)m);
-        std::vector<int32_t> lvl((size_t)m);
-        std::vector<float> ang((size_t)m);
-        std::vector<uint8_t> has((size_t)m);
-        for (int i = 0; i < m; ++i) {
-            const Feature *ft = f->_features[i];
-            if (!ft) { LOG(ERROR) << "StereoRefTracker::TrackReferenceKeyFrame: a null feature" << endl; return 0; }
-            px[2 * (size_t)i] = ft->_pixel[0]; px[2 * (size_t)i + 1] = ft->_pixel[1];
-            lvl[(size_t)i] = std::max(ft->_level, 0);
-            ang[(size_t)i] = (float)ft->_angle;
-            depth[(size_t)i] = ft->_depth;
-            has[(size_t)i] = ft->_depth > 0 ? 1 : 0;
-        }
-        if (!hip::check(ygz_hip_describe_given_angle(c, slot_of[f], px.data(), lvl.data(), ang.data(), m), "describe_given_angle")) return 0;
-        if (!hip::check(ygz_hip_set_keypoint_depths(c, slot_of[f], depth.data(), has.data(), m), "set_keypoint_depths")) return 0;
-    }
+    std::vector<int32_t> all_slot;
+    if (!hip::load_slots("StereoRefTracker::TrackReferenceKeyFrame", all, cells, all_slot)) return 0;
     // 3: one call
-    std::vector<int32_t> kf_slot(kfs.size()), slot(n), status(n), counts(8 * n), kp_point(n * cells), inliers(n);
+    const std::vector<int32_t> kf_slot(all_slot.begin(), all_slot.begin() + (long)kfs.size());       // `all` begins with the keyframes
+    std::vector<int32_t> slot(n), status(n), counts(8 * n), kp_point(n * cells), inliers(n);
     std::vector<uint8_t> outlier(n * cells);
     std::vector<double> T(7 * n), T_out(7 * n);
-    for (size_t s = 0; s < kfs.size(); ++s) kf_slot[s] = slot_of[kfs[s]];
-    for (size_t k = 0; k < n; ++k) { slot[k] = slot_of[frames[k]]; frames[k]->_TCW.to7(&T[7 * k]); }
+    for (size_t k = 0; k < n; ++k) { slot[k] = all_slot[(size_t)(std::find(all.begin(), all.end(), frames[k]) - all.begin())]; frames[k]->_TCW.to7(&T[7 * k]); }
     ygz_srk_params prm;
     ygz_hip_default_srk_params(&prm);
     prm.baseline = _options._baseline; prm.th_low = _options._th_low; prm.knn_ratio = _options._knn_ratio; prm.levelsup = _options._levelsup;
@@ -119,7 +92,6 @@ int StereoRefTracker::TrackReferenceKeyFrame(const std::vector<Frame *> &frames,
     // 4: the frames, in frame order
     int tracked = 0;
     if (results) results->resize(n);
-    PinholeCamera *cam = Frame::_camera;
     for (size_t k = 0; k < n; ++k) {
         Frame *f = frames[k];
         const PointSet &s = sets[(size_t)kf_of[k]];
@@ -133,12 +105,8 @@ int StereoRefTracker::TrackReferenceKeyFrame(const std::vector<Frame *> &frames,
             for (size_t j = 0; j < f->_features.size(); ++j) {
                 Feature *ft = f->_features[j];
                 if (!good(ft->_mappoint)) continue;
-                ft->_bad = outlier[k * cells + j] != 0;
-                if (ft->_bad) ft->_mappoint = nullptr;
-                else {
-                    ft->_depth = cam->World2Camera(ft->_mappoint->_pos_world, f->_TCW)[2];
-                    if (!ft->_mappoint->_obs.empty()) ++kept;
-                }
+                if (!hip::apply_verdict(f, ft, outlier[k * cells + j] != 0)) ft->_mappoint = nullptr;
+                else if (!ft->_mappoint->_obs.empty()) ++kept;
             }
         }
         const bool ok = status[k] == 0 && kept >= _options._min_tracked;

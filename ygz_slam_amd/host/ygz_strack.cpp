@@ -4,30 +4,18 @@
 // section 26.  Every order goes by index, list position or id, never by address.  Error conventions of the other surfaces: a failed call logs
 // and returns 0, only a missing device throws.
 #include "ygz/Algorithm/StereoTracker.h"
-#include "ygz/Algorithm/Matcher.h"
 #include "ygz/Algorithm/PoseOptimizer.h"
 #include "ygz/hip/Runtime.h"
 #include "ygz_hip.h"
+#include "surface_share.h"
 #include <algorithm>
 #include <cstring>
 
 namespace ygz {
 
 namespace {
-bool good(const MapPoint *mp) { return mp && !mp->_bad; }
+using hip::good;
 Frame *frame_of(unsigned long id, const Feature *f) { return f && f->_frame ? f->_frame : Memory::GetKeyFrame(id); }
-
-// one point of a set: false when Matcher::PointAttributes refuses it
-bool add_point(StereoTracker::Search &s, MapPoint *mp)
-{
-    Matcher::PointAttr a;
-    if (!Matcher::PointAttributes(mp, a)) return false;
-    s.points.push_back(mp);
-    for (int k = 0; k < 3; ++k) { s.pw.push_back(mp->_pos_world[k]); s.normal.push_back(a.normal[k]); }
-    s.dmax.push_back(a.dmax);
-    s.desc.insert(s.desc.end(), a.desc, a.desc + 32);
-    return true;
-}
 
 int kept(const Frame *f, bool count_bad)
 {
@@ -54,21 +42,14 @@ bool StereoTracker::Run(Frame *current, Search &s, int mode, const char *what)
 {
     const PinholeCamera *cam = Frame::GetCamera();
     const size_t n = s.points.size(), m = current->_features.size();
-    std::vector<double> px(2 * m), ur(m, -1.0), angle(m);
-    std::vector<int32_t> level(m);
-    std::vector<uint8_t> desc(32 * m);
+    std::vector<double> px, ur(m, -1.0), angle(m);
+    std::vector<int32_t> level;
+    std::vector<uint8_t> desc;
+    if (!hip::keypoint_arrays(current, px, level, desc)) { LOG(ERROR) << "StereoTracker: " << what << ": a feature without a descriptor" << endl; return false; }
     const std::vector<double> *col = Columns(current);
     for (size_t j = 0; j < m; ++j) {
-        const Feature *ft = current->_features[j];
-        if (!ft || !ft->_desc.data || ft->_desc.rows * ft->_desc.cols * (int)ft->_desc.elemSize() < 32) {
-            LOG(ERROR) << "StereoTracker: " << what << ": a feature without a descriptor" << endl;
-            return false;
-        }
-        px[2 * j] = ft->_pixel[0]; px[2 * j + 1] = ft->_pixel[1];
-        level[j] = std::max(ft->_level, 0);
-        angle[j] = ft->_angle;
+        angle[j] = current->_features[j]->_angle;
         if (col && j < col->size() && (*col)[j] >= 0) ur[j] = (*col)[j];
-        memcpy(&desc[32 * j], ft->_desc.data, 32);
     }
     ygz_strack_points set;
     memset(&set, 0, sizeof set);
@@ -116,7 +97,7 @@ int StereoTracker::TrackWithMotionModel(Frame *current, Frame *last, const SE3 &
     // 3
     for (const Feature *f : last->_features) {
         if (!f || f->_bad || !good(f->_mappoint)) continue;
-        if (!add_point(s, f->_mappoint)) continue;
+        if (!hip::append_point(s, f->_mappoint)) continue;
         s.level.push_back(std::max(f->_level, 0));
         s.angle.push_back(f->_angle);
     }
@@ -223,7 +204,7 @@ int StereoTracker::TrackLocalMap(Frame *current, const std::vector<Frame *> &loc
         for (const Feature *f : kf->_features) {
             if (!f || !good(f->_mappoint) || !seen.insert(f->_mappoint).second) continue;
             if ((int)s.points.size() >= YGZ_STRACK_MAX_PAIRS) { ++_stats.local_cut; continue; }
-            add_point(s, f->_mappoint);
+            hip::append_point(s, f->_mappoint);
         }
     }
     _stats.local_points = (int)s.points.size();

@@ -1,13 +1,13 @@
 // ygz::StereoOdometry (include/ygz/Algorithm/StereoOdometry.h): nothing in the reference.  Frame-to-frame stereo odometry for any number of
-// (current, last) pairs: the frames' feature lists and depths are put into their slots the way ygz_host.cpp describes feature lists, then ONE
+// (current, last) pairs: the frames' feature lists and depths are put into their slots (hip::load_slots, surface_share.h), then ONE
 // entry point (ygz_hip_stereo_odometry_slots, ygz_slam_amd/csrc/svo.hip) searches, claims, retries and optimises on the device.  The spec is
 // DESIGN.md section 27.  No map, no point and no _mappoint is touched.  Error conventions of the other surfaces: a failed call logs and returns
 // 0, only a missing device throws.
 #include "ygz/Algorithm/StereoOdometry.h"
 #include "ygz/hip/Runtime.h"
 #include "ygz_hip.h"
+#include "surface_share.h"
 #include <algorithm>
-#include <map>
 
 namespace ygz {
 
@@ -32,43 +32,15 @@ int StereoOdometry::TrackPairs(const std::vector<std::pair<Frame *, Frame *>> &p
         for (Frame *f : { pr.second, pr.first })
             if (std::find(frames.begin(), frames.end(), f) == frames.end()) frames.push_back(f);
     }
-    std::map<Frame *, int> slot;
-    for (Frame *f : frames) {
-        if ((int)f->_features.size() > cells) {
-            LOG(ERROR) << "StereoOdometry::TrackPairs: a frame with more features than the context has cells" << endl;
-            return 0;
-        }
-        slot[f] = rt.Resident(f);
-    }
-    for (Frame *f : frames)                                              // a later frame may have taken an earlier one's slot
-        if (slot[f] < 0 || rt.Resident(f) != slot[f]) {
-            LOG(ERROR) << "StereoOdometry::TrackPairs: more distinct frames than the runtime keeps resident" << endl;
-            return 0;
-        }
     // 2: the feature lists and their depths
-    for (Frame *f : frames) {
-        const int m = (int)f->_features.size();
-        std::vector<double> px(2 * (size_t)m), depth((size_t)m);
-        std::vector<int32_t> lvl((size_t)m);
-        std::vector<float> ang((size_t)m);
-        std::vector<uint8_t> has((size_t)m);
-        for (int i = 0; i < m; ++i) {
-            const Feature *ft = f->_features[i];
-            if (!ft) { LOG(ERROR) << "StereoOdometry::TrackPairs: a null feature" << endl; return 0; }
-            px[2 * (size_t)i] = ft->_pixel[0]; px[2 * (size_t)i + 1] = ft->_pixel[1];
-            lvl[(size_t)i] = std::max(ft->_level, 0);
-            ang[(size_t)i] = (float)ft->_angle;
-            depth[(size_t)i] = ft->_depth;
-            has[(size_t)i] = ft->_depth > 0 ? 1 : 0;
-        }
-        if (!hip::check(ygz_hip_describe_given_angle(c, slot[f], px.data(), lvl.data(), ang.data(), m), "describe_given_angle")) return 0;
-        if (!hip::check(ygz_hip_set_keypoint_depths(c, slot[f], depth.data(), has.data(), m), "set_keypoint_depths")) return 0;
-    }
+    std::vector<int32_t> slot;
+    if (!hip::load_slots("StereoOdometry::TrackPairs", frames, (size_t)cells, slot)) return 0;
+    auto slot_of = [&](const Frame *f) { return slot[(size_t)(std::find(frames.begin(), frames.end(), f) - frames.begin())]; };
     // 3: one call
     std::vector<int32_t> last_slot(n), cur_slot(n), status(n), counts(8 * n), inliers(n), match(n * (size_t)cells);
     std::vector<double> T_init(7 * n), T_rel(7 * n);
     for (size_t p = 0; p < n; ++p) {
-        cur_slot[p] = slot[pairs[p].first]; last_slot[p] = slot[pairs[p].second];
+        cur_slot[p] = slot_of(pairs[p].first); last_slot[p] = slot_of(pairs[p].second);
         (guesses ? (*guesses)[p] : SE3()).to7(&T_init[7 * p]);
     }
     ygz_svo_params prm;
