@@ -79,7 +79,9 @@ extern "C" {
  * Still 6: stereo local-map tracking on resident slots added (ygz_slm_params, ygz_hip_default_slm_params, ygz_hip_stereo_local_map_slots) --
  * no existing argument list changed.
  * Still 6: stereo reference-keyframe tracking on resident slots added (ygz_srk_params, ygz_hip_default_srk_params,
- * ygz_hip_stereo_ref_keyframe_slots) -- no existing argument list changed. */
+ * ygz_hip_stereo_ref_keyframe_slots) -- no existing argument list changed.
+ * Still 6: stereo relocalisation on resident slots added (ygz_srl_params, ygz_hip_default_srl_params, ygz_hip_stereo_relocalize_slots) -- no
+ * existing argument list changed. */
 #define YGZ_HIP_ABI_VERSION 6
 
 typedef struct ygz_hip_ctx ygz_hip_ctx;
@@ -1580,6 +1582,76 @@ int  ygz_hip_stereo_ref_keyframe_slots(ygz_hip_ctx *ctx, int n_sets, const ygz_s
                                        int32_t *kp_point, int32_t *prior, uint8_t *outlier, double *chi2, int32_t *inliers, int32_t *rounds_run,
                                        int32_t *round_status, int32_t *round_iterations, double *round_cost_initial, double *round_cost_final,
                                        double *round_lambda, int32_t *match12, int32_t *outcome, int32_t *rot);
+
+/* ---- stereo relocalisation on resident slots -- nothing in the reference; ORB-SLAM2's Tracking::Relocalization up to and including its first
+ * PoseOptimization, for any number of lost resident frames in one call, each with an ordered list of candidate keyframes.  The result is the
+ * composition of frozen specifications -- yo_search_by_bow and yo_bow_orientation of oracle/bow.c, pr_ransac of tests/pnp_ref.c and
+ * tests/popt_ref.c -- joined by the formulas below (tests/srl_ref.py restates it), and every output is bit-identical to
+ * that composition.  Sets and keyframes are those of ygz_hip_stereo_ref_keyframe_slots.  Frame f is slot[f]; it has no entry pose.  Its
+ * candidates are the keyframes cand_kf[q], cand_off[f] <= q < cand_off[f + 1], in the caller's order (best first); problem q is (frame f,
+ * keyframe cand_kf[q]) and P = cand_off[n_frames] is the number of problems.  A keyframe may be the candidate of several frames, and of one
+ * frame twice; a slot may appear in several frame entries; a frame may have no candidate.  Per problem:
+ *   1 steps 1 to 6 of ygz_hip_stereo_ref_keyframe_slots with this call's th_low, knn_ratio, levelsup and check_orientation: the
+ *     associations in keypoint order of the frame, j ascending: pw of the point, (kx_j, ky_j), kp_ur[j], kp_level[j]; n is their number;
+ *   2 n < min_matches: status 1, no PnP and no optimisation; T_pnp and T_opt are 0 0 0 1 0 0 0, the ygz_pnp_result is that of a problem
+ *     none of whose hypotheses has an inlier, with n_hypotheses = 0, and pnp_inlier, prior, outlier and chi2 are empty;
+ *   3 PnP: ygz_hip_pnp_ransac's result (pr_ransac of tests/pnp_ref.c) on (pw, (kx, ky)) of the n associations in that order with
+ *     params.pnp and the context's camera; the sample sets are ygz_hip_pnp_sample_sets(n, max_iter), formed on the device from n.  T_pnp is
+ *     its T_cw.  success == 0: status 2, T_opt = T_pnp and no optimisation;
+ *   4 pose: the edges are the PnP inliers in keypoint order, kind 2 where kp_ur[j] >= 0, else 1; ygz_hip_optimize_pose_stereo from T_pnp
+ *     with params.pose (its baseline is the call's); T_opt is its pose; status 3 when its inliers are fewer than min_final_inliers (the pose
+ *     is still returned), else 0;
+ *   5 best[f] is the first q of frame f with status 0, or -1; T_out[f] is that problem's T_opt, or 0 0 0 1 0 0 0.
+ * The host reads no count before the copy back.  One packed upload, thirteen launches (k_srl_gather, k_bow_transform, k_srl_gather for the
+ * masked node rows, k_bow_match<0>, k_srl_resolve, k_srl_sets, k_pnp_solve, k_pnp_score, k_pnp_select, k_srl_edges, k_pose_opt,
+ * k_srl_scatter, k_srl_pick), one copy back, one wait.
+ * sizeof: ygz_srl_params 120. */
+#define YGZ_SRL_MAX_FRAMES    256
+#define YGZ_SRL_MAX_PROBLEMS  256
+#define YGZ_SRL_MAX_KEYFRAMES 256
+#define YGZ_SRL_MAX_SETS      64
+#define YGZ_SRL_MAX_HYPOTHESIS_SETS 76800 /* bound of P * max_iter (256 problems of 300 iterations): 384 B of hypotheses each, 28 MiB */
+typedef struct {
+    double  baseline;                     /* 0.1: metres between the rig's cameras, > 0 */
+    int32_t th_low;                       /* 50: a match's Hamming distance is below it, 0 .. 256 */
+    float   knn_ratio;                    /* 0.75: best against second best of the same node, > 0 */
+    int32_t levelsup;                     /* 4: the FeatureVector's node is this many levels above the leaves, >= 0 */
+    int32_t check_orientation;            /* 1: the rotation histogram removes matches */
+    int32_t min_matches;                  /* 15: a problem with fewer associations gets no PnP (status 1); >= 4, what a PnP problem needs */
+    int32_t pad0;
+    ygz_pnp_params pnp;                   /* ygz_hip_default_pnp_params: 300 iterations, chi2 5.991, 10 inliers for success */
+    int32_t min_final_inliers;            /* 50: fewer inliers after the optimisation: status 3; >= 0 */
+    int32_t pad1;
+    ygz_pose_opt_params pose;             /* ygz_hip_default_pose_opt_params; its baseline is ignored: the call's is used */
+} ygz_srl_params;
+void ygz_hip_default_srl_params(ygz_srl_params *p);
+/* sets [n_sets]; kf_slot, kf_set [n_keyframes]; kf_point [n_keyframes][cells] with cells = ygz_hip_max_keypoints; slot [n_frames]; cand_off
+ * [n_frames + 1]; cand_kf [P]; params NULL: defaults.  Outputs, any of them may be NULL except T_out and best: T_out [n_frames][7]; best
+ * [n_frames]; per problem status [P] (0 relocalised, 1 too few associations, 2 PnP without success, 3 too few inliers after the
+ * optimisation), T_pnp, T_opt [P][7], pnp [P], counts [P][10] = the eight of ygz_hip_stereo_ref_keyframe_slots (the last is n), the PnP
+ * inliers, the optimiser's inliers; inliers, rounds_run [P] and round_status, round_iterations, round_cost_initial, round_cost_final,
+ * round_lambda [P][8] (those of an optimisation without edges for status 1 and 2); rot [P][33]; by frame keypoint, [P][cells]: kp_point (the
+ * set index after step 1, -1 without one and past the last keypoint), pnp_inlier (1 where the keypoint's association is an inlier of the PnP
+ * winner, also for status 2), prior = kp_point of the PnP inliers that are no outliers of the optimiser, -1 elsewhere, in the layout and index
+ * space ygz_hip_stereo_local_map_slots takes, outlier (0 where there is no edge) and chi2 (-1.0 there); by keyframe keypoint, [P][cells]:
+ * match12 and outcome as in ygz_hip_stereo_ref_keyframe_slots; sets_out [P][max_iter][3] the sample sets the device formed (zeros for
+ * status 1).  Checked in this order, all before the device is touched: YGZ_E_INVALID for a null sets, kf_slot, kf_set, kf_point, slot,
+ * cand_off, cand_kf, T_out or best, n_sets, n_keyframes or n_frames < 1; YGZ_E_CAPACITY above YGZ_SRL_MAX_SETS, YGZ_SRL_MAX_KEYFRAMES or
+ * YGZ_SRL_MAX_FRAMES; YGZ_E_INVALID for cand_off[0] != 0, a decreasing cand_off or P < 1; YGZ_E_CAPACITY for P above YGZ_SRL_MAX_PROBLEMS;
+ * YGZ_E_INVALID for a non-finite baseline, knn_ratio or pnp.chi2, baseline <= 0, th_low outside [0, 256], knn_ratio <= 0, levelsup < 0,
+ * min_matches < 4, min_final_inliers < 0, pnp.max_iter outside [1, YGZ_PNP_MAX_ITER], pnp.chi2 <= 0, pnp.min_inliers < 0, the rules of
+ * ygz_hip_optimize_pose_stereo for params.pose; YGZ_E_CAPACITY for P * pnp.max_iter above YGZ_SRL_MAX_HYPOTHESIS_SETS; YGZ_E_INVALID for a
+ * set's n_pt < 0 or a null pw of a set with points, a negative slot, a set or keyframe index out of range; a non-finite pw; last,
+ * YGZ_E_INVALID for a null context or a slot past the context's frames, YGZ_E_CAPACITY for a context of more than 32768 cells or P * cells
+ * past 2^31 - 1, YGZ_E_INVALID for a kf_point entry below -1 or not below its set's n_pt, YGZ_E_STATE for a context without a vocabulary, a
+ * slot without keypoints (no pyramid was ever built for it) or a context whose keypoint depths were never written. */
+int  ygz_hip_stereo_relocalize_slots(ygz_hip_ctx *ctx, int n_sets, const ygz_strack_points *sets, int n_keyframes, const int32_t *kf_slot,
+                                     const int32_t *kf_set, const int32_t *kf_point, int n_frames, const int32_t *slot, const int32_t *cand_off,
+                                     const int32_t *cand_kf, const ygz_srl_params *params, double *T_out, int32_t *best, int32_t *status,
+                                     double *T_pnp, double *T_opt, ygz_pnp_result *pnp, int32_t *counts, int32_t *inliers, int32_t *rounds_run,
+                                     int32_t *round_status, int32_t *round_iterations, double *round_cost_initial, double *round_cost_final,
+                                     double *round_lambda, int32_t *rot, int32_t *kp_point, uint8_t *pnp_inlier, int32_t *prior,
+                                     uint8_t *outlier, double *chi2, int32_t *match12, int32_t *outcome, int32_t *sets_out);
 
 #ifdef __cplusplus
 }

@@ -659,6 +659,22 @@ def srk_argtypes(lib):
                                                       dp, ip, ip, ip, ip, bp, dp, ip, ip, ip, ip, dp, dp, dp, ip, ip, ip]
 
 
+class SrlParams(C.Structure):
+    """ygz_srl_params (include/ygz_hip.h)"""
+    _fields_ = [("baseline", C.c_double), ("th_low", C.c_int32), ("knn_ratio", C.c_float), ("levelsup", C.c_int32),
+                ("check_orientation", C.c_int32), ("min_matches", C.c_int32), ("pad0", C.c_int32), ("pnp", PnpParams),
+                ("min_final_inliers", C.c_int32), ("pad1", C.c_int32), ("pose", PoseOptParams)]
+
+
+def srl_argtypes(lib):
+    ip, dp, bp, pp = C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.POINTER(SrlParams)
+    lib.ygz_hip_default_srl_params.argtypes = [pp]
+    lib.ygz_hip_default_srl_params.restype = None
+    lib.ygz_hip_stereo_relocalize_slots.argtypes = [C.c_void_p, C.c_int, C.POINTER(StrackPoints), C.c_int, ip, ip, ip, C.c_int, ip, ip, ip, pp,
+                                                    dp, ip, ip, dp, dp, C.POINTER(PnpResult), ip, ip, ip, ip, ip, dp, dp, dp, ip, ip, bp, ip, bp,
+                                                    dp, ip, ip, ip]
+
+
 # every symbol include/ygz_hip.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
     "ygz_hip_default_params", "ygz_hip_create", "ygz_hip_destroy", "ygz_hip_synchronize", "ygz_hip_join", "ygz_hip_set_overlap", "ygz_hip_error_string",
@@ -701,6 +717,7 @@ ABI_SYMBOLS = [
     "ygz_hip_default_svo_params", "ygz_hip_stereo_odometry_slots",
     "ygz_hip_default_slm_params", "ygz_hip_stereo_local_map_slots",
     "ygz_hip_default_srk_params", "ygz_hip_stereo_ref_keyframe_slots",
+    "ygz_hip_default_srl_params", "ygz_hip_stereo_relocalize_slots",
 ]
 INIT_SYMBOLS = ["ygz_hip_default_init_params", "ygz_hip_initialize", "ygz_hip_init_sample_sets", "ygz_hip_init_hypotheses", "ygz_hip_init_reconstruct"]
 INIT_NONE, INIT_H, INIT_F = 0, 1, 2
@@ -769,6 +786,11 @@ SRK_SYMBOLS = ["ygz_hip_default_srk_params", "ygz_hip_stereo_ref_keyframe_slots"
 SRK_MAX_FRAMES, SRK_MAX_KEYFRAMES, SRK_MAX_SETS = 1024, 256, 64
 SRK_COUNTS = ("keyframe_keypoints", "with_point", "keypoints", "with_right_column", "search_matches", "lost_claim", "removed_by_orientation", "edges")
 SRK_MATCHED, SRK_NO_MATCH, SRK_LOST_CLAIM, SRK_ORIENTATION = 0, 1, 2, 4
+
+SRL_SYMBOLS = ["ygz_hip_default_srl_params", "ygz_hip_stereo_relocalize_slots"]
+SRL_MAX_FRAMES, SRL_MAX_PROBLEMS, SRL_MAX_KEYFRAMES, SRL_MAX_SETS, SRL_MAX_HYPOTHESIS_SETS = 256, 256, 256, 64, 76800
+SRL_COUNTS = SRK_COUNTS + ("pnp_inliers", "final_inliers")
+SRL_RELOCALISED, SRL_TOO_FEW_MATCHES, SRL_PNP_FAILED, SRL_TOO_FEW_INLIERS = range(4)
 
 POPT_SYMBOLS = ["ygz_hip_default_pose_opt_params", "ygz_hip_optimize_pose_stereo"]
 POPT_FAILED, POPT_CONVERGED, POPT_MAX_ITERATIONS, POPT_STALLED = range(4)
@@ -1454,6 +1476,74 @@ class HipContext:
             _p(T0, C.c_double), C.byref(p), f_("T_out"), f_("status"), *[f_(k) for k in names]), "stereo_ref_keyframe_slots")
         del keep
         return {k: v[:n] for k, v in o.items()}
+
+    # ---- stereo relocalisation on resident slots
+    def default_srl_params(self, **fields):
+        """ygz_hip_default_srl_params, with the given fields overwritten; a field of the embedded ygz_pnp_params is given as pnp_<name>, one of
+        the embedded ygz_pose_opt_params as pose_<name>"""
+        srl_argtypes(self.lib)
+        p = SrlParams()
+        self.lib.ygz_hip_default_srl_params(C.byref(p))
+        for k, v in fields.items():
+            tgt, name = (p.pose, k[5:]) if k.startswith("pose_") else (p.pnp, k[4:]) if k.startswith("pnp_") else (p, k)
+            getattr(tgt, name)              # AttributeError for a field the struct does not have
+            setattr(tgt, name, v)
+        return p
+
+    def stereo_relocalize_slots(self, sets, kf_slot, kf_set, kf_point, slots, candidates, params=None, outputs=True, **fields):
+        """relocalisation of the lost resident frames slots[f] against their ordered candidate keyframes candidates[f] (indices into kf_slot /
+        kf_set / kf_point as in stereo_ref_keyframe_slots) in one call: BoW of every named slot, SearchByBoW, the claim, the rotation
+        histogram, P3P RANSAC on the associations and the u, v, uR pose optimisation on its inliers; problem q is the q-th (frame, candidate)
+        in the order given.  Dict of T_out [n, 7], best [n] (the winning problem or -1), cand_off [n + 1], and per problem status, T_pnp, T_opt,
+        pnp_R, pnp_t, pnp_T_cw, pnp_success, pnp_n_inliers, pnp_best_sample, pnp_best_solution, pnp_n_hypotheses, counts [P, 10], inliers,
+        rounds_run, round_status, lm_iterations, cost_initial, cost_final, lambda [P, 8], rot [P, 33], kp_point, pnp_inlier, prior, outlier,
+        chi2, match12, outcome [P, cells], sets [P, max_iter, 3]; outputs=False passes NULL for everything but T_out, best, status, T_opt
+        and prior."""
+        p = params if params is not None else self.default_srl_params(**fields)
+        srl_argtypes(self.lib)
+        keep = []
+        sa = (StrackPoints * max(len(sets), 1))()
+        for s, d in enumerate(sets):
+            a = d.get("pw")
+            a = np.zeros((0, 3)) if a is None else np.ascontiguousarray(a, np.float64).reshape(-1, 3)
+            keep.append(a)
+            sa[s].pw, sa[s].n_pt = (_p(a, C.c_double) if len(a) else C.POINTER(C.c_double)()), len(a)
+        ks, kt = np.ascontiguousarray(kf_slot, np.int32).reshape(-1), np.ascontiguousarray(kf_set, np.int32).reshape(-1)
+        sl = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        if len(ks) != len(kt) or len(sl) != len(candidates):
+            raise ValueError("kf_slot and kf_set, or slots and candidates, differ in length")
+        off = np.concatenate([[0], np.cumsum([len(c) for c in candidates])]).astype(np.int32)
+        ck = np.ascontiguousarray([k for c in candidates for k in c], np.int32).reshape(-1)
+        n, P, c, R, it = len(sl), len(ck), self.cells, POPT_MAX_ROUNDS, max(int(p.pnp.max_iter), 1)
+        kp = np.ascontiguousarray(kf_point, np.int32).reshape(len(ks), c)
+        m, mp = max(n, 1), max(P, 1)
+        o = dict(T_out=np.zeros((m, 7)), best=np.full(m, -7, np.int32), status=np.full(mp, -7, np.int32), T_opt=np.zeros((mp, 7)),
+                 prior=np.full((mp, c), -7, np.int32))
+        names = ("status", "T_pnp", "T_opt", "pnp", "counts", "inliers", "rounds_run", "round_status", "lm_iterations", "cost_initial",
+                 "cost_final", "lambda", "rot", "kp_point", "pnp_inlier", "prior", "outlier", "chi2", "match12", "outcome", "sets")
+        res = (PnpResult * mp)()
+        if outputs:
+            o.update(T_pnp=np.zeros((mp, 7)), counts=np.full((mp, 10), -7, np.int32), inliers=np.full(mp, -7, np.int32),
+                     rounds_run=np.full(mp, -7, np.int32), round_status=np.full((mp, R), -7, np.int32),
+                     lm_iterations=np.full((mp, R), -7, np.int32), cost_initial=np.zeros((mp, R)), cost_final=np.zeros((mp, R)),
+                     rot=np.full((mp, 33), -7, np.int32), kp_point=np.full((mp, c), -7, np.int32), pnp_inlier=np.full((mp, c), 7, np.uint8),
+                     outlier=np.full((mp, c), 7, np.uint8), chi2=np.zeros((mp, c)), match12=np.full((mp, c), -7, np.int32),
+                     outcome=np.full((mp, c), -7, np.int32), sets=np.full((mp, it, 3), -7, np.int32))
+            o["lambda"] = np.zeros((mp, R))
+        types = {np.dtype(np.int32): C.c_int32, np.dtype(np.float64): C.c_double, np.dtype(np.uint8): C.c_uint8}
+        f_ = lambda k: (res if outputs else None) if k == "pnp" else _p(o[k], types[o[k].dtype]) if k in o else None
+        self._chk(self.lib.ygz_hip_stereo_relocalize_slots(
+            self._ctx, len(sets), sa, len(ks), _p(ks, C.c_int32), _p(kt, C.c_int32), _p(kp, C.c_int32), n, _p(sl, C.c_int32), _p(off, C.c_int32),
+            _p(ck, C.c_int32), C.byref(p), f_("T_out"), f_("best"), *[f_(k) for k in names]), "stereo_relocalize_slots")
+        del keep
+        out = {k: (v[:n] if k in ("T_out", "best") else v[:P]) for k, v in o.items()}
+        if outputs:
+            for k in ("R", "t", "T_cw"):
+                out["pnp_" + k] = np.array([list(getattr(res[q], k)) for q in range(P)], np.float64).reshape(P, -1)
+            for k in ("success", "n_inliers", "best_sample", "best_solution", "n_hypotheses"):
+                out["pnp_" + k] = np.array([getattr(res[q], k) for q in range(P)], np.int32)
+        out["cand_off"] = off
+        return out
 
     # ---- keyframe store / device-built BA windows (configs[4])
     def stream_wait(self, signaler):

@@ -5,33 +5,14 @@
 //   k_pnp_solve    lane = (problem, sample): Lambda Twist P3P of the sample's three correspondences, up to 4 poses
 //   k_pnp_score    lane = (problem, hypothesis = sample * 4 + solution), the problem's points staged in LDS: the inlier count
 //   k_pnp_select   block = problem: the highest count (ties: smallest hypothesis), R, t, T_cw, the inlier mask
+// PnpIn, PnpDev and the kernels' prototypes are in pnp_dev.h: srl.hip launches the same three kernels on associations it compacted itself.
 #include "ygz_internal.h"
+#include "pnp_dev.h"
 #include <cstring>
 
-#define PNP_SOLVE_LANES 64                 // k_pnp_solve
-#define PNP_SCORE_LANES 256                // k_pnp_score: hypotheses per block = points per LDS tile
-#define PNP_SEL_THREADS 256                // k_pnp_select
+using namespace ygz_pnp;
 
 namespace {
-
-struct PnpIn {
-    double K4[4];
-    double chi2;
-    int32_t n_problems, max_iter, min_inliers, pad;
-};
-
-struct PnpDev {
-    const PnpIn *in;
-    const int32_t *off;               // [P + 1]
-    const double *pw, *px;            // [N][3], [N][2]
-    const int32_t *sets;              // [P][max_iter][3]
-    // the block that is copied back
-    ygz_pnp_result *res;              // [P]
-    uint8_t *mask;                    // [N]
-    int32_t *nsol;                    // [P][max_iter]
-    int32_t *counts;                  // [P][max_iter][4]
-    double *sol;                      // [P][max_iter][4][12]
-};
 
 // ---- the arithmetic (tests/pnp_ref.c, function by function) ---------------------------------------------------------------------
 #define PR_BISECT 64
@@ -284,7 +265,11 @@ __device__ __forceinline__ void pr_quat_from_matrix(const double *m, double *q)
     }
 }
 
+}  // namespace
+
 // ---- kernels -------------------------------------------------------------------------------------------------------------------
+namespace ygz_pnp {
+
 // grid (samples / 64, problems)
 __global__ __launch_bounds__(PNP_SOLVE_LANES) void k_pnp_solve(PnpDev D)
 {
@@ -293,6 +278,12 @@ __global__ __launch_bounds__(PNP_SOLVE_LANES) void k_pnp_solve(PnpDev D)
     if (s >= it) return;
     const int off = D.off[p];
     const size_t h = (size_t)p * it + s;
+    if (D.skip && D.skip[p]) {                                           // a problem its caller's kernel left out: no hypothesis
+        double *none = D.sol + h * 48;
+        for (int k = 0; k < 48; ++k) none[k] = 0.0;
+        D.nsol[h] = 0;
+        return;
+    }
     double w[9], x[6];
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
@@ -312,7 +303,7 @@ __global__ __launch_bounds__(PNP_SCORE_LANES) void k_pnp_score(PnpDev D)
     __shared__ double sw[3][PNP_SCORE_LANES], su[2][PNP_SCORE_LANES];
     const int p = blockIdx.y, it = D.in->max_iter;
     const int hyp = blockIdx.x * PNP_SCORE_LANES + threadIdx.x;
-    const int off = D.off[p], n = D.off[p + 1] - off;
+    const int off = D.off[p], n = (D.end ? D.end[p] : D.off[p + 1]) - off;
     const double chi2 = D.in->chi2;
     double K4[4];
 #pragma unroll
@@ -361,7 +352,7 @@ __global__ __launch_bounds__(PNP_SEL_THREADS) void k_pnp_select(PnpDev D)
     atomicAdd(&sh_nh, nh);
     __syncthreads();
     const unsigned long long best = sh_key;
-    const int off = D.off[p], n = D.off[p + 1] - off;
+    const int off = D.off[p], n = (D.end ? D.end[p] : D.off[p + 1]) - off;
     ygz_pnp_result *r = D.res + p;
     if (best == 0) {
         for (int i = threadIdx.x; i < n; i += PNP_SEL_THREADS) D.mask[off + i] = 0;
@@ -404,7 +395,11 @@ __global__ __launch_bounds__(PNP_SEL_THREADS) void k_pnp_select(PnpDev D)
     }
 }
 
+}  // namespace ygz_pnp
+
 // ---- host side ----------------------------------------------------------------------------------------------------------------------
+namespace {
+
 static_assert(sizeof(PnpIn) == 56 && sizeof(ygz_pnp_result) == 176, "tests/cpp/blob_layout_host.cpp restates the block with these sizes");
 struct Layout {
     size_t in, off, pw, px, sets, in_end;                    // the upload
@@ -475,6 +470,7 @@ int run(ygz_hip_ctx *ctx, int P, const int32_t *offsets, const double *pw, const
     D.px = ygz_at<const double>(dev, L.px); D.sets = ygz_at<const int32_t>(dev, L.sets);
     D.res = ygz_at<ygz_pnp_result>(dev, L.res); D.mask = dev + L.mask; D.nsol = ygz_at<int32_t>(dev, L.nsol);
     D.counts = ygz_at<int32_t>(dev, L.counts); D.sol = ygz_at<double>(dev, L.sol);
+    D.end = nullptr; D.skip = nullptr;
     YGZ_LAUNCH(ctx, KID_COUNT, k_pnp_solve, dim3(ygz_div_up(it, PNP_SOLVE_LANES), P), dim3(PNP_SOLVE_LANES), D);
     YGZ_LAUNCH(ctx, KID_COUNT, k_pnp_score, dim3(ygz_div_up(4 * it, PNP_SCORE_LANES), P), dim3(PNP_SCORE_LANES), D);
     YGZ_LAUNCH(ctx, KID_COUNT, k_pnp_select, dim3(P), dim3(PNP_SEL_THREADS), D);

@@ -7,6 +7,7 @@
 #include "ygz/Algorithm/BA.h"
 #include "ygz/hip/Runtime.h"
 #include "ygz_hip.h"
+#include "retrieval.h"
 #include <algorithm>
 #include <cstring>
 
@@ -62,32 +63,15 @@ bool Relocalizer::Relocalize(Frame *current, const vector<Frame *> &keyframes)
     };
     if (detected.empty() || current->_bow_vec.empty()) return finish(false);
 
-    // 3. candidates by BoW score: >= _min_score_ratio of the best and > 0, best first, ties by keyframe id
-    // (an attached database answers for the keyframes it holds with one device query: the same numbers, KeyFrameDatabase.h)
-    map<const Frame *, double> db_score;
-    vector<KeyFrameDatabase::Hit> hits;
-    const bool from_db = _kfdb && Frame::_vocab->scoring_ == 0 && _kfdb->Query(current->_bow_vec, hits);
-    for (const KeyFrameDatabase::Hit &h : hits) db_score[h.kf] = h.score;
+    // 3. candidates by BoW score: >= _min_score_ratio of the best and > 0, best first, ties by keyframe id (hip::bow_candidates, retrieval.h;
+    // an attached database answers for the keyframes it holds with one device query: the same numbers, KeyFrameDatabase.h)
+    vector<hip::Retrieved> found;
+    hip::bow_candidates(current, keyframes, _kfdb, std::min(_option._max_candidates, YGZ_PNP_MAX_PROBLEMS), _option._min_score_ratio, found);
     vector<Candidate> cands;
-    for (Frame *kf : keyframes) {
-        if (!kf || kf->_bad || kf == current) continue;
+    for (const hip::Retrieved &r : found) {
         Candidate c;
-        c.kf = kf;
-        if (from_db && _kfdb->Has(kf)) {
-            auto it = db_score.find(kf);
-            c.score = it != db_score.end() ? it->second : -0.0 / 2.0;             // no shared word: what Vocabulary::score returns
-        } else
-            c.score = Frame::_vocab->score(current->_bow_vec, kf->_bow_vec);
-        if (c.score > 0) cands.push_back(std::move(c));
-    }
-    std::sort(cands.begin(), cands.end(), [](const Candidate &a, const Candidate &b) {
-        return a.score != b.score ? a.score > b.score : a.kf->_keyframe_id < b.kf->_keyframe_id; });
-    if (!cands.empty()) {
-        const double floor = _option._min_score_ratio * cands[0].score;
-        size_t keep = 0;
-        const size_t cap = (size_t)std::max(0, std::min(_option._max_candidates, YGZ_PNP_MAX_PROBLEMS));
-        while (keep < cands.size() && keep < cap && cands[keep].score >= floor) ++keep;
-        cands.resize(keep);
+        c.kf = r.kf; c.score = r.score;
+        cands.push_back(std::move(c));
     }
     _stats.candidates = (int)cands.size();
 
