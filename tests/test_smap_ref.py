@@ -2,7 +2,10 @@
 matrices and matrix products from numpy, np.linalg.svd for the null vector of the triangulation, the stereo parallax as the real
 cos(2 atan2(b / 2, d)), np.lexsort for the keyframe's ranking.  Codes and methods must be EQUAL for every pair the witness does not mark as
 near a threshold (a compared quantity within 1e-9 relative of its bound); marked pairs are a condition on the scenes, not a tolerance: at
-most 2 % of a scene, never a whole code class.  Also what the stereo columns buy on the forward-motion scene."""
+most 2 % of a scene, never a whole code class.  What these seeded scenes leave out -- a compared quantity exactly ON its bound, and one
+representable step beyond it -- is held by the crafted pairs of tests/depth_limit_cases.py, where no pair is marked or skipped
+(tests/test_depth_limit_cases.py on the CPU, tests/test_gpu_depth_limits.py on the device).  Also what the stereo columns buy on the
+forward-motion scene."""
 import numpy as np
 import pytest
 
