@@ -81,7 +81,9 @@ extern "C" {
  * Still 6: stereo reference-keyframe tracking on resident slots added (ygz_srk_params, ygz_hip_default_srk_params,
  * ygz_hip_stereo_ref_keyframe_slots) -- no existing argument list changed.
  * Still 6: stereo relocalisation on resident slots added (ygz_srl_params, ygz_hip_default_srl_params, ygz_hip_stereo_relocalize_slots) -- no
- * existing argument list changed. */
+ * existing argument list changed.
+ * Still 6: local-map selection added (ygz_lms_params, ygz_hip_default_lms_params, ygz_hip_local_map_select) -- no existing argument list
+ * changed. */
 #define YGZ_HIP_ABI_VERSION 6
 
 typedef struct ygz_hip_ctx ygz_hip_ctx;
@@ -1652,6 +1654,55 @@ int  ygz_hip_stereo_relocalize_slots(ygz_hip_ctx *ctx, int n_sets, const ygz_str
                                      int32_t *round_status, int32_t *round_iterations, double *round_cost_initial, double *round_cost_final,
                                      double *round_lambda, int32_t *rot, int32_t *kp_point, uint8_t *pnp_inlier, int32_t *prior,
                                      uint8_t *outlier, double *chi2, int32_t *match12, int32_t *outcome, int32_t *sets_out);
+
+/* ---- local-map selection -- nothing in the reference; ORB-SLAM2's Tracking::UpdateLocalKeyFrames in the form of
+ * StereoTracker::LocalKeyFrames (no spanning tree: the data model has none) and Tracking::UpdateLocalPoints, for any number of frames on one
+ * map in one call (tests/lms_ref.c is the frozen specification, and every output is an integer and bit-identical to it).
+ * The map goes up once per call: kf_bad [n_keyframes]; cov [n_keyframes][n_cov], a keyframe's covisible keyframes, best first, in
+ * [-1, n_keyframes), where a -1 is looked at and skipped (it ends nothing); the points in ygz_hip_covisibility's point-major CSR, offsets
+ * [n_points + 1] and kf [n_obs] strictly ascending within a point, with feat [n_obs] the index of the observing feature in its keyframe, in
+ * [0, YGZ_LMS_MAX_FEATURES); pt_bad [n_points] or NULL for "none bad".  The frames: fr_off [n_frames + 1]; fr_pt [fr_off[n_frames]] in
+ * [-1, n_points), the points on a frame in feature order, -1 for no point; a point may stand on a frame twice.  Per frame f:
+ *   1 votes[f][k] is the number of entries e of f with p = fr_pt[e] >= 0, pt_bad[p] == 0 and k in p's list (a point that stands twice votes
+ *     twice: the host rule counts per feature);
+ *   2 ref[f] is the smallest k with the largest vote > 0, bad keyframes included; -1 without a vote;
+ *   3 the list: the voters with kf_bad == 0 in ascending k (n_voters[f] of them, never capped); then for voter i = 0 .. n_voters - 1 in order,
+ *     while the list is shorter than max_keyframes (tested before each voter), the first c of cov[voter_i][0 .. n_cov) with c >= 0,
+ *     kf_bad[c] == 0 and c not yet in the list is appended, at most one per voter.  n_local[f] is the length, local_kf[f][n_keyframes] the
+ *     list, padded with -1; rank_f(k) is k's position in it;
+ *   4 the point set: the points with pt_bad == 0 that have an observer in the list, ascending by the key (smallest rank_f over the point's
+ *     observers, feat of that observation, p): on a map whose observations mirror the keyframes' features that is "keyframes in the given
+ *     order, features by index, each point once", what ygz_hip_stereo_local_map_slots' callers build.  The first max_points are kept:
+ *     local_pt[f][max_points] (padded with -1), n_pt[f] their number, n_cut[f] the number of the rest;
+ *   5 fr_prior[e] is the position of fr_pt[e] in f's kept list, or -1 (no point, a bad point, no observer in the list, a cut point): a
+ *     frame's slice is the `prior` row ygz_hip_stereo_local_map_slots takes once laid out at `cells`.
+ * The entry point builds the keyframe-major index ((feature, point) pairs per keyframe, two counting passes) beside the upload.  One packed
+ * upload, four launches (k_lms_vote, k_lms_points, k_lms_place, k_lms_prior), one copy back, one wait; the host decides nothing in between.
+ * sizeof: ygz_lms_params 8. */
+#define YGZ_LMS_MAX_KEYFRAMES 4096        /* n_keyframes and max_keyframes (= YGZ_MAP_MAX_KEYFRAMES) */
+#define YGZ_LMS_MAX_COV       32          /* n_cov */
+#define YGZ_LMS_MAX_FRAMES    1024        /* n_frames (= YGZ_SLM_MAX_FRAMES) */
+#define YGZ_LMS_MAX_FEATURES  32768       /* entries of one frame; feat is below it */
+typedef struct {
+    int32_t max_keyframes;                /* 80: the extension stops at this length (the voters alone may exceed it), in [1, YGZ_LMS_MAX_KEYFRAMES] */
+    int32_t max_points;                   /* 16384: points kept per frame, >= 1; n_frames * max_points <= YGZ_SLM_MAX_PAIRS */
+} ygz_lms_params;
+void ygz_hip_default_lms_params(ygz_lms_params *p);
+/* params NULL: defaults.  Outputs, any of them may be NULL except n_local and local_kf: votes [n_frames][n_keyframes]; ref, n_voters, n_local
+ * [n_frames]; local_kf [n_frames][n_keyframes]; n_pt, n_cut [n_frames]; local_pt [n_frames][max_points]; fr_prior [fr_off[n_frames]].  Checked
+ * in this order, all before the device is touched: YGZ_E_INVALID for a null kf_bad, offsets, kf, feat, fr_off, fr_pt, n_local or local_kf, a
+ * null cov with n_cov > 0, n_keyframes, n_points or n_frames < 1, n_cov < 0; YGZ_E_CAPACITY for n_keyframes above YGZ_LMS_MAX_KEYFRAMES,
+ * n_cov above YGZ_LMS_MAX_COV or n_frames above YGZ_LMS_MAX_FRAMES; YGZ_E_INVALID for max_keyframes outside [1, YGZ_LMS_MAX_KEYFRAMES] or
+ * max_points < 1; YGZ_E_CAPACITY for n_frames * max_points above YGZ_SLM_MAX_PAIRS or n_frames * n_keyframes above YGZ_COVIS_MAX_CELLS;
+ * YGZ_E_INVALID for offsets[0] or fr_off[0] != 0 or a decreasing offset; YGZ_E_CAPACITY for a point with more than
+ * YGZ_MAP_MAX_OBS_PER_POINT observations, more than YGZ_MAP_MAX_OBS in the call or a frame of more than YGZ_LMS_MAX_FEATURES entries;
+ * YGZ_E_INVALID for a keyframe index out of range, a list that is not strictly ascending, a feat out of range, a cov entry outside
+ * [-1, n_keyframes) or an fr_pt entry outside [-1, n_points); last, for a null context.  A refused call writes nothing. */
+int  ygz_hip_local_map_select(ygz_hip_ctx *ctx, int n_keyframes, const uint8_t *kf_bad, int n_cov, const int32_t *cov, int n_points,
+                              const int32_t *offsets, const int32_t *kf, const int32_t *feat, const uint8_t *pt_bad, int n_frames,
+                              const int32_t *fr_off, const int32_t *fr_pt, const ygz_lms_params *params, int32_t *votes, int32_t *ref,
+                              int32_t *n_voters, int32_t *n_local, int32_t *local_kf, int32_t *n_pt, int32_t *n_cut, int32_t *local_pt,
+                              int32_t *fr_prior);
 
 #ifdef __cplusplus
 }

@@ -675,6 +675,18 @@ def srl_argtypes(lib):
                                                     dp, ip, ip, ip]
 
 
+class LmsParams(C.Structure):
+    """ygz_lms_params (include/ygz_hip.h)"""
+    _fields_ = [("max_keyframes", C.c_int32), ("max_points", C.c_int32)]
+
+
+def lms_argtypes(lib):
+    ip, bp, pp = C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(LmsParams)
+    lib.ygz_hip_default_lms_params.argtypes = [pp]
+    lib.ygz_hip_default_lms_params.restype = None
+    lib.ygz_hip_local_map_select.argtypes = [C.c_void_p, C.c_int, bp, C.c_int, ip, C.c_int, ip, ip, ip, bp, C.c_int, ip, ip, pp] + [ip] * 9
+
+
 # every symbol include/ygz_hip.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
     "ygz_hip_default_params", "ygz_hip_create", "ygz_hip_destroy", "ygz_hip_synchronize", "ygz_hip_join", "ygz_hip_set_overlap", "ygz_hip_error_string",
@@ -718,6 +730,7 @@ ABI_SYMBOLS = [
     "ygz_hip_default_slm_params", "ygz_hip_stereo_local_map_slots",
     "ygz_hip_default_srk_params", "ygz_hip_stereo_ref_keyframe_slots",
     "ygz_hip_default_srl_params", "ygz_hip_stereo_relocalize_slots",
+    "ygz_hip_default_lms_params", "ygz_hip_local_map_select",
 ]
 INIT_SYMBOLS = ["ygz_hip_default_init_params", "ygz_hip_initialize", "ygz_hip_init_sample_sets", "ygz_hip_init_hypotheses", "ygz_hip_init_reconstruct"]
 INIT_NONE, INIT_H, INIT_F = 0, 1, 2
@@ -791,6 +804,10 @@ SRL_SYMBOLS = ["ygz_hip_default_srl_params", "ygz_hip_stereo_relocalize_slots"]
 SRL_MAX_FRAMES, SRL_MAX_PROBLEMS, SRL_MAX_KEYFRAMES, SRL_MAX_SETS, SRL_MAX_HYPOTHESIS_SETS = 256, 256, 256, 64, 76800
 SRL_COUNTS = SRK_COUNTS + ("pnp_inliers", "final_inliers")
 SRL_RELOCALISED, SRL_TOO_FEW_MATCHES, SRL_PNP_FAILED, SRL_TOO_FEW_INLIERS = range(4)
+
+LMS_SYMBOLS = ["ygz_hip_default_lms_params", "ygz_hip_local_map_select"]
+LMS_MAX_KEYFRAMES, LMS_MAX_COV, LMS_MAX_FRAMES, LMS_MAX_FEATURES = 4096, 32, 1024, 32768
+LMS_OUTPUTS = ("votes", "ref", "n_voters", "n_local", "local_kf", "n_pt", "n_cut", "local_pt", "fr_prior")
 
 POPT_SYMBOLS = ["ygz_hip_default_pose_opt_params", "ygz_hip_optimize_pose_stereo"]
 POPT_FAILED, POPT_CONVERGED, POPT_MAX_ITERATIONS, POPT_STALLED = range(4)
@@ -2471,6 +2488,45 @@ class HipContext:
         self._chk(self.lib.ygz_hip_cull_keyframes(self._ctx, P, _p(off, C.c_int32), _p(k, C.c_int32), _p(l, C.c_int32), int(n_keyframes), n,
                                                   _p(c, C.c_int32), C.byref(prm), _p(o["culled"], C.c_int32), _p(o["tracked"], C.c_int32),
                                                   _p(o["redundant"], C.c_int32), _p(o["point_dead"], C.c_uint8)), "cull_keyframes")
+        return o
+
+    # ---- local-map selection
+
+    def local_map_select(self, kf_bad, cov, offsets, kf, feat, frame_offsets, frame_points, pt_bad=None, outputs=None, **params):
+        """the local keyframes and local points of many frames on one map (ygz_hip_local_map_select): kf_bad [K], cov [K][C] (-1: none),
+        offsets [P + 1], kf and feat [n_obs], frame_offsets [F + 1], frame_points [E] (-1: no point), pt_bad [P] or None; params: the fields
+        of ygz_lms_params; outputs: the names of LMS_OUTPUTS to bring back (None: all; n_local and local_kf always).  dict of int32 arrays:
+        votes, local_kf [F][K], ref, n_voters, n_local, n_pt, n_cut [F], local_pt [F][max_points], fr_prior [E]"""
+        one = lambda a: a if len(a) else np.zeros(1, np.int32)
+        bad = np.ascontiguousarray(kf_bad, np.uint8).reshape(-1)
+        K = len(bad)
+        cv = np.ascontiguousarray(cov, np.int32).reshape(K, -1)
+        off = np.ascontiguousarray(offsets, np.int32).reshape(-1)
+        k, ft = np.ascontiguousarray(kf, np.int32).reshape(-1), np.ascontiguousarray(feat, np.int32).reshape(-1)
+        fo, fp = np.ascontiguousarray(frame_offsets, np.int32).reshape(-1), np.ascontiguousarray(frame_points, np.int32).reshape(-1)
+        if len(off) < 2 or len(fo) < 2 or int(off[-1]) != len(k) or len(k) != len(ft) or int(fo[-1]) != len(fp):
+            raise ValueError("the offsets do not describe their arrays")
+        pb = None if pt_bad is None else np.ascontiguousarray(pt_bad, np.uint8).reshape(-1)
+        if pb is not None and len(pb) != len(off) - 1:
+            raise ValueError("pt_bad has one entry per point")
+        lms_argtypes(self.lib)
+        prm = LmsParams()
+        self.lib.ygz_hip_default_lms_params(C.byref(prm))
+        for name, v in params.items():
+            getattr(prm, name)
+            setattr(prm, name, v)
+        F, E, mp = len(fo) - 1, len(fp), max(int(prm.max_points), 1)
+        shape = dict(votes=(F, K), ref=(F,), n_voters=(F,), n_local=(F,), local_kf=(F, K), n_pt=(F,), n_cut=(F,), local_pt=(F, mp), fr_prior=(max(E, 1),))
+        want = set(LMS_OUTPUTS if outputs is None else outputs) | {"n_local", "local_kf"}
+        o = {name: np.full(shape[name], -7, np.int32) for name in LMS_OUTPUTS if name in want}
+        cv1, k1, ft1, fp1 = one(cv.reshape(-1)), one(k), one(ft), one(fp)
+        self._chk(self.lib.ygz_hip_local_map_select(self._ctx, K, _p(bad, C.c_uint8), cv.shape[1], _p(cv1, C.c_int32), len(off) - 1,
+                                                    _p(off, C.c_int32), _p(k1, C.c_int32), _p(ft1, C.c_int32),
+                                                    None if pb is None else _p(pb, C.c_uint8), F, _p(fo, C.c_int32), _p(fp1, C.c_int32),
+                                                    C.byref(prm), *[_p(o[name], C.c_int32) if name in o else None for name in LMS_OUTPUTS]),
+                  "local_map_select")
+        if "fr_prior" in o:
+            o["fr_prior"] = o["fr_prior"][:E]
         return o
 
     # ---- BoW
