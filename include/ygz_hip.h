@@ -83,7 +83,9 @@ extern "C" {
  * Still 6: stereo relocalisation on resident slots added (ygz_srl_params, ygz_hip_default_srl_params, ygz_hip_stereo_relocalize_slots) -- no
  * existing argument list changed.
  * Still 6: local-map selection added (ygz_lms_params, ygz_hip_default_lms_params, ygz_hip_local_map_select) -- no existing argument list
- * changed. */
+ * changed.
+ * Still 6: map-point attributes and local-map tracking on an indexed map added (ygz_hip_map_point_attributes,
+ * ygz_hip_stereo_local_map_indexed) -- no existing argument list changed. */
 #define YGZ_HIP_ABI_VERSION 6
 
 typedef struct ygz_hip_ctx ygz_hip_ctx;
@@ -1703,6 +1705,51 @@ int  ygz_hip_local_map_select(ygz_hip_ctx *ctx, int n_keyframes, const uint8_t *
                               const int32_t *fr_off, const int32_t *fr_pt, const ygz_lms_params *params, int32_t *votes, int32_t *ref,
                               int32_t *n_voters, int32_t *n_local, int32_t *local_kf, int32_t *n_pt, int32_t *n_cut, int32_t *local_pt,
                               int32_t *fr_prior);
+
+/* ---- map-point attributes -- nothing in the reference; ORB-SLAM2's MapPoint::UpdateNormalAndDepth as ygz::Matcher::PointAttributes states it,
+ * for every point of a map in one call (tests/mpa_ref.c is the frozen specification, and every double is bit-identical
+ * to it).  The map is a point-major CSR: point p owns the rows offsets[p] .. offsets[p + 1] - 1 in the caller's order, row e names the
+ * observing keyframe obs_kf[e] (it need not ascend and may repeat) and the level obs_level[e] of the observation; kf_center
+ * [n_keyframes][3] the camera centres, pw [n_points][3].  Per row r = pw_p - kf_center[obs_kf[e]], q = r0 r0, then q + r1 r1, then q + r2 r2,
+ * d = sqrt(q), sum_k += r_k / d, every operation one IEEE double operation in this order, the sum sequential in row order;
+ * normal = sum / (double)rows, dmax = d of the point's first row * 2^max(obs_level of that row, 0).  state [n_points]: 0 for a point without
+ * a row, 2 when some d is 0 or an output is not finite, otherwise 1; with state 0 or 2 dmax and normal are zeros (no NaN leaves the call).
+ * One packed upload, one launch (k_mpa_attr), one copy back, one wait. */
+#define YGZ_MPA_MAX_POINTS 1048576        /* n_points */
+/* Checked in this order, all before the device is touched: YGZ_E_INVALID for a null array, n_keyframes or n_points < 1; YGZ_E_CAPACITY for
+ * n_keyframes above YGZ_MAP_MAX_KEYFRAMES or n_points above YGZ_MPA_MAX_POINTS; YGZ_E_INVALID for offsets[0] != 0 or a decreasing offset;
+ * YGZ_E_CAPACITY for a point with more than YGZ_MAP_MAX_OBS_PER_POINT rows or more than YGZ_MAP_MAX_OBS rows in the call; YGZ_E_INVALID for
+ * an obs_kf outside [0, n_keyframes), an obs_level above 30 or a centre or point that is not finite; last, for a null context.  A refused
+ * call writes nothing. */
+int  ygz_hip_map_point_attributes(ygz_hip_ctx *ctx, int n_keyframes, const double *kf_center, int n_points, const double *pw,
+                                  const int32_t *offsets, const int32_t *obs_kf, const int32_t *obs_level, double *dmax, double *normal,
+                                  int32_t *state);
+
+/* ---- stereo local-map tracking on an indexed map -- ygz_hip_stereo_local_map_slots with the point sets given as index lists into ONE map
+ * (DESIGN.md section 35).  The map: pw [n_points][3], pt_desc [n_points][32], pt_dmax [n_points], pt_normal [n_points][3], what
+ * ygz_hip_map_point_attributes writes; it goes up once.  The lists: list_pt [n_lists][list_stride] and list_len [n_lists] are local_pt and
+ * n_pt of ygz_hip_local_map_select, so its output goes in as it is; the entries past list_len[l] are not read; an index may stand in several
+ * lists and twice in one.  Frame f has the keypoints of slot[f] and the points of list[f]; prior[f][j] is a position in that list.  On the
+ * device k_slm_index (a lane per list entry) gathers every list into a packed point set, and the five launches of
+ * ygz_hip_stereo_local_map_slots run on those sets unchanged: for every accepted input every output is bit-identical to that call on the sets
+ * gathered by the lists on the host, and to tests/slm_ref.py on them.  YGZ_SLM_MAX_SETS does not apply.  One packed upload, six launches, one
+ * copy back, one wait; the host decides nothing in between.
+ * The outputs are those of ygz_hip_stereo_local_map_slots, frame f contributing list_len[list[f]] entries to the per-point ones.  Checked in
+ * this order, all before the device is touched: YGZ_E_INVALID for a null list_pt, list_len, slot, list, T or T_out, n_frames < 1, n_lists < 1
+ * or n_points < 0; YGZ_E_CAPACITY for n_frames or n_lists above YGZ_SLM_MAX_FRAMES or n_points above YGZ_MPA_MAX_POINTS; YGZ_E_INVALID for the
+ * parameters as in ygz_hip_stereo_local_map_slots, a null pw, pt_desc, pt_dmax or pt_normal with n_points > 0, list_stride < 1, a list_len
+ * outside [0, list_stride], a negative slot, a list index out of range, an entry below list_len outside [0, n_points); YGZ_E_CAPACITY for
+ * more than YGZ_SLM_MAX_PAIRS pairs (the sum over the frames of their list's length); YGZ_E_INVALID for a non-finite T, or a non-finite
+ * point, dmax or normal anywhere in the map; last, the context's checks of ygz_hip_stereo_local_map_slots in its order.  A refused call
+ * writes nothing. */
+int  ygz_hip_stereo_local_map_indexed(ygz_hip_ctx *ctx, int n_points, const double *pw, const uint8_t *pt_desc, const double *pt_dmax,
+                                      const double *pt_normal, int n_lists, int list_stride, const int32_t *list_pt, const int32_t *list_len,
+                                      int n_frames, const int32_t *slot, const int32_t *list, const double *T, const int32_t *prior,
+                                      const ygz_slm_params *params, double *T_out, int32_t *status, int32_t *counts, int32_t *kp_point,
+                                      uint8_t *outlier, double *chi2, int32_t *inliers, int32_t *rounds_run, int32_t *round_status,
+                                      int32_t *round_iterations, double *round_cost_initial, double *round_cost_final, double *round_lambda,
+                                      int32_t *match, int32_t *dist, int32_t *level, int32_t *reason, int32_t *outcome, int32_t *n_cand,
+                                      int32_t *n_gated, double *proj);
 
 #ifdef __cplusplus
 }

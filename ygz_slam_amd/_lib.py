@@ -687,6 +687,17 @@ def lms_argtypes(lib):
     lib.ygz_hip_local_map_select.argtypes = [C.c_void_p, C.c_int, bp, C.c_int, ip, C.c_int, ip, ip, ip, bp, C.c_int, ip, ip, pp] + [ip] * 9
 
 
+def mpa_argtypes(lib):
+    ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+    lib.ygz_hip_map_point_attributes.argtypes = [C.c_void_p, C.c_int, dp, C.c_int, dp, ip, ip, ip, dp, dp, ip]
+
+
+def slm_indexed_argtypes(lib):
+    ip, dp, bp, pp = C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.POINTER(SlmParams)
+    lib.ygz_hip_stereo_local_map_indexed.argtypes = [C.c_void_p, C.c_int, dp, bp, dp, dp, C.c_int, C.c_int, ip, ip, C.c_int, ip, ip, dp, ip, pp, dp,
+                                                     ip, ip, ip, bp, dp, ip, ip, ip, ip, dp, dp, dp, ip, ip, ip, ip, ip, ip, ip, dp]
+
+
 # every symbol include/ygz_hip.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
     "ygz_hip_default_params", "ygz_hip_create", "ygz_hip_destroy", "ygz_hip_synchronize", "ygz_hip_join", "ygz_hip_set_overlap", "ygz_hip_error_string",
@@ -731,6 +742,7 @@ ABI_SYMBOLS = [
     "ygz_hip_default_srk_params", "ygz_hip_stereo_ref_keyframe_slots",
     "ygz_hip_default_srl_params", "ygz_hip_stereo_relocalize_slots",
     "ygz_hip_default_lms_params", "ygz_hip_local_map_select",
+    "ygz_hip_map_point_attributes", "ygz_hip_stereo_local_map_indexed",
 ]
 INIT_SYMBOLS = ["ygz_hip_default_init_params", "ygz_hip_initialize", "ygz_hip_init_sample_sets", "ygz_hip_init_hypotheses", "ygz_hip_init_reconstruct"]
 INIT_NONE, INIT_H, INIT_F = 0, 1, 2
@@ -808,6 +820,9 @@ SRL_RELOCALISED, SRL_TOO_FEW_MATCHES, SRL_PNP_FAILED, SRL_TOO_FEW_INLIERS = rang
 LMS_SYMBOLS = ["ygz_hip_default_lms_params", "ygz_hip_local_map_select"]
 LMS_MAX_KEYFRAMES, LMS_MAX_COV, LMS_MAX_FRAMES, LMS_MAX_FEATURES = 4096, 32, 1024, 32768
 LMS_OUTPUTS = ("votes", "ref", "n_voters", "n_local", "local_kf", "n_pt", "n_cut", "local_pt", "fr_prior")
+
+MPA_SYMBOLS = ["ygz_hip_map_point_attributes", "ygz_hip_stereo_local_map_indexed"]
+MPA_MAX_POINTS, MPA_MAX_LEVEL = 1048576, 30
 
 POPT_SYMBOLS = ["ygz_hip_default_pose_opt_params", "ygz_hip_optimize_pose_stereo"]
 POPT_FAILED, POPT_CONVERGED, POPT_MAX_ITERATIONS, POPT_STALLED = range(4)
@@ -2528,6 +2543,82 @@ class HipContext:
         if "fr_prior" in o:
             o["fr_prior"] = o["fr_prior"][:E]
         return o
+
+    # ---- map-point attributes and local-map tracking on an indexed map
+
+    def map_point_attributes(self, kf_center, pw, offsets, obs_kf, obs_level):
+        """dmax [P], normal [P, 3] and state [P] of every point of a map (ygz_hip_map_point_attributes): kf_center [K, 3], pw [P, 3], offsets
+        [P + 1], obs_kf and obs_level [n_obs] in the caller's row order.  state 0: no row, 2: a distance of 0 or an output that is not
+        finite (zeros are written), 1: usable"""
+        c, x = np.ascontiguousarray(kf_center, np.float64).reshape(-1, 3), np.ascontiguousarray(pw, np.float64).reshape(-1, 3)
+        off = np.ascontiguousarray(offsets, np.int32).reshape(-1)
+        k, lv = np.ascontiguousarray(obs_kf, np.int32).reshape(-1), np.ascontiguousarray(obs_level, np.int32).reshape(-1)
+        if len(off) != len(x) + 1 or len(k) != len(lv) or (len(off) and int(off[-1]) != len(k)):
+            raise ValueError("the offsets do not describe their arrays")
+        P = len(x)
+        o = dict(dmax=np.full(max(P, 1), -7.0), normal=np.full((max(P, 1), 3), -7.0), state=np.full(max(P, 1), -7, np.int32))
+        one = lambda a, t: a if len(a) else np.zeros(3, t)
+        mpa_argtypes(self.lib)
+        self._chk(self.lib.ygz_hip_map_point_attributes(self._ctx, len(c), _p(one(c, np.float64), C.c_double), P, _p(one(x, np.float64), C.c_double),
+                                                        _p(off, C.c_int32), _p(one(k, np.int32), C.c_int32), _p(one(lv, np.int32), C.c_int32),
+                                                        _p(o["dmax"], C.c_double), _p(o["normal"], C.c_double), _p(o["state"], C.c_int32)),
+                  "map_point_attributes")
+        return {name: v[:P] for name, v in o.items()}
+
+    def stereo_local_map_indexed(self, points, list_pt, list_len, slots, list_index, T, prior=None, params=None, outputs=True, **fields):
+        """stereo_local_map_slots with the sets given as index lists into one map (ygz_hip_stereo_local_map_indexed).  points: dict of pw
+        [P, 3], pt_desc [P, 32], pt_dmax [P], pt_normal [P, 3] (an empty dict: a map of 0 points); list_pt [n_lists, stride] and list_len
+        [n_lists] as local_map_select writes local_pt and n_pt (the entries past list_len are not read); frame f has the keypoints of
+        slots[f] and the points of list list_index[f].  The result is that of stereo_local_map_slots on the gathered sets."""
+        p = params if params is not None else self.default_slm_params(**fields)
+        slm_indexed_argtypes(self.lib)
+        P = len(np.asarray(points["pt_desc"]).reshape(-1)) // 32 if points.get("pt_desc") is not None else 0
+
+        def arr(name, t, n):
+            a = points.get(name)
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, t).reshape(-1)
+            if len(a) != n:
+                raise ValueError("%s has the wrong length" % name)
+            return a
+        m_pw, m_desc = arr("pw", np.float64, 3 * P), arr("pt_desc", np.uint8, 32 * P)
+        m_dmax, m_nrm = arr("pt_dmax", np.float64, P), arr("pt_normal", np.float64, 3 * P)
+        ll = np.ascontiguousarray(list_len, np.int32).reshape(-1)
+        lp = np.ascontiguousarray(list_pt, np.int32).reshape(max(len(ll), 1), -1)
+        stride = lp.shape[1]
+        sl, li = np.ascontiguousarray(slots, np.int32).reshape(-1), np.ascontiguousarray(list_index, np.int32).reshape(-1)
+        if len(sl) != len(li):
+            raise ValueError("slots and list_index differ in length")
+        n, c, R = len(sl), self.cells, POPT_MAX_ROUNDS
+        T0 = np.ascontiguousarray(T, np.float64).reshape(n, 7)
+        pr = None if prior is None else np.ascontiguousarray(prior, np.int32).reshape(n, c)
+        off = [0]
+        for f in range(n):
+            off.append(off[-1] + (max(int(ll[int(li[f])]), 0) if 0 <= li[f] < len(ll) else 0))
+        N, m = off[-1], max(n, 1)
+        o = dict(T_out=np.zeros((m, 7)), status=np.full(m, -7, np.int32))
+        names = ("counts", "kp_point", "outlier", "chi2", "inliers", "rounds_run", "round_status", "lm_iterations", "cost_initial", "cost_final",
+                 "lambda") + SLM_INT_OUTPUTS + ("proj",)
+        if outputs:
+            o.update(counts=np.full((m, 8), -7, np.int32), kp_point=np.full((m, c), -7, np.int32), outlier=np.full((m, c), 7, np.uint8),
+                     chi2=np.zeros((m, c)), inliers=np.full(m, -7, np.int32), rounds_run=np.full(m, -7, np.int32),
+                     round_status=np.full((m, R), -7, np.int32), lm_iterations=np.full((m, R), -7, np.int32), cost_initial=np.zeros((m, R)),
+                     cost_final=np.zeros((m, R)), proj=np.zeros((max(N, 1), 3)))
+            o["lambda"] = np.zeros((m, R))
+            for k in SLM_INT_OUTPUTS:
+                o[k] = np.full(max(N, 1), -7, np.int32)
+        types = {np.dtype(np.int32): C.c_int32, np.dtype(np.float64): C.c_double, np.dtype(np.uint8): C.c_uint8}
+        f_ = lambda k: _p(o[k], types[o[k].dtype]) if k in o else None
+        q_ = lambda a, t: None if a is None else _p(a, t)
+        self._chk(self.lib.ygz_hip_stereo_local_map_indexed(
+            self._ctx, P, q_(m_pw, C.c_double), q_(m_desc, C.c_uint8), q_(m_dmax, C.c_double), q_(m_nrm, C.c_double), len(ll), stride,
+            _p(lp, C.c_int32), _p(ll, C.c_int32), n, _p(sl, C.c_int32), _p(li, C.c_int32), _p(T0, C.c_double), q_(pr, C.c_int32),
+            C.byref(p), f_("T_out"), f_("status"), *[f_(k) for k in names]), "stereo_local_map_indexed")
+        per_point = SLM_INT_OUTPUTS + ("proj",)
+        out = {k: (v[:N] if k in per_point else v[:n]) for k, v in o.items()}
+        out["offsets"] = np.array(off, np.int64)
+        return out
 
     # ---- BoW
     def vocab_load(self, blob):

@@ -16,6 +16,8 @@
 // FP64 in the stated order; integer atomics on LDS counters only; no floating-point atomic, no wait for another workgroup, no scratch, no
 // environment switch; every loop is a `for` over a count known at entry; every index read from a key or from the prior is checked against
 // n_kp / n_pt before it addresses memory.  One packed upload, five launches, one copy back, one wait.
+// The host body, ygz_slm_run, also serves ygz_hip_stereo_local_map_indexed (slm_index.hip, slm_share.h): there the sets are gathered on the
+// device from index lists into one map by a sixth launch in front of these five.
 #include "ygz_internal.h"
 #include "strack_dev.h"
 #include "popt_dev.h"
@@ -24,10 +26,9 @@
 #pragma clang fp contract(off)
 #include "ur_dev.h"
 #include "slot_pose_dev.h"
+#include "slm_share.h"
 
 #define SL_LANES      256
-
-struct SlmSetTab { uint64_t pw, desc, dmax, normal; int32_t n_pt, pad_; };     // byte offsets of a set's arrays in the packed block
 
 struct SlmDev {
     // the resident keypoints [max_frames][cells]
@@ -257,9 +258,33 @@ int ygz_hip_stereo_local_map_slots(ygz_hip_ctx *ctx, int n_sets, const ygz_strac
                                    double *round_cost_final, double *round_lambda, int32_t *match, int32_t *dist, int32_t *level,
                                    int32_t *reason, int32_t *outcome, int32_t *n_cand, int32_t *n_gated, double *proj)
 {
+    SlmSource src;
+    src.n_sets = n_sets; src.sets = sets;
+    const SlmOutputs out = { T_out, status, counts, kp_point, outlier, chi2, inliers, rounds_run, round_status, round_iterations, round_cost_initial,
+                             round_cost_final, round_lambda, match, dist, level, reason, outcome, n_cand, n_gated, proj };
+    return ygz_slm_run(ctx, src, n_frames, slot, set, T, prior, params, out);
+}
+
+}  // extern "C"
+
+// the body of ygz_hip_stereo_local_map_slots and ygz_hip_stereo_local_map_indexed (slm_share.h): `src` holds the sets, or the map and the lists
+int ygz_slm_run(ygz_hip_ctx *ctx, const SlmSource &src, int n_frames, const int32_t *slot, const int32_t *set, const double *T,
+                const int32_t *prior, const ygz_slm_params *params, const SlmOutputs &out)
+{
+    const bool indexed = src.indexed();
+    const int n_sets = src.n_sets;
+    const ygz_strack_points *sets = src.sets;
+    double *T_out = out.T_out, *chi2 = out.chi2, *round_cost_initial = out.round_cost_initial, *round_cost_final = out.round_cost_final;
+    double *round_lambda = out.round_lambda, *proj = out.proj;
+    uint8_t *outlier = out.outlier;
+    int32_t *status = out.status, *counts = out.counts, *kp_point = out.kp_point, *inliers = out.inliers, *rounds_run = out.rounds_run;
+    int32_t *round_status = out.round_status, *round_iterations = out.round_iterations, *match = out.match, *dist = out.dist, *level = out.level;
+    int32_t *reason = out.reason, *outcome = out.outcome, *n_cand = out.n_cand, *n_gated = out.n_gated;
     // every check before the device is touched; the context last, so that a null context refuses a valid call too
-    if (!sets || !slot || !set || !T || !T_out || n_frames < 1 || n_sets < 1) return YGZ_E_INVALID;
-    if (n_frames > YGZ_SLM_MAX_FRAMES || n_sets > YGZ_SLM_MAX_SETS) return YGZ_E_CAPACITY;
+    if (!slot || !set || !T || !T_out || n_frames < 1 || n_sets < 1) return YGZ_E_INVALID;
+    if (indexed ? (!src.list_pt || !src.list_len || src.n_points < 0) : !sets) return YGZ_E_INVALID;
+    if (n_frames > YGZ_SLM_MAX_FRAMES) return YGZ_E_CAPACITY;
+    if (indexed ? (n_sets > YGZ_SLM_MAX_FRAMES || src.n_points > YGZ_MPA_MAX_POINTS) : n_sets > YGZ_SLM_MAX_SETS) return YGZ_E_CAPACITY;
     ygz_slm_params p;
     if (params) p = *params; else ygz_hip_default_slm_params(&p);
     if (!isfinite(p.baseline) || !isfinite(p.th) || !isfinite(p.ratio) || !isfinite(p.r_near) || !isfinite(p.r_wide) || !isfinite(p.cos_near))
@@ -268,21 +293,39 @@ int ygz_hip_stereo_local_map_slots(ygz_hip_ctx *ctx, int n_sets, const ygz_strac
         p.min_edges < 0)
         return YGZ_E_INVALID;
     if (!ygz_pose_params_ok(p.pose)) return YGZ_E_INVALID;
+    if (indexed) {
+        if (src.n_points > 0 && (!src.pw || !src.desc || !src.dmax || !src.normal)) return YGZ_E_INVALID;
+        if (src.stride < 1) return YGZ_E_INVALID;
+    }
     for (int s = 0; s < n_sets; ++s) {
-        if (sets[s].n_pt < 0) return YGZ_E_INVALID;
-        if (sets[s].n_pt > 0 && (!sets[s].pw || !sets[s].pt_desc || !sets[s].pt_dmax || !sets[s].pt_normal)) return YGZ_E_INVALID;
+        if (src.n_pt(s) < 0 || (indexed && src.n_pt(s) > src.stride)) return YGZ_E_INVALID;
+        if (!indexed && sets[s].n_pt > 0 && (!sets[s].pw || !sets[s].pt_desc || !sets[s].pt_dmax || !sets[s].pt_normal)) return YGZ_E_INVALID;
     }
     const size_t F = (size_t)n_frames;
     size_t N = 0;
     int max_pt = 0;
     for (int f = 0; f < n_frames; ++f) {
         if (slot[f] < 0 || set[f] < 0 || set[f] >= n_sets) return YGZ_E_INVALID;
-        N += (size_t)sets[set[f]].n_pt;
-        if (sets[set[f]].n_pt > max_pt) max_pt = sets[set[f]].n_pt;
+        N += (size_t)src.n_pt(set[f]);
+        if (src.n_pt(set[f]) > max_pt) max_pt = src.n_pt(set[f]);
+    }
+    // by index: the lists some frame reads; the others are neither checked nor gathered
+    std::vector<uint8_t> read_(indexed ? (size_t)n_sets : 0, 0);
+    if (indexed) {
+        for (int f = 0; f < n_frames; ++f) read_[(size_t)set[f]] = 1;
+        for (int s = 0; s < n_sets; ++s) {
+            const int32_t *row = src.list_pt + (size_t)s * (size_t)src.stride;
+            for (int i = 0; read_[(size_t)s] && i < src.list_len[s]; ++i)
+                if (row[i] < 0 || row[i] >= src.n_points) return YGZ_E_INVALID;
+        }
     }
     if (N > YGZ_SLM_MAX_PAIRS) return YGZ_E_CAPACITY;
     if (!ygz_all_finite(T, 7 * F)) return YGZ_E_INVALID;
-    for (int s = 0; s < n_sets; ++s) {
+    if (indexed) {
+        const size_t n = (size_t)src.n_points;
+        if (n && (!ygz_all_finite(src.pw, 3 * n) || !ygz_all_finite(src.dmax, n) || !ygz_all_finite(src.normal, 3 * n))) return YGZ_E_INVALID;
+    }
+    for (int s = 0; !indexed && s < n_sets; ++s) {
         const size_t n = (size_t)sets[s].n_pt;
         if (n && (!ygz_all_finite(sets[s].pw, 3 * n) || !ygz_all_finite(sets[s].pt_dmax, n) || !ygz_all_finite(sets[s].pt_normal, 3 * n))) return YGZ_E_INVALID;
     }
@@ -295,7 +338,7 @@ int ygz_hip_stereo_local_map_slots(ygz_hip_ctx *ctx, int n_sets, const ygz_strac
     const size_t Cn = (size_t)ctx->cells, NK = F * Cn;
     if (prior)
         for (size_t f = 0; f < F; ++f) {
-            const int32_t n = sets[set[f]].n_pt, *row = prior + f * Cn;
+            const int32_t n = src.n_pt(set[f]), *row = prior + f * Cn;
             for (size_t j = 0; j < Cn; ++j)
                 if (row[j] < -1 || row[j] >= n) return YGZ_E_INVALID;
         }
@@ -310,7 +353,7 @@ int ygz_hip_stereo_local_map_slots(ygz_hip_ctx *ctx, int n_sets, const ygz_strac
     size_t run = 0;
     for (size_t f = 0; f < F; ++f) {
         ds[f] = ygz_distinct_slot(slots, where, slot[f]);
-        pt_off[f] = (int32_t)run; run += (size_t)sets[set[f]].n_pt;
+        pt_off[f] = (int32_t)run; run += (size_t)src.n_pt(set[f]);
         e_off[f] = (int32_t)(f * Cn);
     }
     const size_t D = slots.size();
@@ -322,7 +365,11 @@ int ygz_hip_stereo_local_map_slots(ygz_hip_ctx *ctx, int n_sets, const ygz_strac
     const size_t o_fset = B.add_n<int32_t>(F), o_ptoff = B.add_n<int32_t>(F), o_off = B.add_n<int32_t>(F);
     const size_t o_tab = B.add_n<SlmSetTab>((size_t)n_sets);
     std::vector<SlmSetTab> tab((size_t)n_sets);
-    for (int s = 0; s < n_sets; ++s) {
+    // by index the map and the lists go up in the sets' place, and the sets' arrays lie behind everything else: k_slm_index fills them
+    const size_t MP = indexed ? (size_t)src.n_points : 0, LS = indexed ? (size_t)n_sets * (size_t)src.stride : 0;
+    const size_t o_mpw = B.add_n<double>(MP * 3), o_mdesc = B.add_n<uint4>(MP * 2), o_mdmax = B.add_n<double>(MP), o_mnrm = B.add_n<double>(MP * 3);
+    const size_t o_lpt = B.add_n<int32_t>(LS);
+    for (int s = 0; !indexed && s < n_sets; ++s) {
         const size_t n = (size_t)sets[s].n_pt;
         tab[(size_t)s].pw = B.add_n<double>(n * 3);
         tab[(size_t)s].desc = B.add_n<uint4>(n * 2);                     // 16-byte aligned: read as two uint4
@@ -351,7 +398,18 @@ int ygz_hip_stereo_local_map_slots(ygz_hip_ctx *ctx, int n_sets, const ygz_strac
     const size_t o_keys = B.add_n<uint4>(N * 2);
     PB.add_edges(B, F, Cn);
     const size_t o_sets = B.add_n<StSetDev>((size_t)n_sets), o_probs = B.add_n<StProbDev>(F);
-    const size_t o_gur = B.add_n<double>(D * Cn), o_taken = B.add_n<uint8_t>(prior ? NK : 0), total = B.end;
+    const size_t o_gur = B.add_n<double>(D * Cn), o_taken = B.add_n<uint8_t>(prior ? NK : 0);
+    int longest = 1;
+    for (int s = 0; indexed && s < n_sets; ++s) {
+        const size_t n = read_[(size_t)s] ? (size_t)src.list_len[s] : 0;
+        tab[(size_t)s].pw = B.add_n<double>(n * 3);
+        tab[(size_t)s].desc = B.add_n<uint4>(n * 2);
+        tab[(size_t)s].dmax = B.add_n<double>(n);
+        tab[(size_t)s].normal = B.add_n<double>(n * 3);
+        tab[(size_t)s].n_pt = (int32_t)n; tab[(size_t)s].pad_ = 0;
+        if ((int)n > longest) longest = (int)n;
+    }
+    const size_t total = B.end;
     YgzBlob blob;
     int rc = ygz_blob_open(ctx, SCR_SLM, total, back_end, &blob);
     if (rc != YGZ_OK) return rc;
@@ -365,7 +423,12 @@ int ygz_hip_stereo_local_map_slots(ygz_hip_ctx *ctx, int n_sets, const ygz_strac
     memcpy(up + o_slots, slots.data(), D * 4); memcpy(up + o_fslot, slot, F * 4); memcpy(up + o_fds, ds.data(), F * 4);
     memcpy(up + o_fset, set, F * 4); memcpy(up + o_ptoff, pt_off.data(), F * 4); memcpy(up + o_off, e_off.data(), F * 4);
     memcpy(up + o_tab, tab.data(), (size_t)n_sets * sizeof(SlmSetTab));
-    for (int s = 0; s < n_sets; ++s) {
+    if (MP) {
+        memcpy(up + o_mpw, src.pw, MP * 24); memcpy(up + o_mdesc, src.desc, MP * 32);
+        memcpy(up + o_mdmax, src.dmax, MP * 8); memcpy(up + o_mnrm, src.normal, MP * 24);
+    }
+    if (LS) memcpy(up + o_lpt, src.list_pt, LS * 4);
+    for (int s = 0; !indexed && s < n_sets; ++s) {
         const size_t n = (size_t)sets[s].n_pt;
         if (!n) continue;
         const SlmSetTab &t = tab[(size_t)s];
@@ -405,6 +468,13 @@ int ygz_hip_stereo_local_map_slots(ygz_hip_ctx *ctx, int n_sets, const ygz_strac
     if (n_sets > widest) widest = n_sets;
     const unsigned bx = (unsigned)ygz_div_up(ctx->cells, SL_LANES), bt = (unsigned)ygz_div_up(widest, SL_LANES);
     const unsigned sx = (unsigned)ygz_div_up(max_pt > 0 ? max_pt : 1, ST_DEV_LANES);
+    if (indexed) {
+        SlmIndexDev X;
+        X.block = dev; X.tab = A.set_tab;
+        X.pw = ygz_at<const double>(dev, o_mpw); X.desc = ygz_at<const uint4>(dev, o_mdesc); X.dmax = ygz_at<const double>(dev, o_mdmax);
+        X.normal = ygz_at<const double>(dev, o_mnrm); X.list_pt = ygz_at<const int32_t>(dev, o_lpt); X.stride = src.stride;
+        src.index(ctx, X, n_sets, longest);
+    }
     YGZ_LAUNCH(ctx, KID_SLM_GATHER, k_slm_gather, dim3(bt, (unsigned)(D + (prior ? F : 0))), dim3(SL_LANES), A);
     YGZ_LAUNCH(ctx, KID_STRACK_SEARCH, k_strack_search, dim3(sx, (unsigned)n_frames), dim3(ST_DEV_LANES), ygz_at<const StIn>(dev, o_in), A.sets,
                A.probs, A.keys, A.n_cand, A.n_gated, A.level, A.reason, A.proj);
@@ -431,5 +501,3 @@ int ygz_hip_stereo_local_map_slots(ygz_hip_ctx *ctx, int n_sets, const ygz_strac
     }
     return YGZ_OK;
 }
-
-}  // extern "C"

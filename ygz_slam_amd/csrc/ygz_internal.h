@@ -219,7 +219,7 @@ struct YgzDeviceGuard {
 // kernel ids for the probe
 enum { KID_BGR2GRAY = 0, KID_PYR_DOWN, KID_FAST_SELECT, KID_COMPACT, KID_DESCRIBE, KID_HAMMING_NN, KID_MATCH_FINALIZE,
        KID_TRACK_LOAD, KID_FDP, KID_ALIGN2D, KID_SPARSE_ALIGN, KID_SCHARR, KID_KLT, KID_KLT_PAD, KID_BA_POSE_PREP, KID_BA_POINTS,
-       KID_BA_POSES, KID_BA_CHI2, KID_POSE_ONLY, KID_BA_LM, KID_BOW_TRANSFORM, KID_BOW_MATCH, KID_DEPTH_TRI, KID_LMAP_MATCH, KID_LMAP_AUX, KID_MATCH_POSTFILTER, KID_TRACK_AUX, KID_DEPTH_FILTER, KID_WINDOW, KID_UNDISTORT, KID_STEREO_MATCH, KID_STEREO_MEDIAN, KID_POSE_OPT, KID_RECTIFY, KID_SMAP_PAIRS, KID_SMAP_KEYFRAME, KID_SRL_GATHER, KID_SRL_RESOLVE, KID_SRL_SETS, KID_SRL_EDGES, KID_SRL_SCATTER, KID_SRL_PICK, KID_PNP_SOLVE, KID_PNP_SCORE, KID_PNP_SELECT, KID_SRK_GATHER, KID_SRK_RESOLVE, KID_SRK_SCATTER, KID_SLM_GATHER, KID_SLM_RESOLVE, KID_SLM_SCATTER, KID_LMS_VOTE, KID_LMS_POINTS, KID_LMS_PLACE, KID_LMS_PRIOR, KID_SVO_GATHER, KID_SVO_RESOLVE, KID_SVO_SCATTER, KID_LFUSE_SEARCH, KID_STRACK_SEARCH, KID_COUNT };
+       KID_BA_POSES, KID_BA_CHI2, KID_POSE_ONLY, KID_BA_LM, KID_BOW_TRANSFORM, KID_BOW_MATCH, KID_DEPTH_TRI, KID_LMAP_MATCH, KID_LMAP_AUX, KID_MATCH_POSTFILTER, KID_TRACK_AUX, KID_DEPTH_FILTER, KID_WINDOW, KID_UNDISTORT, KID_STEREO_MATCH, KID_STEREO_MEDIAN, KID_POSE_OPT, KID_RECTIFY, KID_SMAP_PAIRS, KID_SMAP_KEYFRAME, KID_SRL_GATHER, KID_SRL_RESOLVE, KID_SRL_SETS, KID_SRL_EDGES, KID_SRL_SCATTER, KID_SRL_PICK, KID_PNP_SOLVE, KID_PNP_SCORE, KID_PNP_SELECT, KID_MPA_ATTR, KID_SLM_INDEX, KID_SRK_GATHER, KID_SRK_RESOLVE, KID_SRK_SCATTER, KID_SLM_GATHER, KID_SLM_RESOLVE, KID_SLM_SCATTER, KID_LMS_VOTE, KID_LMS_POINTS, KID_LMS_PLACE, KID_LMS_PRIOR, KID_SVO_GATHER, KID_SVO_RESOLVE, KID_SVO_SCATTER, KID_LFUSE_SEARCH, KID_STRACK_SEARCH, KID_COUNT };
 
 #define YGZ_LAUNCH(ctx, kid, kern, grid, block, ...)                                                         \
     do { const bool pr_ = (ctx)->probe_id == (kid) && (ctx)->probe_used + 2 <= (int)(ctx)->probe_ev.size();    \
@@ -265,7 +265,8 @@ static_assert(SCR_GEN_0 == 16 && SCR_INIT == 27 && SCR_STEREO == 36 && SCR_SBA =
 static_assert(SCR_LAST < YGZ_N_SCRATCH, "ygz_hip_ctx::scratch holds every id");
 static_assert(SCR_SRK == 44 && SCR_SRK < YGZ_N_SCRATCH, "the id behind SCR_LAST has a buffer too");
 // id 45 is the packed block of ygz_hip_stereo_relocalize_slots: a constant in srl.hip, outside this enum, whose text tests pin; id 46 is the packed block of
-// ygz_hip_local_map_select, a constant in lms.hip in the same way; the next id is 47
+// ygz_hip_local_map_select, a constant in lms.hip in the same way; id 47 is that of ygz_hip_map_point_attributes, a constant in mpa.hip: the
+// table is full, and the next block needs a larger YGZ_N_SCRATCH
 
 int ygz_scratch(ygz_hip_ctx *ctx, int id, size_t bytes, void **out);
 // the RANSAC sample sets of cv::RNG's scheme (init.hip): a fresh generator (state 0xffffffff), per iteration k distinct indices of [0, n) by the
