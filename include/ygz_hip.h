@@ -85,7 +85,9 @@ extern "C" {
  * Still 6: local-map selection added (ygz_lms_params, ygz_hip_default_lms_params, ygz_hip_local_map_select) -- no existing argument list
  * changed.
  * Still 6: map-point attributes and local-map tracking on an indexed map added (ygz_hip_map_point_attributes,
- * ygz_hip_stereo_local_map_indexed) -- no existing argument list changed. */
+ * ygz_hip_stereo_local_map_indexed) -- no existing argument list changed.
+ * Still 6: the resident map added (ygz_hip_map, ygz_map_arrays, ygz_map_info, ygz_hip_map_create, _destroy, _info, _upload, _update,
+ * _download, ygz_hip_stereo_local_map_resident) -- no existing argument list changed. */
 #define YGZ_HIP_ABI_VERSION 6
 
 typedef struct ygz_hip_ctx ygz_hip_ctx;
@@ -1750,6 +1752,87 @@ int  ygz_hip_stereo_local_map_indexed(ygz_hip_ctx *ctx, int n_points, const doub
                                       int32_t *round_iterations, double *round_cost_initial, double *round_cost_final, double *round_lambda,
                                       int32_t *match, int32_t *dist, int32_t *level, int32_t *reason, int32_t *outcome, int32_t *n_cand,
                                       int32_t *n_gated, double *proj);
+
+/* ---- the resident map -- the map of the three calls above with a home in device memory, and local-map tracking on it in ONE call
+ * (DESIGN.md section 36).  A ygz_hip_map belongs to the context it was created with and owns its device buffers (its own allocations, grown
+ * by the rule of the context's scratch buffers; the context's table of scratch buffers is not used).  Several maps may live in one context;
+ * ygz_hip_destroy frees the ones still alive.  Every call below refuses a null map or a map of another context with YGZ_E_INVALID, behind
+ * its own argument checks and the null context, and before the device is touched.
+ * ygz_map_arrays carries exactly what the three calls take, in their layouts: the selection side (n_keyframes, kf_bad, n_cov, cov, n_points,
+ * offsets, kf, feat, pt_bad or NULL) as ygz_hip_local_map_select; the attribute side (n_centres, centre [n_centres][3], a_offsets
+ * [n_points + 1], a_kf, a_level: the point-major CSR of ygz_hip_map_point_attributes with rows in the caller's order); the tracking side (pw
+ * [n_points][3], pt_desc [n_points][32], pt_has_desc [n_points] or NULL for "every point has one").
+ * sizeof: ygz_map_arrays 120, ygz_map_info 40. */
+typedef struct ygz_hip_map ygz_hip_map;
+typedef struct {
+    int32_t n_keyframes, n_cov, n_points, n_centres;
+    const uint8_t *kf_bad; const int32_t *cov; const int32_t *offsets, *kf, *feat; const uint8_t *pt_bad;
+    const double *centre; const int32_t *a_offsets, *a_kf, *a_level;
+    const double *pw; const uint8_t *pt_desc, *pt_has_desc;
+} ygz_map_arrays;
+typedef struct {
+    int32_t n_keyframes, n_cov, n_points, n_obs, n_centres, n_rows;   /* of the resident map; zeros before the first upload */
+    int32_t uploads, updates;                                         /* accepted ones since ygz_hip_map_create */
+    uint64_t resident_bytes;                                          /* device memory the map holds, its call buffers included */
+} ygz_map_info;
+int  ygz_hip_map_create(ygz_hip_ctx *ctx, ygz_hip_map **map);         /* YGZ_E_INVALID for a null map or context */
+int  ygz_hip_map_destroy(ygz_hip_ctx *ctx, ygz_hip_map *map);         /* waits for the stream, then frees */
+int  ygz_hip_map_info(ygz_hip_ctx *ctx, ygz_hip_map *map, ygz_map_info *info);
+/* Makes the whole map resident: the arrays go up, the keyframe-major index of the selection is built beside the upload and stays on the
+ * device, and k_mpa_attr computes the attributes there.  dmax [n_points], normal [n_points][3] and state [n_points] come back when they are
+ * not NULL, bit-identical to ygz_hip_map_point_attributes on the same arrays.  A later upload may be larger or smaller.  One upload, one
+ * launch, one copy back, one wait.  Checked in this order, all before the device is touched: the map-side checks of
+ * ygz_hip_local_map_select in its order (null kf_bad, offsets, kf or feat, null cov with n_cov > 0, n_keyframes or n_points < 1, n_cov < 0;
+ * the capacities; the offsets; the observations; the cov entries), then those of ygz_hip_map_point_attributes in its order with n_centres
+ * for n_keyframes (dmax, normal and state may be null), then YGZ_E_INVALID for a null pt_desc; last the null context and the map.  A refused
+ * upload leaves the resident map as it was, and usable. */
+int  ygz_hip_map_upload(ygz_hip_ctx *ctx, ygz_hip_map *map, const ygz_map_arrays *m, double *dmax, double *normal, int32_t *state);
+/* The delta after a bundle adjustment or a culling; it changes no observation (a new keyframe or a new or erased observation is a new
+ * upload).  n_pt point rows: pt_idx [n_pt] and, each NULL for "keep", pw [n_pt][3], pt_desc [n_pt][32], pt_bad [n_pt], pt_has_desc [n_pt];
+ * n_kf keyframe rows kf_idx, kf_bad; n_c centre rows c_idx, centre [n_c][3].  k_rmap_scatter (a lane per row) writes them, then k_mpa_attr
+ * recomputes the attributes of the whole map: afterwards the resident state is bit-identical to a fresh upload of the updated arrays.  One
+ * upload, two launches, one wait.  Checked in this order, all before the device is touched: the null context and the map; YGZ_E_STATE for a
+ * map without an upload; YGZ_E_INVALID for a negative count, a null index array with a count above 0, an index out of range or twice within
+ * one array, a null kf_bad with n_kf > 0 or a null centre with n_c > 0, a pw or centre that is not finite.  A refused update writes
+ * nothing. */
+int  ygz_hip_map_update(ygz_hip_ctx *ctx, ygz_hip_map *map, int n_pt, const int32_t *pt_idx, const double *pw, const uint8_t *pt_desc,
+                        const uint8_t *pt_bad, const uint8_t *pt_has_desc, int n_kf, const int32_t *kf_idx, const uint8_t *kf_bad, int n_c,
+                        const int32_t *c_idx, const double *centre);
+/* A test aid: the arrays as the device holds them, any of them may be NULL: pw, pt_desc, pt_bad, pt_has_desc, kf_bad [n_keyframes], centre
+ * [n_centres][3], dmax, normal, state.  YGZ_E_STATE for a map without an upload. */
+int  ygz_hip_map_download(ygz_hip_ctx *ctx, ygz_hip_map *map, double *pw, uint8_t *pt_desc, uint8_t *pt_bad, uint8_t *pt_has_desc,
+                          uint8_t *kf_bad, double *centre, double *dmax, double *normal, int32_t *state);
+/* Local-map selection and tracking of n_frames resident frames on the resident map.  Only the frames' entries (fr_off, fr_pt as
+ * ygz_hip_local_map_select takes them), their slots and their poses go up.  For every accepted input every output is bit-identical to:
+ *   1 ygz_hip_local_map_select on the map's selection arrays and the frames' entries (the cut at max_points happens here: a cut point is not
+ *     re-admitted when a refused one leaves);
+ *   2 point p is refused when state[p] != 1 (the resident attributes) or pt_has_desc[p] == 0;
+ *   3 the refused entries leave every frame's list, the order of the rest is kept; moved[i] is an entry's new position or -1; n_removed[f]
+ *     counts them; local_pt is padded with -1;
+ *   4 prior[f][j] = moved[fr_prior[fr_off[f] + j]] when j is below the frame's number of entries and that fr_prior is >= 0, otherwise -1,
+ *     for j up to the context's cells;
+ *   5 ygz_hip_stereo_local_map_indexed on the resident map with list[f] = f, the filtered lists and that prior.
+ * Outputs, any may be NULL except T_out: votes, ref, n_voters, n_local, local_kf, n_cut as the selection writes them; n_pt [n_frames] and
+ * local_pt [n_frames][max_points] AFTER the filter; n_removed [n_frames]; prior [n_frames][cells]; then the outputs of
+ * ygz_hip_stereo_local_map_indexed, the per-point ones laid out [n_frames][max_points] (proj [n_frames][max_points][3]): the first n_pt[f]
+ * entries of row f are written, the rest are left untouched.  Two uploads (the tracking block, the frames' entries), eleven launches
+ * (k_lms_vote, k_lms_points, k_lms_place, k_lms_prior, k_rmap_filter, k_slm_index and the five of ygz_hip_stereo_local_map_slots; k_lms_prior
+ * is left out when no frame has an entry), two copies back, one wait; the host decides nothing in between and the map is not sent.
+ * Checked in this order, all before the device is touched: YGZ_E_INVALID for a null slot, T, fr_off, fr_pt or T_out or n_frames < 1;
+ * YGZ_E_CAPACITY for n_frames above YGZ_LMS_MAX_FRAMES; YGZ_E_INVALID for max_keyframes outside [1, YGZ_LMS_MAX_KEYFRAMES] or max_points < 1;
+ * YGZ_E_CAPACITY for n_frames * max_points above YGZ_SLM_MAX_PAIRS; YGZ_E_INVALID for fr_off[0] != 0 or a decreasing offset; YGZ_E_CAPACITY for
+ * a frame of more than YGZ_LMS_MAX_FEATURES entries; YGZ_E_INVALID for a null context or the map; YGZ_E_STATE for a map without an upload;
+ * YGZ_E_CAPACITY for n_frames * n_keyframes above YGZ_COVIS_MAX_CELLS; YGZ_E_INVALID for an fr_pt entry outside [-1, n_points) or a frame
+ * with more entries than cells; then the parameter, pose and context checks of ygz_hip_stereo_local_map_indexed in its order.  A refused
+ * call writes nothing. */
+int  ygz_hip_stereo_local_map_resident(ygz_hip_ctx *ctx, ygz_hip_map *map, int n_frames, const int32_t *slot, const double *T,
+                                       const int32_t *fr_off, const int32_t *fr_pt, const ygz_lms_params *lms, const ygz_slm_params *params,
+                                       int32_t *votes, int32_t *ref, int32_t *n_voters, int32_t *n_local, int32_t *local_kf, int32_t *n_cut,
+                                       int32_t *n_pt, int32_t *local_pt, int32_t *n_removed, int32_t *prior, double *T_out, int32_t *status,
+                                       int32_t *counts, int32_t *kp_point, uint8_t *outlier, double *chi2, int32_t *inliers,
+                                       int32_t *rounds_run, int32_t *round_status, int32_t *round_iterations, double *round_cost_initial,
+                                       double *round_cost_final, double *round_lambda, int32_t *match, int32_t *dist, int32_t *level,
+                                       int32_t *reason, int32_t *outcome, int32_t *n_cand, int32_t *n_gated, double *proj);
 
 #ifdef __cplusplus
 }

@@ -66,10 +66,8 @@ def r256(x):
     return (x + 255) // 256 * 256
 
 
-def main():
-    out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "lmt_bench.json")
-    rng = np.random.default_rng(31)
-    ctx = _lib.HipContext(width=W, height=H, levels=3, max_frames=SLOTS)
+def resident_frames(ctx, rng):
+    """SLOTS resident frames: detected keypoints of a texture, 60 % with a depth; the keypoint counts"""
     tex = sr.texture(W + 8 * SLOTS, H, 5)
     for s in range(SLOTS):
         ctx.upload_gray(s, np.ascontiguousarray(tex[:, 8 * s:8 * s + W]))
@@ -79,7 +77,12 @@ def main():
     for s in range(SLOTS):
         n = int(counts[s])
         ctx.set_keypoint_depths(s, rng.uniform(2, 10, n), (rng.uniform(size=n) < 0.6).astype(np.uint8))
-    # the map
+    return counts
+
+
+def make_map(rng):
+    """the map (also tools/rmap_bench.py's): center, pw, off, kf, level as tests/mpa_ref.py names them, and per point the first observer
+    (start) and the number of observers (n_obs), which are consecutive keyframes"""
     n_obs = np.clip(1 + rng.poisson(MEAN_OBS - 1.0, N_POINTS), 1, K).astype(np.int64)
     off = np.concatenate([[0], np.cumsum(n_obs)]).astype(np.int32)
     start = rng.integers(0, K - n_obs + 1)
@@ -89,7 +92,16 @@ def main():
     z = rng.uniform(2, 10, N_POINTS)
     px = np.stack([rng.uniform(0, W, N_POINTS), rng.uniform(0, H, N_POINTS)], 1)
     pw = np.stack([(px[:, 0] - CX) / FX * z, (px[:, 1] - CY) / FX * z, z], 1)
-    m = dict(center=center, pw=pw, off=off, kf=kf, level=level)
+    return dict(center=center, pw=pw, off=off, kf=kf, level=level, start=start, n_obs=n_obs)
+
+
+def main():
+    out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "lmt_bench.json")
+    rng = np.random.default_rng(31)
+    ctx = _lib.HipContext(width=W, height=H, levels=3, max_frames=SLOTS)
+    counts = resident_frames(ctx, rng)
+    m = make_map(rng)
+    center, pw, off, kf, level = m["center"], m["pw"], m["off"], m["kf"], m["level"]
     att = ctx.map_point_attributes(center, pw, off, kf, level)
     ref = mr.attributes(m)
     mr.same(att, ref)

@@ -698,6 +698,31 @@ def slm_indexed_argtypes(lib):
                                                      ip, ip, ip, bp, dp, ip, ip, ip, ip, dp, dp, dp, ip, ip, ip, ip, ip, ip, ip, dp]
 
 
+class MapArrays(C.Structure):
+    _fields_ = [("n_keyframes", C.c_int32), ("n_cov", C.c_int32), ("n_points", C.c_int32), ("n_centres", C.c_int32),
+                ("kf_bad", C.POINTER(C.c_uint8)), ("cov", C.POINTER(C.c_int32)), ("offsets", C.POINTER(C.c_int32)), ("kf", C.POINTER(C.c_int32)),
+                ("feat", C.POINTER(C.c_int32)), ("pt_bad", C.POINTER(C.c_uint8)), ("centre", C.POINTER(C.c_double)),
+                ("a_offsets", C.POINTER(C.c_int32)), ("a_kf", C.POINTER(C.c_int32)), ("a_level", C.POINTER(C.c_int32)),
+                ("pw", C.POINTER(C.c_double)), ("pt_desc", C.POINTER(C.c_uint8)), ("pt_has_desc", C.POINTER(C.c_uint8))]
+
+
+class MapInfo(C.Structure):
+    _fields_ = [("n_keyframes", C.c_int32), ("n_cov", C.c_int32), ("n_points", C.c_int32), ("n_obs", C.c_int32), ("n_centres", C.c_int32),
+                ("n_rows", C.c_int32), ("uploads", C.c_int32), ("updates", C.c_int32), ("resident_bytes", C.c_uint64)]
+
+
+def rmap_argtypes(lib):
+    ip, dp, bp, vp = C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.c_void_p
+    lib.ygz_hip_map_create.argtypes = [vp, C.POINTER(vp)]
+    lib.ygz_hip_map_destroy.argtypes = [vp, vp]
+    lib.ygz_hip_map_info.argtypes = [vp, vp, C.POINTER(MapInfo)]
+    lib.ygz_hip_map_upload.argtypes = [vp, vp, C.POINTER(MapArrays), dp, dp, ip]
+    lib.ygz_hip_map_update.argtypes = [vp, vp, C.c_int, ip, dp, bp, bp, bp, C.c_int, ip, bp, C.c_int, ip, dp]
+    lib.ygz_hip_map_download.argtypes = [vp, vp, dp, bp, bp, bp, bp, dp, dp, dp, ip]
+    lib.ygz_hip_stereo_local_map_resident.argtypes = [vp, vp, C.c_int, ip, dp, ip, ip, C.POINTER(LmsParams), C.POINTER(SlmParams)] + [ip] * 10 + [
+        dp, ip, ip, ip, bp, dp, ip, ip, ip, ip, dp, dp, dp, ip, ip, ip, ip, ip, ip, ip, dp]
+
+
 # every symbol include/ygz_hip.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
     "ygz_hip_default_params", "ygz_hip_create", "ygz_hip_destroy", "ygz_hip_synchronize", "ygz_hip_join", "ygz_hip_set_overlap", "ygz_hip_error_string",
@@ -743,6 +768,8 @@ ABI_SYMBOLS = [
     "ygz_hip_default_srl_params", "ygz_hip_stereo_relocalize_slots",
     "ygz_hip_default_lms_params", "ygz_hip_local_map_select",
     "ygz_hip_map_point_attributes", "ygz_hip_stereo_local_map_indexed",
+    "ygz_hip_map_create", "ygz_hip_map_destroy", "ygz_hip_map_info", "ygz_hip_map_upload", "ygz_hip_map_update", "ygz_hip_map_download",
+    "ygz_hip_stereo_local_map_resident",
 ]
 INIT_SYMBOLS = ["ygz_hip_default_init_params", "ygz_hip_initialize", "ygz_hip_init_sample_sets", "ygz_hip_init_hypotheses", "ygz_hip_init_reconstruct"]
 INIT_NONE, INIT_H, INIT_F = 0, 1, 2
@@ -823,6 +850,11 @@ LMS_OUTPUTS = ("votes", "ref", "n_voters", "n_local", "local_kf", "n_pt", "n_cut
 
 MPA_SYMBOLS = ["ygz_hip_map_point_attributes", "ygz_hip_stereo_local_map_indexed"]
 MPA_MAX_POINTS, MPA_MAX_LEVEL = 1048576, 30
+
+RMAP_SYMBOLS = ["ygz_hip_map_create", "ygz_hip_map_destroy", "ygz_hip_map_info", "ygz_hip_map_upload", "ygz_hip_map_update", "ygz_hip_map_download",
+                "ygz_hip_stereo_local_map_resident"]
+RMAP_SELECT_OUTPUTS = ("votes", "ref", "n_voters", "n_local", "local_kf", "n_cut", "n_pt", "local_pt", "n_removed", "prior")
+RMAP_DOWNLOAD = ("pw", "pt_desc", "pt_bad", "pt_has_desc", "kf_bad", "centre", "dmax", "normal", "state")
 
 POPT_SYMBOLS = ["ygz_hip_default_pose_opt_params", "ygz_hip_optimize_pose_stereo"]
 POPT_FAILED, POPT_CONVERGED, POPT_MAX_ITERATIONS, POPT_STALLED = range(4)
@@ -2620,6 +2652,59 @@ class HipContext:
         out["offsets"] = np.array(off, np.int64)
         return out
 
+    # ---- the resident map
+
+    def map_create(self):
+        """a resident map of this context (ygz_hip_map_create): see ResidentMap"""
+        return ResidentMap(self)
+
+    def stereo_local_map_resident(self, rmap, slots, T, frame_offsets, frame_points, lms=None, params=None, outputs=True, fill=None, **fields):
+        """local-map selection and tracking of resident frames on a resident map in one device call (ygz_hip_stereo_local_map_resident).
+        frame_offsets [F + 1] and frame_points [E] as local_map_select takes them; lms: dict of ygz_lms_params fields; params / fields: the
+        ygz_slm_params.  The per-point outputs are [F, max_points] (proj [F, max_points, 3]); row f holds n_pt[f] entries, the rest keep the
+        fill value.  fill: dict name -> value the outputs are pre-filled with (tests)."""
+        p = params if params is not None else self.default_slm_params(**fields)
+        lms_argtypes(self.lib)
+        rmap_argtypes(self.lib)
+        q = LmsParams()
+        self.lib.ygz_hip_default_lms_params(C.byref(q))
+        for name, v in (lms or {}).items():
+            getattr(q, name)
+            setattr(q, name, v)
+        sl = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        fo, fp = np.ascontiguousarray(frame_offsets, np.int32).reshape(-1), np.ascontiguousarray(frame_points, np.int32).reshape(-1)
+        n, c, R, K, mp = len(sl), self.cells, POPT_MAX_ROUNDS, max(rmap.info()["n_keyframes"], 1), max(int(q.max_points), 1)
+        if len(fo) != n + 1:
+            raise ValueError("frame_offsets has one entry per frame and one more")
+        T0 = np.ascontiguousarray(T, np.float64).reshape(n, 7)
+        m = max(n, 1)
+        o = dict(T_out=np.zeros((m, 7)), status=np.full(m, -7, np.int32))
+        sel = dict(votes=(m, K), ref=(m,), n_voters=(m,), n_local=(m,), local_kf=(m, K), n_cut=(m,), n_pt=(m,), local_pt=(m, mp), n_removed=(m,),
+                   prior=(m, c))
+        names = ("counts", "kp_point", "outlier", "chi2", "inliers", "rounds_run", "round_status", "lm_iterations", "cost_initial", "cost_final",
+                 "lambda") + SLM_INT_OUTPUTS + ("proj",)
+        if outputs:
+            for k, shp in sel.items():
+                o[k] = np.full(shp, -7, np.int32)
+            o.update(counts=np.full((m, 8), -7, np.int32), kp_point=np.full((m, c), -7, np.int32), outlier=np.full((m, c), 7, np.uint8),
+                     chi2=np.zeros((m, c)), inliers=np.full(m, -7, np.int32), rounds_run=np.full(m, -7, np.int32),
+                     round_status=np.full((m, R), -7, np.int32), lm_iterations=np.full((m, R), -7, np.int32), cost_initial=np.zeros((m, R)),
+                     cost_final=np.zeros((m, R)), proj=np.full((m, mp, 3), -7.0))
+            o["lambda"] = np.zeros((m, R))
+            for k in SLM_INT_OUTPUTS:
+                o[k] = np.full((m, mp), -7, np.int32)
+        for k, v in (fill or {}).items():
+            o[k][...] = v
+        types = {np.dtype(np.int32): C.c_int32, np.dtype(np.float64): C.c_double, np.dtype(np.uint8): C.c_uint8}
+        f_ = lambda k: _p(o[k], types[o[k].dtype]) if k in o else None
+        fp1 = fp if len(fp) else np.zeros(1, np.int32)
+        rc = self.lib.ygz_hip_stereo_local_map_resident(
+            self._ctx, rmap._map, n, _p(sl, C.c_int32), _p(T0, C.c_double), _p(fo, C.c_int32), _p(fp1, C.c_int32), C.byref(q), C.byref(p),
+            *[f_(k) for k in RMAP_SELECT_OUTPUTS], f_("T_out"), f_("status"), *[f_(k) for k in names])
+        self.last_outputs = o                                     # what a refused call left in the arrays (tests)
+        self._chk(rc, "stereo_local_map_resident")
+        return {k: v[:n] for k, v in o.items()}
+
     # ---- BoW
     def vocab_load(self, blob):
         buf = np.frombuffer(blob, np.uint8).copy()
@@ -2900,3 +2985,76 @@ class KeyframeDatabase:
         self._ctx._chk(self.lib.ygz_hip_kfdb_query(self._db, len(vectors), _p(off, C.c_int32), _p(word, C.c_int32), _p(weight, C.c_double),
                                                    _p(common, C.c_int32), _p(score, C.c_double)), "kfdb_query")
         return common, score
+
+
+class ResidentMap:
+    """a map that stays in device memory between calls (ygz_hip_map_*).  It belongs to its HipContext and dies with it."""
+
+    def __init__(self, ctx):
+        rmap_argtypes(ctx.lib)
+        self.ctx, self.lib = ctx, ctx.lib
+        h = C.c_void_p()
+        ctx._chk(self.lib.ygz_hip_map_create(ctx._ctx, C.byref(h)), "map_create")
+        self._map = h
+
+    def destroy(self):
+        if self._map is not None:
+            h, self._map = self._map, None
+            self.ctx._chk(self.lib.ygz_hip_map_destroy(self.ctx._ctx, h), "map_destroy")
+
+    def info(self):
+        i = MapInfo()
+        self.ctx._chk(self.lib.ygz_hip_map_info(self.ctx._ctx, self._map, C.byref(i)), "map_info")
+        return {name: int(getattr(i, name)) for name, _ in MapInfo._fields_}
+
+    @staticmethod
+    def pack(m):
+        """the ygz_map_arrays of a dict with its keys (pt_bad and pt_has_desc optional), and the arrays that keep its pointers alive"""
+        t = dict(kf_bad=np.uint8, cov=np.int32, offsets=np.int32, kf=np.int32, feat=np.int32, pt_bad=np.uint8, centre=np.float64,
+                 a_offsets=np.int32, a_kf=np.int32, a_level=np.int32, pw=np.float64, pt_desc=np.uint8, pt_has_desc=np.uint8)
+        ct = {np.uint8: C.c_uint8, np.int32: C.c_int32, np.float64: C.c_double}
+        keep = {k: np.ascontiguousarray(m[k], t[k]) for k in t if m.get(k) is not None}
+        K = len(keep["kf_bad"].reshape(-1)) if "kf_bad" in keep else int(m.get("n_keyframes", 0))
+        a = MapArrays()
+        a.n_keyframes = int(m.get("n_keyframes", K))
+        a.n_cov = int(m.get("n_cov", keep["cov"].reshape(max(K, 1), -1).shape[1] if "cov" in keep else 0))
+        a.n_points = int(m.get("n_points", len(keep["offsets"].reshape(-1)) - 1 if "offsets" in keep else 0))
+        a.n_centres = int(m.get("n_centres", len(keep["centre"].reshape(-1)) // 3 if "centre" in keep else 0))
+        for k in t:
+            if k in keep:
+                if keep[k].size == 0:
+                    keep[k] = np.zeros(3, t[k])
+                setattr(a, k, _p(keep[k], ct[t[k]]))
+        return a, keep
+
+    def upload(self, m, outputs=True):
+        """the whole map (ygz_hip_map_upload): m is a dict with the fields of ygz_map_arrays.  dict of dmax, normal, state as the device
+        computed them (outputs False: nothing comes back)"""
+        a, keep = self.pack(m)
+        P = max(int(a.n_points), 1)
+        o = dict(dmax=np.full(P, -7.0), normal=np.full((P, 3), -7.0), state=np.full(P, -7, np.int32)) if outputs else {}
+        self.ctx._chk(self.lib.ygz_hip_map_upload(self.ctx._ctx, self._map, C.byref(a), _p(o["dmax"], C.c_double) if o else None,
+                                                  _p(o["normal"], C.c_double) if o else None, _p(o["state"], C.c_int32) if o else None),
+                      "map_upload")
+        return o
+
+    def update(self, pt_idx=(), pw=None, pt_desc=None, pt_bad=None, pt_has_desc=None, kf_idx=(), kf_bad=None, c_idx=(), centre=None):
+        """the delta after a bundle adjustment or a culling (ygz_hip_map_update); a None array keeps what the map holds"""
+        arr = lambda a, t: None if a is None else np.ascontiguousarray(a, t).reshape(-1)
+        pi, ki, ci = arr(pt_idx, np.int32), arr(kf_idx, np.int32), arr(c_idx, np.int32)
+        x, d, b, h = arr(pw, np.float64), arr(pt_desc, np.uint8), arr(pt_bad, np.uint8), arr(pt_has_desc, np.uint8)
+        kb, cc = arr(kf_bad, np.uint8), arr(centre, np.float64)
+        q = lambda a, t: None if a is None or len(a) == 0 else _p(a, t)
+        self.ctx._chk(self.lib.ygz_hip_map_update(self.ctx._ctx, self._map, len(pi), q(pi, C.c_int32), q(x, C.c_double), q(d, C.c_uint8),
+                                                  q(b, C.c_uint8), q(h, C.c_uint8), len(ki), q(ki, C.c_int32), q(kb, C.c_uint8), len(ci),
+                                                  q(ci, C.c_int32), q(cc, C.c_double)), "map_update")
+
+    def download(self):
+        """the arrays as the device holds them (ygz_hip_map_download): dict of RMAP_DOWNLOAD"""
+        i = self.info()
+        P, K, Kc = max(i["n_points"], 1), max(i["n_keyframes"], 1), max(i["n_centres"], 1)
+        o = dict(pw=np.zeros((P, 3)), pt_desc=np.zeros((P, 32), np.uint8), pt_bad=np.zeros(P, np.uint8), pt_has_desc=np.zeros(P, np.uint8),
+                 kf_bad=np.zeros(K, np.uint8), centre=np.zeros((Kc, 3)), dmax=np.zeros(P), normal=np.zeros((P, 3)), state=np.zeros(P, np.int32))
+        types = {np.dtype(np.int32): C.c_int32, np.dtype(np.float64): C.c_double, np.dtype(np.uint8): C.c_uint8}
+        self.ctx._chk(self.lib.ygz_hip_map_download(self.ctx._ctx, self._map, *[_p(o[k], types[o[k].dtype]) for k in RMAP_DOWNLOAD]), "map_download")
+        return o

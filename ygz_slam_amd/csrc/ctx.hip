@@ -322,6 +322,7 @@ void ygz_hip_destroy(ygz_hip_ctx *ctx)
     ygz_kf_store_free(ctx);
     ygz_undistort_free(ctx);
     ygz_rectify_free(ctx);
+    ygz_rmap_free_all(ctx);
     if (ctx->stage) (void)hipHostFree(ctx->stage);
     if (ctx->depth_img) (void)hipFree(ctx->depth_img);
     if (ctx->ev_xctx) (void)hipEventDestroy(ctx->ev_xctx);
@@ -520,7 +521,7 @@ static const char *const k_kernel_names[KID_COUNT] = {
     "k_find_direct_projection", "k_align2d", "k_sparse_align", "k_scharr", "k_klt", "k_klt_pad", "k_ba_pose_prep", "k_ba_points", "k_ba_final",
     "k_ba_chi2", "k_pose_only_ba", "k_ba_lm", "k_bow_transform", "k_bow_match", "k_depth_from_triangulation", "k_lmap_match", "k_lmap_aux",
     "k_match_postfilter", "k_track_aux", "k_depth_filter", "k_window", "k_undistort", "k_stereo_match", "k_stereo_median", "k_pose_opt", "k_rectify",
-    "k_smap_pairs", "k_smap_keyframe", "k_srl_gather", "k_srl_resolve", "k_srl_sets", "k_srl_edges", "k_srl_scatter", "k_srl_pick", "k_pnp_solve", "k_pnp_score", "k_pnp_select", "k_mpa_attr", "k_slm_index", "k_srk_gather", "k_srk_resolve", "k_srk_scatter", "k_slm_gather", "k_slm_resolve", "k_slm_scatter", "k_lms_vote", "k_lms_points", "k_lms_place", "k_lms_prior", "k_svo_gather", "k_svo_resolve", "k_svo_scatter", "k_lfuse_search", "k_strack_search" };
+    "k_smap_pairs", "k_smap_keyframe", "k_srl_gather", "k_srl_resolve", "k_srl_sets", "k_srl_edges", "k_srl_scatter", "k_srl_pick", "k_pnp_solve", "k_pnp_score", "k_pnp_select", "k_mpa_attr", "k_slm_index", "k_rmap_filter", "k_rmap_scatter", "k_srk_gather", "k_srk_resolve", "k_srk_scatter", "k_slm_gather", "k_slm_resolve", "k_slm_scatter", "k_lms_vote", "k_lms_points", "k_lms_place", "k_lms_prior", "k_svo_gather", "k_svo_resolve", "k_svo_scatter", "k_lfuse_search", "k_strack_search" };
 
 int ygz_hip_probe_begin(ygz_hip_ctx *ctx, const char *kernel_name, int max_launches)
 {

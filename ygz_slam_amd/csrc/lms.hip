@@ -22,6 +22,7 @@
 // no scratch memory.  The arithmetic is that of tests/lms_ref.c, bit for bit.  Every index a kernel forms was validated by the entry point.
 #include "ygz_internal.h"
 #include "lms_index.h"
+#include "lms_dev.h"
 #include <algorithm>
 #include <string.h>
 #pragma clang fp contract(off)
@@ -39,15 +40,6 @@ namespace {
 #define LMS_NONE  0xFFFF
 #define LMS_GRID_RANKS 256                       // workgroups a frame's ranks are dealt to
 static_assert(YGZ_LMS_MAX_COV == LMS_ROW && YGZ_LMS_MAX_KEYFRAMES <= 4096, "a rank fits the 12 bits under the vote");
-
-struct LmsDev {
-    int K, C, max_kf, max_pt;
-    const uint8_t *kf_bad, *pt_bad;
-    const int32_t *cov, *offsets, *obs, *koff, *kpt, *fr_off, *fr_pt;
-    int32_t *votes, *ref, *n_voters, *n_local, *local_kf, *n_pt, *n_cut, *local_pt, *fr_prior;
-    uint16_t *rank;                              // [F][K]
-    int32_t *cnt, *start, *local_ft;             // [F][K], [F][K + 1], [F][max_pt]
-};
 
 // the position of a set flag among the workgroup's flags in lane order, and their number; two barriers
 __device__ __forceinline__ int lms_block_rank(bool flag, int32_t *s_w, int *total)
@@ -265,6 +257,18 @@ bool params_ok(const ygz_lms_params &q)
 
 }  // namespace
 
+// the four launches on a bound table (lms_dev.h): what ygz_hip_local_map_select enqueues, and the resident call of rmap.hip on its own buffers
+void ygz_lms_launch(ygz_hip_ctx *ctx, const LmsDev &A, int n_frames, int max_len)
+{
+    const int n_keyframes = A.K;
+    const dim3 ranks((unsigned)std::min(n_keyframes, LMS_GRID_RANKS), (unsigned)n_frames);
+    YGZ_LAUNCH(ctx, KID_LMS_VOTE, k_lms_vote, dim3((unsigned)n_frames), dim3(LMS_LANES), A);
+    YGZ_LAUNCH(ctx, KID_LMS_POINTS, k_lms_points, ranks, dim3(LMS_LANES), A);
+    YGZ_LAUNCH(ctx, KID_LMS_PLACE, k_lms_place, ranks, dim3(LMS_LANES), A);
+    if (max_len > 0)
+        YGZ_LAUNCH(ctx, KID_LMS_PRIOR, k_lms_prior, dim3((unsigned)ygz_div_up(max_len, LMS_LANES), (unsigned)n_frames), dim3(LMS_LANES), A);
+}
+
 extern "C" {
 
 void ygz_hip_default_lms_params(ygz_lms_params *p)
@@ -351,12 +355,7 @@ int ygz_hip_local_map_select(ygz_hip_ctx *ctx, int n_keyframes, const uint8_t *k
     A.n_cut = ygz_at<int32_t>(b.dev, o_ncut); A.local_pt = ygz_at<int32_t>(b.dev, o_lpt); A.fr_prior = ygz_at<int32_t>(b.dev, o_prior);
     A.rank = ygz_at<uint16_t>(b.dev, o_rank); A.cnt = ygz_at<int32_t>(b.dev, o_cnt); A.start = ygz_at<int32_t>(b.dev, o_start);
     A.local_ft = ygz_at<int32_t>(b.dev, o_lft);
-    const dim3 ranks((unsigned)std::min(n_keyframes, LMS_GRID_RANKS), (unsigned)n_frames);
-    YGZ_LAUNCH(ctx, KID_LMS_VOTE, k_lms_vote, dim3((unsigned)n_frames), dim3(LMS_LANES), A);
-    YGZ_LAUNCH(ctx, KID_LMS_POINTS, k_lms_points, ranks, dim3(LMS_LANES), A);
-    YGZ_LAUNCH(ctx, KID_LMS_PLACE, k_lms_place, ranks, dim3(LMS_LANES), A);
-    if (max_len > 0)
-        YGZ_LAUNCH(ctx, KID_LMS_PRIOR, k_lms_prior, dim3((unsigned)ygz_div_up(max_len, LMS_LANES), (unsigned)n_frames), dim3(LMS_LANES), A);
+    ygz_lms_launch(ctx, A, n_frames, max_len);
     if ((rc = ygz_blob_fetch(ctx, b, o_ref, votes ? out_end : small_end)) != YGZ_OK) return rc;
     memcpy(n_local, b.host + o_nloc, F * 4);
     memcpy(local_kf, b.host + o_lkf, F * K * 4);

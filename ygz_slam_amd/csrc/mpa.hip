@@ -11,6 +11,7 @@
 // and every index a lane forms was validated by the entry point.  One packed upload, one launch, one copy back, one wait.
 #include "ygz_internal.h"
 #include "pose_block.h"
+#include "mpa_dev.h"
 #include <math.h>
 #include <string.h>
 #pragma clang fp contract(off)
@@ -21,14 +22,6 @@ static_assert(SCR_MPA == YGZ_N_SCRATCH - 1, "47 is the last id ygz_hip_ctx::scra
 namespace {
 
 #define MPA_LANES 256
-
-struct MpaDev {
-    int P;
-    const double *center, *pw;
-    const int32_t *offsets, *obs_kf, *obs_level;
-    double *dmax, *normal;
-    int32_t *state;
-};
 
 __global__ __launch_bounds__(MPA_LANES) void k_mpa_attr(MpaDev A)
 {
@@ -65,6 +58,12 @@ __global__ __launch_bounds__(MPA_LANES) void k_mpa_attr(MpaDev A)
 }
 
 }  // namespace
+
+// the launch on a bound table (mpa_dev.h): ygz_hip_map_point_attributes on its packed block, rmap.hip on a resident map
+void ygz_mpa_launch(ygz_hip_ctx *ctx, const MpaDev &A)
+{
+    YGZ_LAUNCH(ctx, KID_MPA_ATTR, k_mpa_attr, dim3((unsigned)ygz_div_up(A.P, MPA_LANES)), dim3(MPA_LANES), A);
+}
 
 extern "C" {
 
@@ -110,7 +109,7 @@ int ygz_hip_map_point_attributes(ygz_hip_ctx *ctx, int n_keyframes, const double
     A.offsets = ygz_at<const int32_t>(b.dev, o_off); A.obs_kf = ygz_at<const int32_t>(b.dev, o_kf);
     A.obs_level = ygz_at<const int32_t>(b.dev, o_lv);
     A.dmax = ygz_at<double>(b.dev, o_dmax); A.normal = ygz_at<double>(b.dev, o_nrm); A.state = ygz_at<int32_t>(b.dev, o_st);
-    YGZ_LAUNCH(ctx, KID_MPA_ATTR, k_mpa_attr, dim3((unsigned)ygz_div_up(n_points, MPA_LANES)), dim3(MPA_LANES), A);
+    ygz_mpa_launch(ctx, A);
     if ((rc = ygz_blob_fetch(ctx, b, o_dmax, total)) != YGZ_OK) return rc;
     memcpy(dmax, b.host + o_dmax, P * 8);
     memcpy(normal, b.host + o_nrm, 3 * P * 8);

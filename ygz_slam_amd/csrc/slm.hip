@@ -17,7 +17,9 @@
 // environment switch; every loop is a `for` over a count known at entry; every index read from a key or from the prior is checked against
 // n_kp / n_pt before it addresses memory.  One packed upload, five launches, one copy back, one wait.
 // The host body, ygz_slm_run, also serves ygz_hip_stereo_local_map_indexed (slm_index.hip, slm_share.h): there the sets are gathered on the
-// device from index lists into one map by a sixth launch in front of these five.
+// device from index lists into one map by a sixth launch in front of these five, and
+// ygz_hip_stereo_local_map_resident (rmap.hip): there the map is resident, and the lists, their lengths and the prior are written by the
+// launches of the source's hook, so every list has the stride as its room and its length exists on the device alone (section 36).
 #include "ygz_internal.h"
 #include "strack_dev.h"
 #include "popt_dev.h"
@@ -271,7 +273,7 @@ int ygz_hip_stereo_local_map_slots(ygz_hip_ctx *ctx, int n_sets, const ygz_strac
 int ygz_slm_run(ygz_hip_ctx *ctx, const SlmSource &src, int n_frames, const int32_t *slot, const int32_t *set, const double *T,
                 const int32_t *prior, const ygz_slm_params *params, const SlmOutputs &out)
 {
-    const bool indexed = src.indexed();
+    const bool indexed = src.indexed(), resident = src.is_resident();   // resident is indexed with the map, the lists and the prior on the device
     const int n_sets = src.n_sets;
     const ygz_strack_points *sets = src.sets;
     double *T_out = out.T_out, *chi2 = out.chi2, *round_cost_initial = out.round_cost_initial, *round_cost_final = out.round_cost_final;
@@ -282,7 +284,7 @@ int ygz_slm_run(ygz_hip_ctx *ctx, const SlmSource &src, int n_frames, const int3
     int32_t *reason = out.reason, *outcome = out.outcome, *n_cand = out.n_cand, *n_gated = out.n_gated;
     // every check before the device is touched; the context last, so that a null context refuses a valid call too
     if (!slot || !set || !T || !T_out || n_frames < 1 || n_sets < 1) return YGZ_E_INVALID;
-    if (indexed ? (!src.list_pt || !src.list_len || src.n_points < 0) : !sets) return YGZ_E_INVALID;
+    if (indexed ? ((!resident && (!src.list_pt || !src.list_len)) || src.n_points < 0) : !sets) return YGZ_E_INVALID;
     if (n_frames > YGZ_SLM_MAX_FRAMES) return YGZ_E_CAPACITY;
     if (indexed ? (n_sets > YGZ_SLM_MAX_FRAMES || src.n_points > YGZ_MPA_MAX_POINTS) : n_sets > YGZ_SLM_MAX_SETS) return YGZ_E_CAPACITY;
     ygz_slm_params p;
@@ -311,7 +313,7 @@ int ygz_slm_run(ygz_hip_ctx *ctx, const SlmSource &src, int n_frames, const int3
     }
     // by index: the lists some frame reads; the others are neither checked nor gathered
     std::vector<uint8_t> read_(indexed ? (size_t)n_sets : 0, 0);
-    if (indexed) {
+    if (indexed && !resident) {
         for (int f = 0; f < n_frames; ++f) read_[(size_t)set[f]] = 1;
         for (int s = 0; s < n_sets; ++s) {
             const int32_t *row = src.list_pt + (size_t)s * (size_t)src.stride;
@@ -321,7 +323,7 @@ int ygz_slm_run(ygz_hip_ctx *ctx, const SlmSource &src, int n_frames, const int3
     }
     if (N > YGZ_SLM_MAX_PAIRS) return YGZ_E_CAPACITY;
     if (!ygz_all_finite(T, 7 * F)) return YGZ_E_INVALID;
-    if (indexed) {
+    if (indexed && !resident) {                                          // a resident map was checked when it went up
         const size_t n = (size_t)src.n_points;
         if (n && (!ygz_all_finite(src.pw, 3 * n) || !ygz_all_finite(src.dmax, n) || !ygz_all_finite(src.normal, 3 * n))) return YGZ_E_INVALID;
     }
@@ -366,7 +368,8 @@ int ygz_slm_run(ygz_hip_ctx *ctx, const SlmSource &src, int n_frames, const int3
     const size_t o_tab = B.add_n<SlmSetTab>((size_t)n_sets);
     std::vector<SlmSetTab> tab((size_t)n_sets);
     // by index the map and the lists go up in the sets' place, and the sets' arrays lie behind everything else: k_slm_index fills them
-    const size_t MP = indexed ? (size_t)src.n_points : 0, LS = indexed ? (size_t)n_sets * (size_t)src.stride : 0;
+    const size_t MP = indexed && !resident ? (size_t)src.n_points : 0, LS = indexed && !resident ? (size_t)n_sets * (size_t)src.stride : 0;
+    const bool has_prior = prior || resident;
     const size_t o_mpw = B.add_n<double>(MP * 3), o_mdesc = B.add_n<uint4>(MP * 2), o_mdmax = B.add_n<double>(MP), o_mnrm = B.add_n<double>(MP * 3);
     const size_t o_lpt = B.add_n<int32_t>(LS);
     for (int s = 0; !indexed && s < n_sets; ++s) {
@@ -377,7 +380,8 @@ int ygz_slm_run(ygz_hip_ctx *ctx, const SlmSource &src, int n_frames, const int3
         tab[(size_t)s].normal = B.add_n<double>(n * 3);
         tab[(size_t)s].n_pt = sets[s].n_pt; tab[(size_t)s].pad_ = 0;
     }
-    const size_t o_prior = B.add_n<int32_t>(prior ? NK : 0), o_skip = B.add_n<uint8_t>(prior ? N : 0);
+    const size_t o_prior = B.add_n<int32_t>(prior ? NK : 0);
+    size_t o_skip = B.add_n<uint8_t>(prior ? N : 0);
     const size_t o_pose = B.add_n<double>(F * 7), in_end = B.end;
     const size_t o_status = B.add_n<int32_t>(F), o_counts = B.add_n<int32_t>(F * 8);
     YgzPoseBlock PB;
@@ -398,15 +402,16 @@ int ygz_slm_run(ygz_hip_ctx *ctx, const SlmSource &src, int n_frames, const int3
     const size_t o_keys = B.add_n<uint4>(N * 2);
     PB.add_edges(B, F, Cn);
     const size_t o_sets = B.add_n<StSetDev>((size_t)n_sets), o_probs = B.add_n<StProbDev>(F);
-    const size_t o_gur = B.add_n<double>(D * Cn), o_taken = B.add_n<uint8_t>(prior ? NK : 0);
+    const size_t o_gur = B.add_n<double>(D * Cn), o_taken = B.add_n<uint8_t>(has_prior ? NK : 0);
+    if (resident) o_skip = B.add_n<uint8_t>(N);                          // zeroed by the hook's launches, not by the upload
     int longest = 1;
     for (int s = 0; indexed && s < n_sets; ++s) {
-        const size_t n = read_[(size_t)s] ? (size_t)src.list_len[s] : 0;
+        const size_t n = resident ? (size_t)src.stride : read_[(size_t)s] ? (size_t)src.list_len[s] : 0;
         tab[(size_t)s].pw = B.add_n<double>(n * 3);
         tab[(size_t)s].desc = B.add_n<uint4>(n * 2);
         tab[(size_t)s].dmax = B.add_n<double>(n);
         tab[(size_t)s].normal = B.add_n<double>(n * 3);
-        tab[(size_t)s].n_pt = (int32_t)n; tab[(size_t)s].pad_ = 0;
+        tab[(size_t)s].n_pt = resident ? 0 : (int32_t)n; tab[(size_t)s].pad_ = 0;   // resident: the room is n, the length comes from the hook
         if ((int)n > longest) longest = (int)n;
     }
     const size_t total = B.end;
@@ -473,9 +478,17 @@ int ygz_slm_run(ygz_hip_ctx *ctx, const SlmSource &src, int n_frames, const int3
         X.block = dev; X.tab = A.set_tab;
         X.pw = ygz_at<const double>(dev, o_mpw); X.desc = ygz_at<const uint4>(dev, o_mdesc); X.dmax = ygz_at<const double>(dev, o_mdmax);
         X.normal = ygz_at<const double>(dev, o_mnrm); X.list_pt = ygz_at<const int32_t>(dev, o_lpt); X.stride = src.stride;
+        if (resident) {
+            SlmResidentDev R;
+            R.tab = ygz_at<SlmSetTab>(dev, o_tab); R.pt_skip = dev + o_skip; R.n_frames = n_frames; R.stride = src.stride; R.cells = ctx->cells;
+            R.list_pt = nullptr; R.prior = nullptr;
+            if ((rc = src.resident(ctx, src.user, R)) != YGZ_OK) return rc;
+            X.pw = src.pw; X.desc = reinterpret_cast<const uint4 *>(src.desc); X.dmax = src.dmax; X.normal = src.normal;
+            X.list_pt = R.list_pt; A.prior = R.prior;
+        }
         src.index(ctx, X, n_sets, longest);
     }
-    YGZ_LAUNCH(ctx, KID_SLM_GATHER, k_slm_gather, dim3(bt, (unsigned)(D + (prior ? F : 0))), dim3(SL_LANES), A);
+    YGZ_LAUNCH(ctx, KID_SLM_GATHER, k_slm_gather, dim3(bt, (unsigned)(D + (has_prior ? F : 0))), dim3(SL_LANES), A);
     YGZ_LAUNCH(ctx, KID_STRACK_SEARCH, k_strack_search, dim3(sx, (unsigned)n_frames), dim3(ST_DEV_LANES), ygz_at<const StIn>(dev, o_in), A.sets,
                A.probs, A.keys, A.n_cand, A.n_gated, A.level, A.reason, A.proj);
     YGZ_LAUNCH(ctx, KID_SLM_RESOLVE, k_slm_resolve, dim3((unsigned)n_frames), dim3(SL_LANES), A);

@@ -26,12 +26,13 @@ __global__ __launch_bounds__(SLI_LANES) void k_slm_index(SlmIndexDev A)
     normal[0] = A.normal[3 * p]; normal[1] = A.normal[3 * p + 1]; normal[2] = A.normal[3 * p + 2];
 }
 
-void launch_index(ygz_hip_ctx *ctx, const SlmIndexDev &A, int n_lists, int longest)
+}  // namespace
+
+// also the `index` of the resident source (rmap.hip): there the table's lengths are written by a launch in front of this one
+void ygz_slm_launch_index(ygz_hip_ctx *ctx, const SlmIndexDev &A, int n_lists, int longest)
 {
     YGZ_LAUNCH(ctx, KID_SLM_INDEX, k_slm_index, dim3((unsigned)ygz_div_up(longest, SLI_LANES), (unsigned)n_lists), dim3(SLI_LANES), A);
 }
-
-}  // namespace
 
 extern "C" {
 
@@ -47,7 +48,7 @@ int ygz_hip_stereo_local_map_indexed(ygz_hip_ctx *ctx, int n_points, const doubl
     SlmSource src;
     src.n_sets = n_lists; src.n_points = n_points; src.stride = list_stride;
     src.pw = pw; src.desc = pt_desc; src.dmax = pt_dmax; src.normal = pt_normal;
-    src.list_pt = list_pt; src.list_len = list_len; src.index = launch_index;
+    src.list_pt = list_pt; src.list_len = list_len; src.index = ygz_slm_launch_index;
     const SlmOutputs out = { T_out, status, counts, kp_point, outlier, chi2, inliers, rounds_run, round_status, round_iterations, round_cost_initial,
                              round_cost_final, round_lambda, match, dist, level, reason, outcome, n_cand, n_gated, proj };
     return ygz_slm_run(ctx, src, n_frames, slot, list, T, prior, params, out);

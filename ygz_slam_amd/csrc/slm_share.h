@@ -1,7 +1,10 @@
-// What ygz_hip_stereo_local_map_slots (slm.hip) and ygz_hip_stereo_local_map_indexed (slm_index.hip) share: ONE host body, ygz_slm_run in
-// slm.hip -- the check list, the packed block, the launch sequence and the copy back -- with two sources of the point sets.  By value the
-// sets' arrays go up as they are.  By index the map goes up once with the lists, the packed per-list arrays lie in the part of the block
-// that stays on the device, and the source's `index` launches k_slm_index to fill them before the five launches, which read both alike.
+// What ygz_hip_stereo_local_map_slots (slm.hip), ygz_hip_stereo_local_map_indexed (slm_index.hip) and ygz_hip_stereo_local_map_resident
+// (rmap.hip) share: ONE host body, ygz_slm_run in slm.hip -- the check list, the packed block, the launch sequence and the copy back -- with
+// three sources of the point sets.  By value the sets' arrays go up as they are.  By index the map goes up once with the lists, the packed
+// per-list arrays lie in the part of the block that stays on the device, and the source's `index` launches k_slm_index to fill them before
+// the five launches, which read both alike.  Resident is by index with everything already on the device: the map's
+// arrays are device pointers, and the lists, their lengths and the prior are written by the launches of the source's `resident` hook, which
+// runs behind the block's upload and in front of `index`.  The host knows no length then, so every list has the stride as its room.
 #pragma once
 #include "ygz_internal.h"
 
@@ -15,6 +18,15 @@ struct SlmIndexDev {
     int stride;
 };
 
+// what the resident hook is given (device pointers into the call's block) and what it hands back (device pointers of its own)
+struct SlmResidentDev {
+    SlmSetTab *tab;                                  // [n_frames]: the hook's launches write n_pt of every entry
+    uint8_t *pt_skip;                                // [n_frames][stride]: the hook's launches zero the first n_pt bytes of every row
+    int n_frames, stride, cells;
+    const int32_t *list_pt;                          // out: [n_frames][stride], list f is frame f's
+    const int32_t *prior;                            // out: [n_frames][cells]
+};
+
 struct SlmSource {
     int n_sets = 0;                                  // sets, or lists
     const ygz_strack_points *sets = nullptr;         // by value
@@ -22,8 +34,12 @@ struct SlmSource {
     const double *pw = nullptr; const uint8_t *desc = nullptr; const double *dmax = nullptr, *normal = nullptr;
     const int32_t *list_pt = nullptr, *list_len = nullptr;
     void (*index)(ygz_hip_ctx *ctx, const SlmIndexDev &A, int n_lists, int longest) = nullptr;
+    // resident: pw, desc, dmax and normal are device pointers, list_pt and list_len stay null, n_sets is the number of frames
+    int (*resident)(ygz_hip_ctx *ctx, void *user, SlmResidentDev &R) = nullptr;
+    void *user = nullptr;
     bool indexed() const { return index != nullptr; }
-    int n_pt(int s) const { return indexed() ? list_len[s] : sets[s].n_pt; }
+    bool is_resident() const { return resident != nullptr; }
+    int n_pt(int s) const { return is_resident() ? stride : indexed() ? list_len[s] : sets[s].n_pt; }
 };
 
 struct SlmOutputs {
@@ -34,3 +50,5 @@ struct SlmOutputs {
 
 int ygz_slm_run(ygz_hip_ctx *ctx, const SlmSource &src, int n_frames, const int32_t *slot, const int32_t *set, const double *T,
                 const int32_t *prior, const ygz_slm_params *params, const SlmOutputs &out);
+// slm_index.hip: the launch of k_slm_index, the `index` of both indexed sources
+void ygz_slm_launch_index(ygz_hip_ctx *ctx, const SlmIndexDev &A, int n_lists, int longest);

@@ -174,6 +174,8 @@ struct ygz_hip_ctx {
     int32_t *rect_qx[YGZ_RECT_CAMERAS] = {nullptr, nullptr}, *rect_qy[YGZ_RECT_CAMERAS] = {nullptr, nullptr};
     void *rect_box[YGZ_RECT_CAMERAS] = {nullptr, nullptr};
     ygz_rectify_params rect_prm[YGZ_RECT_CAMERAS] = {};
+    // the resident maps that are alive (rmap.hip): each owns its device buffers; ygz_hip_destroy frees the ones still here
+    std::vector<ygz_hip_map *> maps;
 };
 
 #define YGZ_HIPCHK(ctx, call)                                            \
@@ -219,7 +221,7 @@ struct YgzDeviceGuard {
 // kernel ids for the probe
 enum { KID_BGR2GRAY = 0, KID_PYR_DOWN, KID_FAST_SELECT, KID_COMPACT, KID_DESCRIBE, KID_HAMMING_NN, KID_MATCH_FINALIZE,
        KID_TRACK_LOAD, KID_FDP, KID_ALIGN2D, KID_SPARSE_ALIGN, KID_SCHARR, KID_KLT, KID_KLT_PAD, KID_BA_POSE_PREP, KID_BA_POINTS,
-       KID_BA_POSES, KID_BA_CHI2, KID_POSE_ONLY, KID_BA_LM, KID_BOW_TRANSFORM, KID_BOW_MATCH, KID_DEPTH_TRI, KID_LMAP_MATCH, KID_LMAP_AUX, KID_MATCH_POSTFILTER, KID_TRACK_AUX, KID_DEPTH_FILTER, KID_WINDOW, KID_UNDISTORT, KID_STEREO_MATCH, KID_STEREO_MEDIAN, KID_POSE_OPT, KID_RECTIFY, KID_SMAP_PAIRS, KID_SMAP_KEYFRAME, KID_SRL_GATHER, KID_SRL_RESOLVE, KID_SRL_SETS, KID_SRL_EDGES, KID_SRL_SCATTER, KID_SRL_PICK, KID_PNP_SOLVE, KID_PNP_SCORE, KID_PNP_SELECT, KID_MPA_ATTR, KID_SLM_INDEX, KID_SRK_GATHER, KID_SRK_RESOLVE, KID_SRK_SCATTER, KID_SLM_GATHER, KID_SLM_RESOLVE, KID_SLM_SCATTER, KID_LMS_VOTE, KID_LMS_POINTS, KID_LMS_PLACE, KID_LMS_PRIOR, KID_SVO_GATHER, KID_SVO_RESOLVE, KID_SVO_SCATTER, KID_LFUSE_SEARCH, KID_STRACK_SEARCH, KID_COUNT };
+       KID_BA_POSES, KID_BA_CHI2, KID_POSE_ONLY, KID_BA_LM, KID_BOW_TRANSFORM, KID_BOW_MATCH, KID_DEPTH_TRI, KID_LMAP_MATCH, KID_LMAP_AUX, KID_MATCH_POSTFILTER, KID_TRACK_AUX, KID_DEPTH_FILTER, KID_WINDOW, KID_UNDISTORT, KID_STEREO_MATCH, KID_STEREO_MEDIAN, KID_POSE_OPT, KID_RECTIFY, KID_SMAP_PAIRS, KID_SMAP_KEYFRAME, KID_SRL_GATHER, KID_SRL_RESOLVE, KID_SRL_SETS, KID_SRL_EDGES, KID_SRL_SCATTER, KID_SRL_PICK, KID_PNP_SOLVE, KID_PNP_SCORE, KID_PNP_SELECT, KID_MPA_ATTR, KID_SLM_INDEX, KID_RMAP_FILTER, KID_RMAP_SCATTER, KID_SRK_GATHER, KID_SRK_RESOLVE, KID_SRK_SCATTER, KID_SLM_GATHER, KID_SLM_RESOLVE, KID_SLM_SCATTER, KID_LMS_VOTE, KID_LMS_POINTS, KID_LMS_PLACE, KID_LMS_PRIOR, KID_SVO_GATHER, KID_SVO_RESOLVE, KID_SVO_SCATTER, KID_LFUSE_SEARCH, KID_STRACK_SEARCH, KID_COUNT };
 
 #define YGZ_LAUNCH(ctx, kid, kern, grid, block, ...)                                                         \
     do { const bool pr_ = (ctx)->probe_id == (kid) && (ctx)->probe_used + 2 <= (int)(ctx)->probe_ev.size();    \
@@ -350,6 +352,7 @@ int ygz_launch_undistort(ygz_hip_ctx *ctx, int slot_begin, int n_slots, int from
 void ygz_undistort_free(ygz_hip_ctx *ctx);
 int ygz_launch_rectify(ygz_hip_ctx *ctx, int slot_begin, int n_slots, int from_bgr, const uint8_t *camera_of_slot);   // rectify.hip: level 0 = the slots' uploads through their cameras' rectifying maps
 void ygz_rectify_free(ygz_hip_ctx *ctx);
+void ygz_rmap_free_all(ygz_hip_ctx *ctx);                                                 // rmap.hip: every resident map of the context
 // undistort.hip, for both launchers and their entry points: the source of the slots' remap (the BGR uploads, or their level 0 put aside in undist_plane),
 // the lens validation, and a device map of the context's size copied to the host (YGZ_E_STATE where the map is null)
 int ygz_remap_source(ygz_hip_ctx *ctx, int slot_begin, int n_slots, int from_bgr, const uint8_t **src);

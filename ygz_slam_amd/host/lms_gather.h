@@ -37,6 +37,22 @@ struct LmsGather {
             const Frame *kf = kfs[i];
             for (size_t j = 0; j < kf->_cov_keyframes.size() && j < (size_t)neighbours; ++j) meet(kf->_cov_keyframes[j]);
         }
+        build(frames, neighbours, kf_at);
+    }
+
+    // the map of a list of keyframes alone, without a tracked frame (ygz::ResidentMap::Upload): the same rules on the keyframes as given,
+    // null and repeated entries skipped; the points are those on the keyframes' features
+    void gather_map(const std::vector<Frame *> &keyframes, int neighbours)
+    {
+        std::unordered_map<const Frame *, int32_t> kf_at;
+        for (Frame *kf : keyframes)
+            if (kf && kf_at.emplace(kf, 0).second) kfs.push_back(kf);
+        build(std::vector<Frame *>(), neighbours, kf_at);
+    }
+
+    // step 2 on the keyframes met so far: their order, the covisible rows, the points and the observations
+    void build(const std::vector<Frame *> &frames, int neighbours, std::unordered_map<const Frame *, int32_t> &kf_at)
+    {
         std::stable_sort(kfs.begin(), kfs.end(), [](const Frame *a, const Frame *b) { return a->_keyframe_id < b->_keyframe_id; });
         for (size_t k = 0; k < kfs.size(); ++k) kf_at[kfs[k]] = (int32_t)k;
         no_keyframe = kfs.empty();                                 // no frame has a point with an observer: every list is empty

@@ -9,6 +9,7 @@
 #include "ygz_hip.h"
 #include "surface_share.h"
 #include "lms_gather.h"
+#include "lmt_share.h"
 #include <algorithm>
 #include <cstring>
 #include <set>
@@ -20,6 +21,86 @@ namespace {
 using hip::good;
 bool has32(const Mat &d) { return d.data && d.rows * d.cols * (int)d.elemSize() >= 32; }
 }
+
+namespace hip {
+
+bool LmtRows::descriptor(const MapPoint *mp, uint8_t out[32])
+{
+    const Feature *first = nullptr;
+    for (const auto &ob : mp->_obs)
+        if (ob.second && ob.second->_frame) { first = ob.second; break; }
+    const Mat *d = has32(mp->_distinctive_desc) && mp->_distinctive_desc.rows * mp->_distinctive_desc.cols * (int)mp->_distinctive_desc.elemSize() == 32
+                       ? &mp->_distinctive_desc : (first && has32(first->_desc) ? &first->_desc : nullptr);
+    if (d) memcpy(out, d->data, 32);
+    return d != nullptr;
+}
+
+// step 3 of LocalMapTracker::Track: every usable observation in key order, the centre once per distinct frame
+void LmtRows::collect(const std::vector<MapPoint *> &pts)
+{
+    const size_t P = pts.size();
+    centre.clear(); row_kf.clear(); row_level.clear(); centre_at.clear();
+    pw.assign(3 * std::max<size_t>(P, 1), 0.0); off.assign(1, 0); desc.assign(32 * std::max<size_t>(P, 1), 0); has_desc.assign(P, 0);
+    for (size_t p = 0; p < P; ++p) {
+        const MapPoint *mp = pts[p];
+        for (const auto &ob : mp->_obs) {
+            const Feature *f = ob.second;
+            if (!f || !f->_frame) continue;
+            const auto at = centre_at.emplace(f->_frame, (int32_t)centre_at.size());
+            if (at.second) {
+                const Vector3d cc = f->_frame->GetCamCenter();
+                for (int k = 0; k < 3; ++k) centre.push_back(cc[k]);
+            }
+            row_kf.push_back(at.first->second);
+            row_level.push_back(f->_level);
+        }
+        off.push_back((int32_t)row_kf.size());
+        for (int k = 0; k < 3; ++k) pw[3 * p + k] = mp->_pos_world[k];
+        has_desc[p] = descriptor(mp, &desc[32 * p]) ? 1 : 0;
+    }
+}
+
+// step 6 of LocalMapTracker::Track: the frames and the map points, in frame order
+int lmt_apply(const std::vector<Frame *> &frames, const LmtTracked &t, std::vector<LocalMapTracker::Result> *results)
+{
+    const size_t n = frames.size(), MP = t.MP, cells = t.cells;
+    const std::vector<MapPoint *> &pts = *t.pts;
+    int tracked = 0;
+    if (results) results->resize(n);
+    for (size_t k = 0; k < n; ++k) {
+        Frame *f = frames[k];
+        const int32_t *lp = &t.list_pt[k * MP], *pr = &t.prior[k * cells], *kp = &t.kp_point[k * cells];
+        const size_t len = (size_t)t.list_len[k];
+        std::set<const MapPoint *> on_frame;
+        for (size_t j = 0; j < f->_features.size(); ++j)
+            if (pr[j] >= 0 && on_frame.insert(pts[(size_t)lp[pr[j]]]).second) ++pts[(size_t)lp[pr[j]]]->_cnt_visible;
+        for (size_t i = 0; i < len; ++i) {
+            MapPoint *mp = pts[(size_t)lp[i]];
+            if (on_frame.count(mp)) continue;                            // skipped through the prior: not touched
+            if (t.reason[t.poff[k] + i] == 0) { ++mp->_cnt_visible; mp->_track_in_view = true; }
+            else mp->_track_in_view = false;
+        }
+        for (size_t j = 0; j < f->_features.size(); ++j)
+            if (pr[j] < 0 && kp[j] >= 0 && (size_t)kp[j] < len) f->_features[j]->_mappoint = pts[(size_t)lp[kp[j]]];
+        f->_TCW = SE3::from7(&t.T_out[7 * k]);
+        for (size_t j = 0; j < f->_features.size(); ++j) {
+            Feature *ft = f->_features[j];
+            if (kp[j] < 0 || !good(ft->_mappoint)) continue;
+            if (hip::apply_verdict(f, ft, t.outlier[k * cells + j] != 0)) ft->_mappoint->_cnt_found++;
+        }
+        Frame *best = !t.no_keyframe && t.ref[k] >= 0 ? (*t.kfs)[(size_t)t.ref[k]] : nullptr;
+        if (best) f->_ref_keyframe = best;
+        const bool ok = t.status[k] == 0 && t.inliers[k] >= t.min_tracked;
+        if (ok) ++tracked;
+        if (!results) continue;
+        LocalMapTracker::Result &r = (*results)[k];
+        r.status = t.status[k]; r.new_matches = t.counts[8 * k + 6]; r.edges = t.counts[8 * k + 7]; r.inliers = t.inliers[k]; r.tracked = ok;
+        r.ref = best; r.voters = t.n_voters[k]; r.cut = t.n_cut[k]; r.points = (int)len;
+    }
+    return tracked;
+}
+
+}  // namespace hip
 
 int LocalMapTracker::Track(const std::vector<Frame *> &frames, std::vector<Result> *results)
 {
@@ -48,32 +129,12 @@ int LocalMapTracker::Track(const std::vector<Frame *> &frames, std::vector<Resul
     if (!hip::lms_select(who, g, n, _options._local_keyframes_max, _options._max_points, ans)) return 0;
     const size_t MP = ans.MP, P = g.pts.size();
     // 3: the attributes of the whole map.  Every usable observation in key order, the centre once per distinct frame
-    std::vector<double> centre, pw(3 * std::max<size_t>(P, 1), 0.0), dmax(std::max<size_t>(P, 1), 0.0), normal(3 * std::max<size_t>(P, 1), 0.0);
-    std::vector<int32_t> off(1, 0), row_kf, row_level, state(std::max<size_t>(P, 1), 0);
-    std::vector<uint8_t> desc(32 * std::max<size_t>(P, 1), 0), has_desc(P, 0);
-    std::unordered_map<const Frame *, int32_t> centre_at;
-    for (size_t p = 0; p < P; ++p) {
-        const MapPoint *mp = g.pts[p];
-        const Feature *first = nullptr;
-        for (const auto &ob : mp->_obs) {
-            const Feature *f = ob.second;
-            if (!f || !f->_frame) continue;
-            if (!first) first = f;
-            const auto at = centre_at.emplace(f->_frame, (int32_t)centre_at.size());
-            if (at.second) {
-                const Vector3d cc = f->_frame->GetCamCenter();
-                for (int k = 0; k < 3; ++k) centre.push_back(cc[k]);
-            }
-            row_kf.push_back(at.first->second);
-            row_level.push_back(f->_level);
-        }
-        off.push_back((int32_t)row_kf.size());
-        for (int k = 0; k < 3; ++k) pw[3 * p + k] = mp->_pos_world[k];
-        const Mat *d = has32(mp->_distinctive_desc) && mp->_distinctive_desc.rows * mp->_distinctive_desc.cols * (int)mp->_distinctive_desc.elemSize() == 32
-                           ? &mp->_distinctive_desc : (first && has32(first->_desc) ? &first->_desc : nullptr);
-        if (d) { memcpy(&desc[32 * p], d->data, 32); has_desc[p] = 1; }
-    }
-    _stats.centres = (int)centre_at.size(); _stats.attribute_rows = (int)row_kf.size();
+    hip::LmtRows rows;
+    rows.collect(g.pts);
+    std::vector<double> &centre = rows.centre, &pw = rows.pw, dmax(std::max<size_t>(P, 1), 0.0), normal(3 * std::max<size_t>(P, 1), 0.0);
+    std::vector<int32_t> &off = rows.off, &row_kf = rows.row_kf, &row_level = rows.row_level, state(std::max<size_t>(P, 1), 0);
+    std::vector<uint8_t> &desc = rows.desc, &has_desc = rows.has_desc;
+    _stats.centres = (int)rows.centre_at.size(); _stats.attribute_rows = (int)row_kf.size();
     if (P > 0) {
         if (centre.empty()) centre.assign(3, 0.0);                      // no usable observation anywhere: every point gets state 0
         if (row_kf.empty()) { row_kf.push_back(0); row_level.push_back(0); }
@@ -129,39 +190,10 @@ int LocalMapTracker::Track(const std::vector<Frame *> &frames, std::vector<Resul
                                                      nullptr, nullptr, nullptr), "stereo_local_map_indexed"))
         return 0;
     // 6: the frames and the map points, in frame order
-    int tracked = 0;
-    if (results) results->resize(n);
-    for (size_t k = 0; k < n; ++k) {
-        Frame *f = frames[k];
-        const int32_t *lp = &list_pt[k * MP], *pr = &prior[k * cells], *kp = &kp_point[k * cells];
-        const size_t len = (size_t)list_len[k];
-        std::set<const MapPoint *> on_frame;
-        for (size_t j = 0; j < f->_features.size(); ++j)
-            if (pr[j] >= 0 && on_frame.insert(g.pts[(size_t)lp[pr[j]]]).second) ++g.pts[(size_t)lp[pr[j]]]->_cnt_visible;
-        for (size_t i = 0; i < len; ++i) {
-            MapPoint *mp = g.pts[(size_t)lp[i]];
-            if (on_frame.count(mp)) continue;                            // skipped through the prior: not touched
-            if (reason[poff[k] + i] == 0) { ++mp->_cnt_visible; mp->_track_in_view = true; }
-            else mp->_track_in_view = false;
-        }
-        for (size_t j = 0; j < f->_features.size(); ++j)
-            if (pr[j] < 0 && kp[j] >= 0 && (size_t)kp[j] < len) f->_features[j]->_mappoint = g.pts[(size_t)lp[kp[j]]];
-        f->_TCW = SE3::from7(&T_out[7 * k]);
-        for (size_t j = 0; j < f->_features.size(); ++j) {
-            Feature *ft = f->_features[j];
-            if (kp[j] < 0 || !good(ft->_mappoint)) continue;
-            if (hip::apply_verdict(f, ft, outlier[k * cells + j] != 0)) ft->_mappoint->_cnt_found++;
-        }
-        Frame *best = !g.no_keyframe && ans.ref[k] >= 0 ? g.kfs[(size_t)ans.ref[k]] : nullptr;
-        if (best) f->_ref_keyframe = best;
-        const bool ok = status[k] == 0 && inliers[k] >= o._min_tracked;
-        if (ok) ++tracked;
-        if (!results) continue;
-        Result &r = (*results)[k];
-        r.status = status[k]; r.new_matches = counts[8 * k + 6]; r.edges = counts[8 * k + 7]; r.inliers = inliers[k]; r.tracked = ok;
-        r.ref = best; r.voters = ans.n_voters[k]; r.cut = ans.n_cut[k]; r.points = (int)len;
-    }
-    return tracked;
+    const hip::LmtTracked t = { &g.pts, &g.kfs, g.no_keyframe, MP, cells, list_pt.data(), list_len.data(), prior.data(), kp_point.data(), reason.data(),
+                                poff.data(), outlier.data(), T_out.data(), status.data(), counts.data(), inliers.data(), ans.ref.data(),
+                                ans.n_voters.data(), ans.n_cut.data(), o._min_tracked };
+    return hip::lmt_apply(frames, t, results);
 }
 
 }  // namespace ygz
