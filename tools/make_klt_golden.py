@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Run ON THE GPU BOX with the build whose outputs are the reference: tracks tests/klt_case.py's two seeded VGA pairs with the batched
 LK path (k_klt3) and writes every output array to the given .npz (tests/golden/klt_bitexact.npz, read by tests/test_gpu_klt_bitexact.py).
+The CPU restatement tests/klt_ref.c (order 1) reproduces this output bit for bit without a GPU: tests/test_klt_ref.py.
 usage: tools/make_klt_golden.py out.npz"""
 import os
 import sys

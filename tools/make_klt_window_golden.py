@@ -4,6 +4,7 @@ tracks the cases of tests/klt_window_case.py and writes every output array to th
 tests/test_gpu_klt_window_reuse.py).  Before it tracks anything it confirms on the CPU, with the oracle, that the inputs are worth
 tracking: the one-level case has triples in which a point that iterates moves to new pixels while another one stays on its own, and
 evaluations at which no point of the triple moves.
+The CPU restatement tests/klt_ref.c (order 1) reproduces this output bit for bit without a GPU, the batched_* arrays included: tests/test_klt_ref.py.
 usage: tools/make_klt_window_golden.py out.npz"""
 import os
 import sys
