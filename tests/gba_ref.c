@@ -47,6 +47,7 @@ typedef struct {
 } gb_problem;
 
 /* ---- one edge ------------------------------------------------------------------------------------------------------------------ */
+/* on the device: ygz_quat_rotation (ygz_slam_amd/csrc/posemath_dev.h) */
 void gb_rotation(const double *q, double *R)
 {
     const double x = q[0], y = q[1], z = q[2], w = q[3];
@@ -110,6 +111,7 @@ void gb_hpl(const double *Jp, const double *Jl, double w, double *H)
 }
 
 /* T <- Delta(d) o T, d = (omega, t) */
+/* on the device: ygz_se3_retract (ygz_slam_amd/csrc/posemath_dev.h) */
 void gb_retract(const double *T, const double *d, double *out)
 {
     double dq[4] = { 0.5 * d[0], 0.5 * d[1], 0.5 * d[2], 1.0 };
@@ -156,6 +158,7 @@ static void gb_sym3_mul(const double *M, const double *v, double *o)
 }
 
 /* D: the upper triangle row by row (21); Lo: the Cholesky factor, lower triangle row by row (21); 0 on a non-positive pivot */
+/* on the device: ygz_sym_unpack and ygz_chol_factor (ygz_slam_amd/csrc/posemath_dev.h) */
 int gb_chol6(const double *D, double *Lo)
 {
     double A[36], L[36];
@@ -183,6 +186,7 @@ int gb_chol6(const double *D, double *Lo)
 }
 
 /* x = (L L^T)^-1 b */
+/* on the device: ygz_chol_solve_packed (ygz_slam_amd/csrc/posemath_dev.h) */
 void gb_chol6_solve(const double *Lo, const double *b, double *x)
 {
     double L[36], y[6];

@@ -166,6 +166,7 @@ double ir_det3(const double *a)                                      /* cofactor
     const double c0 = a[4] * a[8] - a[5] * a[7], c1 = a[5] * a[6] - a[3] * a[8], c2 = a[3] * a[7] - a[4] * a[6];
     return a[0] * c0 + a[1] * c1 + a[2] * c2;
 }
+/* on the device: ygz_inv3 (ygz_slam_amd/csrc/posemath_dev.h) */
 void ir_inv3(const double *a, double *r)                             /* adj(a) * (1 / det), det = a00 C00 + a01 C01 + a02 C02 */
 {
     double C[9];
@@ -179,6 +180,7 @@ void ir_inv3(const double *a, double *r)                             /* adj(a) *
 }
 
 /* Sophus SO3(const Matrix3d &) = Eigen's quaternion-from-matrix (trace branch, else the largest diagonal); q = (x, y, z, w) */
+/* on the device: ygz_quat_from_matrix (ygz_slam_amd/csrc/posemath_dev.h) */
 void ir_quat_from_matrix(const double *m, double *q)
 {
     const double tr = m[0] + m[4] + m[8];

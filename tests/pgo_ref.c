@@ -35,6 +35,7 @@ typedef struct {
 } pg_result;
 
 /* ---- Sim3 algebra ------------------------------------------------------------------------------------------------------------ */
+/* on the device: ygz_quat_rotation (ygz_slam_amd/csrc/posemath_dev.h) */
 void pg_rotation(const double *q, double *R)
 {
     const double x = q[0], y = q[1], z = q[2], w = q[3];
@@ -43,12 +44,14 @@ void pg_rotation(const double *q, double *R)
     R[6] = 2.0 * (x * z - w * y);       R[7] = 2.0 * (y * z + w * x);       R[8] = 1.0 - 2.0 * (x * x + y * y);
 }
 
+/* on the device: ygz_mat3_vec (ygz_slam_amd/csrc/posemath_dev.h) */
 static void mat_vec(const double *R, const double *v, double *o)
 {
     for (int i = 0; i < 3; ++i) o[i] = R[3 * i] * v[0] + R[3 * i + 1] * v[1] + R[3 * i + 2] * v[2];
 }
 
 /* S^-1: (1/s, R^T, -(1/s) R^T t) */
+/* on the device: ygz_sim3_inverse (ygz_slam_amd/csrc/posemath_dev.h) */
 void pg_inverse(const double *S, double *Si)
 {
     Si[0] = -S[0]; Si[1] = -S[1]; Si[2] = -S[2]; Si[3] = S[3];
@@ -78,6 +81,7 @@ void pg_compose(const double *A, const double *B, double *out)
 }
 
 /* the left-multiplicative update S <- Delta(x) o S, x = (omega, t, sigma): sim3_ref.c's sr_apply_delta; 0 when |sigma| >= 2 */
+/* on the device: ygz_sim3_retract (ygz_slam_amd/csrc/posemath_dev.h) */
 int pg_retract(const double *S, const double *x, double *out)
 {
     if (!(fabs(x[6]) < 2.0)) return 0;
@@ -172,6 +176,7 @@ int pg_edge_terms(const double *Si, const double *Sj, const double *M, int fix_s
 /* ---- 7x7 Cholesky of a diagonal block ------------------------------------------------------------------------------------------ */
 /* D: the upper triangle row by row (28); L: the factor of D + lambda I, lower triangle row by row (28); with fix_scale row and column 6
  * are the identity's; 0 on a non-positive pivot */
+/* on the device: pg_chol7 of pgo.hip on ygz_sym_unpack and ygz_chol_factor (ygz_slam_amd/csrc/posemath_dev.h) */
 int pg_chol7(const double *D, double lambda, int fix_scale, double *Lo)
 {
     double A[49], L[49];
@@ -204,6 +209,7 @@ int pg_chol7(const double *D, double lambda, int fix_scale, double *Lo)
 }
 
 /* x = (L L^T)^-1 b */
+/* on the device: ygz_chol_solve_packed (ygz_slam_amd/csrc/posemath_dev.h) */
 void pg_chol7_solve(const double *Lo, const double *b, double *x)
 {
     double L[49], y[7];

@@ -144,6 +144,7 @@ static void bearing(const double *px, const double *K4, double *y)
     y[0] = x / n; y[1] = v / n; y[2] = 1.0 / n;
 }
 
+/* on the device: ygz_inv3 (ygz_slam_amd/csrc/posemath_dev.h) */
 static void inv3(const double *a, double *r)
 {
     double C[9];
@@ -294,6 +295,7 @@ void pr_hypotheses(const double *pw, const double *px, int n, const double *K4, 
 }
 
 /* Sophus SO3(const Matrix3d &) = Eigen::Quaterniond(const Matrix3d &): the trace branch, else the largest diagonal (qx qy qz qw) */
+/* on the device: ygz_quat_from_matrix (ygz_slam_amd/csrc/posemath_dev.h) */
 void pr_quat_from_matrix(const double *m, double *q)
 {
     const double tr = m[0] + m[4] + m[8];

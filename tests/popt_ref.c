@@ -46,6 +46,7 @@ void pr_default_params(pr_params *p)
 }
 
 /* ---- one edge -------------------------------------------------------------------------------------------------------------------- */
+/* on the device: ygz_quat_rotation (ygz_slam_amd/csrc/posemath_dev.h) */
 void pr_rotation(const double *q, double *R)
 {
     const double x = q[0], y = q[1], z = q[2], w = q[3];
@@ -55,6 +56,7 @@ void pr_rotation(const double *q, double *R)
 }
 
 /* T <- Delta(d) o T, d = (omega, t) */
+/* on the device: ygz_se3_retract (ygz_slam_amd/csrc/posemath_dev.h) */
 void pr_retract(const double *T, const double *d, double *out)
 {
     double dq[4] = { 0.5 * d[0], 0.5 * d[1], 0.5 * d[2], 1.0 };
@@ -74,6 +76,7 @@ void pr_retract(const double *T, const double *d, double *out)
 }
 
 /* w = 4^-level */
+/* on the device: ygz_level_weight (ygz_slam_amd/csrc/posemath_dev.h) */
 static double pr_weight(int level) { return 1.0 / (double)(1 << (2 * level)); }
 
 /* P = R X + t and the residuals r [3] (r[2] = 0 for a mono edge); K = fx fy cx cy bf; 0 when the edge is rejected */

@@ -42,6 +42,7 @@ typedef struct {
 } sb_problem;
 
 /* ---- one edge ------------------------------------------------------------------------------------------------------------------ */
+/* on the device: ygz_level_weight (ygz_slam_amd/csrc/posemath_dev.h) */
 double sb_weight(int level) { return 1.0 / (double)(1 << (2 * level)); }
 
 /* r [3] (r2 = 0.0 for a mono edge), R and P; 0 when the edge is rejected */

@@ -59,6 +59,7 @@ void sr_sample_sets(int n, int max_iter, int32_t *sets)
 }
 
 /* ---- Sim3 algebra: S = (q, t, s) stored as qx qy qz qw tx ty tz s; S X = s (R X) + t ----------------------------------------- */
+/* on the device: ygz_quat_rotation (ygz_slam_amd/csrc/posemath_dev.h) */
 void sr_rotation(const double *q, double *R)
 {
     const double x = q[0], y = q[1], z = q[2], w = q[3];
@@ -67,6 +68,7 @@ void sr_rotation(const double *q, double *R)
     R[6] = 2.0 * (x * z - w * y);       R[7] = 2.0 * (y * z + w * x);       R[8] = 1.0 - 2.0 * (x * x + y * y);
 }
 
+/* on the device: ygz_mat3_vec (ygz_slam_amd/csrc/posemath_dev.h) */
 static void mat_vec(const double *R, const double *v, double *o)
 {
     for (int i = 0; i < 3; ++i) o[i] = R[3 * i] * v[0] + R[3 * i + 1] * v[1] + R[3 * i + 2] * v[2];
@@ -81,6 +83,7 @@ static void sim3_act(const double *S, const double *R, const double *X, double *
 }
 
 /* S21 = S12^-1: (1/s, R^T (the conjugate quaternion), -(1/s) R^T t) */
+/* on the device: ygz_sim3_inverse (ygz_slam_amd/csrc/posemath_dev.h) */
 void sr_inverse(const double *S, double *Si)
 {
     Si[0] = -S[0]; Si[1] = -S[1]; Si[2] = -S[2]; Si[3] = S[3];
@@ -271,6 +274,7 @@ void sr_hypotheses(const double *X1, const double *X2, const double *px1, const 
 
 /* ---- refinement ------------------------------------------------------------------------------------------------------------ */
 /* the left-multiplicative update S <- Delta(x) o S, x = (omega, t, sigma); 0 when |sigma| >= 2 */
+/* on the device: ygz_sim3_retract (ygz_slam_amd/csrc/posemath_dev.h) */
 int sr_apply_delta(const double *S, const double *x, double *out)
 {
     if (!(fabs(x[6]) < 2.0)) return 0;

@@ -42,6 +42,9 @@ def test_summation_constants_are_shared_with_the_restatement():
         assert int(re.search(r"#define\s+%s\s+(\d+)" % dev, hip).group(1)) == int(re.search(r"#define\s+%s\s+(\d+)" % host, ref).group(1)) == value
     assert (gb.LANES, gb.CHUNK, gb.CG_CAP) == (256, 1024, 1024)
     assert hip.count("__launch_bounds__(GBA_LANES)") == len(BUDGET)
-    code = re.sub(r"//[^\n]*", "", hip)
-    for word in ["getenv", "hipLaunchCooperativeKernel", "cooperative_groups", "atomicAdd", "__threadfence", "while ("]:
-        assert word not in code, word
+    # gba_phases.h takes the rotation, the retraction and the Cholesky loops from posemath_dev.h: the same words are kept out of it
+    shared = open(os.path.join(ROOT, "ygz_slam_amd", "csrc", "posemath_dev.h")).read()
+    for text in (hip, shared):
+        code = re.sub(r"//[^\n]*", "", text)
+        for word in ["getenv", "hipLaunchCooperativeKernel", "cooperative_groups", "atomicAdd", "__threadfence", "while ("]:
+            assert word not in code, word

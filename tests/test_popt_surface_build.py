@@ -49,7 +49,8 @@ def test_public_surface():
     assert mk.count("ygz_popt.cpp") == 2
     host = open(os.path.join(PKG, "host", "ygz_popt.cpp")).read()
     assert host.count("ygz_hip_optimize_pose_stereo(") == 1                          # one call for all frames of a batch
-    for path in (os.path.join(PKG, "host", "ygz_popt.cpp"), os.path.join(PKG, "csrc", "popt.hip"), os.path.join(ROOT, "tests", "cpp", "popt_surface.cpp")):
+    for path in (os.path.join(PKG, "host", "ygz_popt.cpp"), os.path.join(PKG, "csrc", "popt.hip"), os.path.join(PKG, "csrc", "posemath_dev.h"),
+                 os.path.join(ROOT, "tests", "cpp", "popt_surface.cpp")):
         assert "getenv" not in open(path).read(), path
     # Feature keeps its layout: the surface adds no member to it
     feat = open(os.path.join(ROOT, "include", "ygz", "Basic", "Feature.h")).read()

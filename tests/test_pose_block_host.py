@@ -27,7 +27,8 @@ def test_the_header_needs_no_hip_and_is_the_only_copy():
     includes = [line for line in h.splitlines() if line.startswith("#include")]
     assert not any("hip/" in line or "ygz_internal" in line for line in includes), includes
     mk = open(os.path.join(CSRC, "Makefile")).read()
-    assert "pose_block.h" in mk[mk.index("build/%.o:"):] and "slot_pose_dev.h" in mk[mk.index("build/%.o:"):]
+    # every object depends on every header of csrc/, pose_block.h and slot_pose_dev.h among them
+    assert "$(wildcard *.h)" in mk[mk.index("build/%.o:"):].split("\n")[0] and os.path.exists(os.path.join(CSRC, "slot_pose_dev.h"))
     # one range check, one finiteness check, one rotation rule under csrc/ (bow.hip keeps its own, held to the oracle)
     texts = {f: open(os.path.join(CSRC, f)).read() for f in sorted(os.listdir(CSRC)) if f.endswith((".hip", ".h"))}
     assert not any("isfinite(q.chi2_mono)" in t for t in texts.values())

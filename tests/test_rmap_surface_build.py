@@ -50,7 +50,9 @@ def test_symbols_struct_sizes_and_ids(hip_lib):
         code = re.sub(r"//[^\n]*", "", open(path).read())
         assert "getenv" not in code and "environ" not in code, path
     mk = open(os.path.join(PKG, "csrc", "Makefile")).read()
-    assert all(h in mk for h in ("rmap_host.h", "lms_dev.h", "mpa_dev.h")) and "$(wildcard *.hip)" in mk
+    # every object depends on every header of csrc/, these three among them
+    assert "$(wildcard *.h)" in re.search(r"build/%\.o:[^\n]*", mk).group(0) and "$(wildcard *.hip)" in mk
+    assert all(os.path.exists(os.path.join(PKG, "csrc", h)) for h in ("rmap_host.h", "lms_dev.h", "mpa_dev.h"))
 
 
 def test_struct_size_from_the_c_compiler(tmp_path):

@@ -55,7 +55,8 @@ def test_summation_constants_and_rules_are_shared():
     assert (gb.LANES, gb.CHUNK, gb.CG_CAP) == (256, 1024, 1024)
     assert hip.count("__launch_bounds__(GBA_LANES)") == len(BUDGET) and "__global__" not in hdr
     assert '#include "gba_phases.h"' in hip and '#include "gba_phases.h"' in old and "#pragma clang fp contract(off)" in hip
-    for text in (hip, hdr):
+    assert '#include "posemath_dev.h"' in hdr                          # the shared pose arithmetic: held to the same words
+    for text in (hip, hdr, open(os.path.join(csrc, "posemath_dev.h")).read()):
         code = re.sub(r"//[^\n]*", "", text)
         for word in ["getenv", "hipLaunchCooperativeKernel", "cooperative_groups", "atomicAdd", "__threadfence", "while ("]:
             assert word not in code, word

@@ -5,6 +5,7 @@
 // gathers and the trial cost; they live in the including file.  The other eleven work on Hpp, Hll, bp, bl and the 6 x 3 Hpl blocks alone.
 #pragma once
 #include "ygz_internal.h"
+#include "posemath_dev.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -62,18 +63,10 @@ template <int K> struct GbaRed {
     double out[K];
 };
 
-// ---- the arithmetic (tests/gba_ref.c, function by function) ------------------------------------------------------------------------
-__device__ __forceinline__ void gb_rotation(const double *q, double *R)
-{
-    const double x = q[0], y = q[1], z = q[2], w = q[3];
-    R[0] = 1.0 - 2.0 * (y * y + z * z); R[1] = 2.0 * (x * y - w * z);       R[2] = 2.0 * (x * z + w * y);
-    R[3] = 2.0 * (x * y + w * z);       R[4] = 1.0 - 2.0 * (x * x + z * z); R[5] = 2.0 * (y * z - w * x);
-    R[6] = 2.0 * (x * z - w * y);       R[7] = 2.0 * (y * z + w * x);       R[8] = 1.0 - 2.0 * (x * x + y * y);
-}
-
+// ---- the arithmetic (tests/gba_ref.c, function by function; its rotation, retraction and Cholesky loops are posemath_dev.h's) -----------
 __device__ __forceinline__ int gb_residual(const double *T, const double *X, const double *ob, const double *K, double *R, double *P, double *r)
 {
-    gb_rotation(T, R);
+    ygz_quat_rotation(T, R);
 #pragma unroll
     for (int i = 0; i < 3; ++i) P[i] = (R[3 * i] * X[0] + R[3 * i + 1] * X[1] + R[3 * i + 2] * X[2]) + T[4 + i];
     if (!(P[2] > 0)) return 0;
@@ -119,27 +112,6 @@ __device__ __forceinline__ int gb_edge_terms(const double *T, const double *X, c
     return 1;
 }
 
-__device__ __forceinline__ void gb_retract(const double *T, const double *d, double *out)
-{
-    double dq[4] = { 0.5 * d[0], 0.5 * d[1], 0.5 * d[2], 1.0 };
-    const double dn = sqrt(dq[0] * dq[0] + dq[1] * dq[1] + dq[2] * dq[2] + dq[3] * dq[3]);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) dq[k] = dq[k] / dn;
-    const double ax = dq[0], ay = dq[1], az = dq[2], aw = dq[3], bx = T[0], by = T[1], bz = T[2], bw = T[3];
-    double q[4];
-    q[0] = aw * bx + ax * bw + ay * bz - az * by;
-    q[1] = aw * by - ax * bz + ay * bw + az * bx;
-    q[2] = aw * bz + ax * by - ay * bx + az * bw;
-    q[3] = aw * bw - ax * bx - ay * by - az * bz;
-    const double qn = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) out[k] = q[k] / qn;
-    double dR[9];
-    gb_rotation(dq, dR);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) out[4 + i] = (dR[3 * i] * T[4] + dR[3 * i + 1] * T[5] + dR[3 * i + 2] * T[6]) + d[3 + i];
-}
-
 __device__ __forceinline__ int gb_inv3(const double *A, double lambda, double *inv)
 {
     const double a00 = A[0] + lambda, a01 = A[1], a02 = A[2], a11 = A[3] + lambda, a12 = A[4], a22 = A[5] + lambda;
@@ -163,63 +135,12 @@ __device__ __forceinline__ void gb_sym3_mul(const double *M, const double *v, do
     o[2] = M[2] * v[0] + M[4] * v[1] + M[5] * v[2];
 }
 
+// gb_chol6 of tests/gba_ref.c: the packed upper triangle D, the packed lower factor Lo
 __device__ __forceinline__ int gb_chol6(const double *D, double *Lo)
 {
-    double A[36], L[36];
-    int m = 0;
-#pragma unroll
-    for (int a = 0; a < 6; ++a)
-#pragma unroll
-        for (int b = a; b < 6; ++b) { A[a * 6 + b] = D[m]; A[b * 6 + a] = D[m]; ++m; }
-#pragma unroll
-    for (int k = 0; k < 36; ++k) L[k] = 0.0;
-    int ok = 1;
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-        double d = A[j * 6 + j];
-#pragma unroll
-        for (int k = 0; k < j; ++k) d -= L[j * 6 + k] * L[j * 6 + k];
-        ok &= d > 0;
-        const double ljj = sqrt(d);
-        L[j * 6 + j] = ljj;
-#pragma unroll
-        for (int i = j + 1; i < 6; ++i) {
-            double v = A[i * 6 + j];
-#pragma unroll
-            for (int k = 0; k < j; ++k) v -= L[i * 6 + k] * L[j * 6 + k];
-            L[i * 6 + j] = v / ljj;
-        }
-    }
-    m = 0;
-#pragma unroll
-    for (int i = 0; i < 6; ++i)
-#pragma unroll
-        for (int j = 0; j <= i; ++j) Lo[m++] = L[i * 6 + j];
-    return ok;
-}
-
-__device__ __forceinline__ void gb_chol6_solve(const double *Lo, const double *b, double *x)
-{
-    double L[36], y[6];
-    int m = 0;
-#pragma unroll
-    for (int i = 0; i < 6; ++i)
-#pragma unroll
-        for (int j = 0; j <= i; ++j) L[i * 6 + j] = Lo[m++];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        double v = b[i];
-#pragma unroll
-        for (int k = 0; k < i; ++k) v -= L[i * 6 + k] * y[k];
-        y[i] = v / L[i * 6 + i];
-    }
-#pragma unroll
-    for (int i = 5; i >= 0; --i) {
-        double v = y[i];
-#pragma unroll
-        for (int k = i + 1; k < 6; ++k) v -= L[k * 6 + i] * x[k];
-        x[i] = v / L[i * 6 + i];
-    }
+    double A[36];
+    ygz_sym_unpack<6>(D, A);
+    return ygz_chol_factor<6>(A, Lo);
 }
 
 // ---- sums ------------------------------------------------------------------------------------------------------------------------------
@@ -366,7 +287,7 @@ __device__ __forceinline__ void gba_ph_cg_begin(const GbaDev &D)
             for (int k = 0; k < 21; ++k) Lo[k] = D.Lf[21 * v + k];
 #pragma unroll
             for (int k = 0; k < 6; ++k) { r[k] = D.bt[6 * v + k]; D.x[6 * v + k] = 0.0; D.r[6 * v + k] = r[k]; }
-            gb_chol6_solve(Lo, r, z);
+            ygz_chol_solve_packed<6>(Lo, r, z);
 #pragma unroll
             for (int k = 0; k < 6; ++k) { D.z[6 * v + k] = z[k]; D.p[6 * v + k] = z[k]; d += r[k] * z[k]; }
             acc += d;
@@ -483,7 +404,7 @@ __device__ __forceinline__ void gba_ph_cg_step(const GbaDev &D)
             r[k] = D.r[6 * v + k] - alpha * D.q[6 * v + k];
             D.r[6 * v + k] = r[k];
         }
-        gb_chol6_solve(Lo, r, z);
+        ygz_chol_solve_packed<6>(Lo, r, z);
 #pragma unroll
         for (int k = 0; k < 6; ++k) { D.z[6 * v + k] = z[k]; d += r[k] * z[k]; }
         acc += d;
@@ -558,7 +479,7 @@ __device__ __forceinline__ void gba_ph_pose_update(const GbaDev &D)
 #pragma unroll
         for (int k = 0; k < 7; ++k) Tn[k] = T[k];
     } else {
-        gb_retract(T, x, Tn);
+        ygz_se3_retract(T, x, Tn);
     }
 #pragma unroll
     for (int k = 0; k < 7; ++k) D.Tn[7 * v + k] = Tn[k];

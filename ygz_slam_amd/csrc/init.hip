@@ -13,6 +13,7 @@
 //   k_init_parallax    block = solution: count and the 51st smallest float cos-parallax by rank (:607-614)
 //   k_init_accept      the H / F acceptance rule (:462-500, :879-937), SE3(R21, t21), the accepted points
 #include "ygz_internal.h"
+#include "posemath_dev.h"
 #include <cstring>
 #include <mutex>
 #include <map>
@@ -25,7 +26,7 @@
 
 namespace {
 
-// ---- the arithmetic (tests/init_ref.c, function by function) ----------------------------------------------------------------------
+// ---- the arithmetic (tests/init_ref.c, function by function; 3 x 3 inverse and matrix -> quaternion: posemath_dev.h) -----------------
 #define IR_JACOBI_TOL 1e-15
 #define IR_JACOBI_SWEEPS 40
 template <int ST>
@@ -151,42 +152,6 @@ __device__ __forceinline__ double ir_det3(const double *a)
     const double c0 = a[4] * a[8] - a[5] * a[7], c1 = a[5] * a[6] - a[3] * a[8], c2 = a[3] * a[7] - a[4] * a[6];
     return a[0] * c0 + a[1] * c1 + a[2] * c2;
 }
-__device__ __forceinline__ void ir_inv3(const double *a, double *r)
-{
-    double C[9];
-    C[0] = a[4] * a[8] - a[5] * a[7]; C[1] = a[5] * a[6] - a[3] * a[8]; C[2] = a[3] * a[7] - a[4] * a[6];
-    C[3] = a[2] * a[7] - a[1] * a[8]; C[4] = a[0] * a[8] - a[2] * a[6]; C[5] = a[1] * a[6] - a[0] * a[7];
-    C[6] = a[1] * a[5] - a[2] * a[4]; C[7] = a[2] * a[3] - a[0] * a[5]; C[8] = a[0] * a[4] - a[1] * a[3];
-    const double det = a[0] * C[0] + a[1] * C[1] + a[2] * C[2];
-    const double inv = 1.0 / det;
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) r[i * 3 + j] = C[j * 3 + i] * inv;
-}
-__device__ __forceinline__ void ir_quat_from_matrix(const double *m, double *q)
-{
-    const double tr = m[0] + m[4] + m[8];
-    if (tr > 0) {
-        double t = sqrt(tr + 1.0);
-        q[3] = 0.5 * t;
-        t = 0.5 / t;
-        q[0] = (m[2 * 3 + 1] - m[1 * 3 + 2]) * t;
-        q[1] = (m[0 * 3 + 2] - m[2 * 3 + 0]) * t;
-        q[2] = (m[1 * 3 + 0] - m[0 * 3 + 1]) * t;
-    } else {
-        int i = 0;
-        if (m[4] > m[0]) i = 1;
-        if (m[8] > m[i * 3 + i]) i = 2;
-        const int j = (i + 1) % 3, k = (j + 1) % 3;
-        double t = sqrt(m[i * 3 + i] - m[j * 3 + j] - m[k * 3 + k] + 1.0);
-        q[i] = 0.5 * t;
-        t = 0.5 / t;
-        q[3] = (m[k * 3 + j] - m[j * 3 + k]) * t;
-        q[j] = (m[j * 3 + i] + m[i * 3 + j]) * t;
-        q[k] = (m[k * 3 + i] + m[i * 3 + k]) * t;
-    }
-}
 
 __device__ __forceinline__ float ir_h_contrib(const double *H12, double u1, double v1, double u2, double v2, float invSigmaSquare, int *in)
 {
@@ -227,7 +192,7 @@ __device__ __forceinline__ void ir_f_contrib(const float *f, double du1, double 
 __device__ __forceinline__ int ir_h_solutions(const double *H21, const double *K, double *Rs, double *ts)
 {
     double invK[9], A[9], U[9], sg[3], V[9];
-    ir_inv3(K, invK);
+    ygz_inv3(K, invK);
     mul3(invK, H21, A); mul3(A, K, A);
     ir_svd3(A, U, sg, V);
     const double d1 = sg[0], d2 = sg[1], d3 = sg[2];
@@ -347,7 +312,7 @@ __global__ __launch_bounds__(256) void k_init_normalize(InitDev D)
             T[0] = sX; T[1] = 0; T[2] = -m0 * sX; T[3] = 0; T[4] = sY; T[5] = -m1 * sY; T[6] = 0; T[7] = 0; T[8] = 1;
         }
         double T2inv[9], T2t[9];
-        ir_inv3(T2, T2inv);
+        ygz_inv3(T2, T2inv);
         tr3(T2, T2t);
         for (int k = 0; k < 9; ++k) { D.T[k] = T1[k]; D.T[9 + k] = T2inv[k]; D.T[18 + k] = T2t[k]; }
     }
@@ -390,7 +355,7 @@ __global__ __launch_bounds__(INIT_MODEL_LANES) void k_init_models(InitDev D)
     if (isH) {                                               // FindHomography :123-125
         mul3(Tl, x, M); mul3(M, T1r, M);
         double H12[9];
-        ir_inv3(M, H12);
+        ygz_inv3(M, H12);
 #pragma unroll
         for (int k = 0; k < 9; ++k) { D.H21[h * 9 + k] = M[k]; D.H12[h * 9 + k] = H12[k]; }
     } else {                                                 // ComputeF21 :759-761, FindFundamental :702-703
@@ -674,7 +639,7 @@ __global__ __launch_bounds__(256) void k_init_accept(InitDev D)
         }
         double q[4], Rm[9];
         for (int k = 0; k < 9; ++k) Rm[k] = r->R21[k];
-        ir_quat_from_matrix(Rm, q);                          // _T21 = SE3(R21, t21) (:79)
+        ygz_quat_from_matrix(Rm, q);                          // _T21 = SE3(R21, t21) (:79)
         for (int k = 0; k < 4; ++k) r->T21[k] = q[k];
         for (int k = 0; k < 3; ++k) r->T21[4 + k] = r->t21[k];
         sh_best = best; sh_ok = accept; sh_tri = 0;

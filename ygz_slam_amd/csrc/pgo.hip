@@ -6,6 +6,7 @@
 //                    the gathers over the CSR adjacency (edge-index order, no atomics), the 7x7 Cholesky preconditioner and the vector updates.
 //                    Every block-wide sum is lane-strided in index order, then the fixed tree over the lanes.
 #include "ygz_internal.h"
+#include "posemath_dev.h"
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -41,75 +42,19 @@ struct PgoShared {
     double tot;
 };
 
-// ---- the arithmetic (tests/pgo_ref.c, function by function) ------------------------------------------------------------------------
-__device__ __forceinline__ void pg_rotation(const double *q, double *R)
-{
-    const double x = q[0], y = q[1], z = q[2], w = q[3];
-    R[0] = 1.0 - 2.0 * (y * y + z * z); R[1] = 2.0 * (x * y - w * z);       R[2] = 2.0 * (x * z + w * y);
-    R[3] = 2.0 * (x * y + w * z);       R[4] = 1.0 - 2.0 * (x * x + z * z); R[5] = 2.0 * (y * z - w * x);
-    R[6] = 2.0 * (x * z - w * y);       R[7] = 2.0 * (y * z + w * x);       R[8] = 1.0 - 2.0 * (x * x + y * y);
-}
-
-__device__ __forceinline__ void mat_vec(const double *R, const double *v, double *o)
-{
-#pragma unroll
-    for (int i = 0; i < 3; ++i) o[i] = R[3 * i] * v[0] + R[3 * i + 1] * v[1] + R[3 * i + 2] * v[2];
-}
-
-__device__ __forceinline__ void pg_inverse(const double *S, double *Si)
-{
-    Si[0] = -S[0]; Si[1] = -S[1]; Si[2] = -S[2]; Si[3] = S[3];
-    Si[7] = 1.0 / S[7];
-    double R[9], r[3];
-    pg_rotation(Si, R);
-    mat_vec(R, S + 4, r);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) Si[4 + k] = -(Si[7] * r[k]);
-}
-
+// ---- the arithmetic (tests/pgo_ref.c, function by function; rotation, Sim3 inverse and retraction, Cholesky loops: posemath_dev.h) ---
 __device__ __forceinline__ void pg_compose(const double *A, const double *B, double *out)
 {
-    const double ax = A[0], ay = A[1], az = A[2], aw = A[3], bx = B[0], by = B[1], bz = B[2], bw = B[3];
-    double q[4];
-    q[0] = aw * bx + ax * bw + ay * bz - az * by;
-    q[1] = aw * by - ax * bz + ay * bw + az * bx;
-    q[2] = aw * bz + ax * by - ay * bx + az * bw;
-    q[3] = aw * bw - ax * bx - ay * by - az * bz;
+    double q[4], R[9], r[3];
+    ygz_quat_mul(A, B, q);
     const double qn = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-    double R[9], r[3];
-    pg_rotation(A, R);
-    mat_vec(R, B + 4, r);
+    ygz_quat_rotation(A, R);
+    ygz_mat3_vec(R, B + 4, r);
 #pragma unroll
     for (int k = 0; k < 4; ++k) out[k] = q[k] / qn;
 #pragma unroll
     for (int k = 0; k < 3; ++k) out[4 + k] = A[7] * r[k] + A[4 + k];
     out[7] = A[7] * B[7];
-}
-
-__device__ __forceinline__ int pg_retract(const double *S, const double *x, double *out)
-{
-    if (!(fabs(x[6]) < 2.0)) return 0;
-    double dq[4] = { 0.5 * x[0], 0.5 * x[1], 0.5 * x[2], 1.0 };
-    const double dn = sqrt(dq[0] * dq[0] + dq[1] * dq[1] + dq[2] * dq[2] + dq[3] * dq[3]);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) dq[k] = dq[k] / dn;
-    const double ds = (2.0 + x[6]) / (2.0 - x[6]);
-    const double ax = dq[0], ay = dq[1], az = dq[2], aw = dq[3], bx = S[0], by = S[1], bz = S[2], bw = S[3];
-    double q[4];
-    q[0] = aw * bx + ax * bw + ay * bz - az * by;
-    q[1] = aw * by - ax * bz + ay * bw + az * bx;
-    q[2] = aw * bz + ax * by - ay * bx + az * bw;
-    q[3] = aw * bw - ax * bx - ay * by - az * bz;
-    const double qn = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) out[k] = q[k] / qn;
-    double dR[9], r[3];
-    pg_rotation(dq, dR);
-    mat_vec(dR, S + 4, r);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) out[4 + k] = ds * r[k] + x[3 + k];
-    out[7] = ds * S[7];
-    return 1;
 }
 
 __device__ __forceinline__ int pg_lift(const double *E, double *r)
@@ -130,7 +75,7 @@ __device__ __forceinline__ int pg_edge_residual(const double *Si, const double *
 {
     double A[8], Sji[8];
     pg_compose(M, Si, A);
-    pg_inverse(Sj, Sji);
+    ygz_sim3_inverse(Sj, Sji);
     pg_compose(A, Sji, E);
     return pg_lift(E, r);
 }
@@ -139,7 +84,7 @@ __device__ __forceinline__ int pg_edge_residual(const double *Si, const double *
 __device__ __forceinline__ void pg_block(const double *E, const double *r, const double *A, double sign, int fix_scale, double *Jout)
 {
     double R[9], Lr[9], K[9], J[49];
-    pg_rotation(A, R);
+    ygz_quat_rotation(A, R);
     const double a0 = r[0], a1 = r[1], a2 = r[2];
     Lr[0] = 1.0 + 0.25 * (a0 * a0);       Lr[1] = 0.5 * a2 + 0.25 * (a0 * a1);  Lr[2] = -(0.5 * a1) + 0.25 * (a0 * a2);
     Lr[3] = -(0.5 * a2) + 0.25 * (a1 * a0); Lr[4] = 1.0 + 0.25 * (a1 * a1);     Lr[5] = 0.5 * a0 + 0.25 * (a1 * a2);
@@ -184,14 +129,11 @@ __device__ __forceinline__ int pg_edge_terms(const double *Si, const double *Sj,
     return 1;
 }
 
+// D + lambda I, the scale's row and column replaced by the unit ones when the scale is fixed
 __device__ __forceinline__ int pg_chol7(const double *D, double lambda, int fix_scale, double *Lo)
 {
-    double A[49], L[49];
-    int m = 0;
-#pragma unroll
-    for (int a = 0; a < 7; ++a)
-#pragma unroll
-        for (int b = a; b < 7; ++b) { A[a * 7 + b] = D[m]; A[b * 7 + a] = D[m]; ++m; }
+    double A[49];
+    ygz_sym_unpack<7>(D, A);
 #pragma unroll
     for (int a = 0; a < 7; ++a) A[a * 7 + a] = A[a * 7 + a] + lambda;
     if (fix_scale) {
@@ -199,55 +141,7 @@ __device__ __forceinline__ int pg_chol7(const double *D, double lambda, int fix_
         for (int a = 0; a < 7; ++a) { A[a * 7 + 6] = 0.0; A[6 * 7 + a] = 0.0; }
         A[48] = 1.0;
     }
-#pragma unroll
-    for (int k = 0; k < 49; ++k) L[k] = 0.0;
-    int ok = 1;
-#pragma unroll
-    for (int j = 0; j < 7; ++j) {
-        double d = A[j * 7 + j];
-#pragma unroll
-        for (int k = 0; k < j; ++k) d -= L[j * 7 + k] * L[j * 7 + k];
-        ok &= d > 0;
-        const double ljj = sqrt(d);
-        L[j * 7 + j] = ljj;
-#pragma unroll
-        for (int i = j + 1; i < 7; ++i) {
-            double v = A[i * 7 + j];
-#pragma unroll
-            for (int k = 0; k < j; ++k) v -= L[i * 7 + k] * L[j * 7 + k];
-            L[i * 7 + j] = v / ljj;
-        }
-    }
-    m = 0;
-#pragma unroll
-    for (int i = 0; i < 7; ++i)
-#pragma unroll
-        for (int j = 0; j <= i; ++j) Lo[m++] = L[i * 7 + j];
-    return ok;
-}
-
-__device__ __forceinline__ void pg_chol7_solve(const double *Lo, const double *b, double *x)
-{
-    double L[49], y[7];
-    int m = 0;
-#pragma unroll
-    for (int i = 0; i < 7; ++i)
-#pragma unroll
-        for (int j = 0; j <= i; ++j) L[i * 7 + j] = Lo[m++];
-#pragma unroll
-    for (int i = 0; i < 7; ++i) {
-        double v = b[i];
-#pragma unroll
-        for (int k = 0; k < i; ++k) v -= L[i * 7 + k] * y[k];
-        y[i] = v / L[i * 7 + i];
-    }
-#pragma unroll
-    for (int i = 6; i >= 0; --i) {
-        double v = y[i];
-#pragma unroll
-        for (int k = i + 1; k < 7; ++k) v -= L[k * 7 + i] * x[k];
-        x[i] = v / L[i * 7 + i];
-    }
+    return ygz_chol_factor<7>(A, Lo);
 }
 
 // ---- block-wide sums -----------------------------------------------------------------------------------------------------------------
@@ -379,7 +273,7 @@ __device__ int pgo_cg(const PgoDev &D, PgoShared &sh, int n, int ne, int fix_sca
         double r[7], z[7];
 #pragma unroll
         for (int k = 0; k < 7; ++k) { r[k] = D.b[7 * v + k]; D.x[7 * v + k] = 0.0; D.r[7 * v + k] = r[k]; }
-        pg_chol7_solve(D.Lf + 28 * v, r, z);
+        ygz_chol_solve_packed<7>(D.Lf + 28 * v, r, z);
 #pragma unroll
         for (int k = 0; k < 7; ++k) { D.z[7 * v + k] = z[k]; D.p[7 * v + k] = z[k]; acc += r[k] * z[k]; }
     }
@@ -454,7 +348,7 @@ __device__ int pgo_cg(const PgoDev &D, PgoShared &sh, int n, int ne, int fix_sca
                 r[k] = D.r[7 * v + k] - alpha * D.q[7 * v + k];
                 D.r[7 * v + k] = r[k];
             }
-            pg_chol7_solve(D.Lf + 28 * v, r, z);
+            ygz_chol_solve_packed<7>(D.Lf + 28 * v, r, z);
 #pragma unroll
             for (int k = 0; k < 7; ++k) { D.z[7 * v + k] = z[k]; acc += r[k] * z[k]; }
         }
@@ -530,7 +424,7 @@ __global__ __launch_bounds__(PGO_LANES) void k_pgo_optimize(PgoDev D)
                     if (fx || zero) {
 #pragma unroll
                         for (int k = 0; k < 8; ++k) Sn[k] = S[k];
-                    } else if (!pg_retract(S, x, Sn)) {
+                    } else if (!ygz_sim3_retract(S, x, Sn)) {
                         bad = 1;
 #pragma unroll
                         for (int k = 0; k < 8; ++k) Sn[k] = S[k];

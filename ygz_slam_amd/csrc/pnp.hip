@@ -8,13 +8,14 @@
 // PnpIn, PnpDev and the kernels' prototypes are in pnp_dev.h: srl.hip launches the same three kernels on associations it compacted itself.
 #include "ygz_internal.h"
 #include "pnp_dev.h"
+#include "posemath_dev.h"
 #include <cstring>
 
 using namespace ygz_pnp;
 
 namespace {
 
-// ---- the arithmetic (tests/pnp_ref.c, function by function) ---------------------------------------------------------------------
+// ---- the arithmetic (tests/pnp_ref.c, function by function; 3 x 3 inverse and matrix -> quaternion: posemath_dev.h) -----------------
 #define PR_BISECT 64
 #define PR_REFINE 5
 
@@ -111,19 +112,6 @@ __device__ __forceinline__ void bearing(const double *px, const double *K4, doub
     y[0] = x / n; y[1] = v / n; y[2] = 1.0 / n;
 }
 
-__device__ __forceinline__ void inv3(const double *a, double *r)
-{
-    double C[9];
-    C[0] = a[4] * a[8] - a[5] * a[7]; C[1] = a[5] * a[6] - a[3] * a[8]; C[2] = a[3] * a[7] - a[4] * a[6];
-    C[3] = a[2] * a[7] - a[1] * a[8]; C[4] = a[0] * a[8] - a[2] * a[6]; C[5] = a[1] * a[6] - a[0] * a[7];
-    C[6] = a[1] * a[5] - a[2] * a[4]; C[7] = a[2] * a[3] - a[0] * a[5]; C[8] = a[0] * a[4] - a[1] * a[3];
-    const double inv = 1.0 / (a[0] * C[0] + a[1] * C[1] + a[2] * C[2]);
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) r[i * 3 + j] = C[j * 3 + i] * inv;
-}
-
 __device__ __forceinline__ int pose_from_depths(const double *l, const double *y1, const double *y2, const double *y3, const double *x1,
                                                 const double *Xi, double *out)
 {
@@ -196,7 +184,7 @@ __device__ __forceinline__ int pr_p3p(const double *pw, const double *px, const 
     double X[9], Xi[9];
 #pragma unroll
     for (int k = 0; k < 3; ++k) { X[k * 3 + 0] = d12[k]; X[k * 3 + 1] = d13[k]; X[k * 3 + 2] = nx[k]; }
-    inv3(X, Xi);
+    ygz_inv3(X, Xi);
     int cnt = 0;
 #pragma unroll
     for (int si = 0; si < 2; ++si) {
@@ -239,30 +227,6 @@ __device__ __forceinline__ int pr_is_inlier(const double *P, double w0, double w
     const double du = K4[0] * (X / Z) + K4[2] - u;
     const double dv = K4[1] * (Y / Z) + K4[3] - v;
     return du * du + dv * dv <= chi2;
-}
-
-__device__ __forceinline__ void pr_quat_from_matrix(const double *m, double *q)
-{
-    const double tr = m[0] + m[4] + m[8];
-    if (tr > 0) {
-        double t = sqrt(tr + 1.0);
-        q[3] = 0.5 * t;
-        t = 0.5 / t;
-        q[0] = (m[2 * 3 + 1] - m[1 * 3 + 2]) * t;
-        q[1] = (m[0 * 3 + 2] - m[2 * 3 + 0]) * t;
-        q[2] = (m[1 * 3 + 0] - m[0 * 3 + 1]) * t;
-    } else {
-        int i = 0;
-        if (m[4] > m[0]) i = 1;
-        if (m[8] > m[i * 3 + i]) i = 2;
-        const int j = (i + 1) % 3, k = (j + 1) % 3;
-        double t = sqrt(m[i * 3 + i] - m[j * 3 + j] - m[k * 3 + k] + 1.0);
-        q[i] = 0.5 * t;
-        t = 0.5 / t;
-        q[3] = (m[k * 3 + j] - m[j * 3 + k]) * t;
-        q[j] = (m[j * 3 + i] + m[i * 3 + j]) * t;
-        q[k] = (m[k * 3 + i] + m[i * 3 + k]) * t;
-    }
 }
 
 }  // namespace
@@ -383,7 +347,7 @@ __global__ __launch_bounds__(PNP_SEL_THREADS) void k_pnp_select(PnpDev D)
     __syncthreads();
     if (threadIdx.x == 0) {
         double q[4];
-        pr_quat_from_matrix(P, q);
+        ygz_quat_from_matrix(P, q);
         for (int k = 0; k < 9; ++k) r->R[k] = P[k];
         for (int k = 0; k < 3; ++k) r->t[k] = P[9 + k];
         for (int k = 0; k < 4; ++k) r->T_cw[k] = q[k];

@@ -12,6 +12,7 @@
 // same path.
 #include "ygz_internal.h"
 #include "popt_dev.h"                   // PoptArgs and the kernel's prototype: svo.hip launches it too
+#include "posemath_dev.h"               // rotation, retraction T <- Delta(d) o T (pr_retract), level weight
 #include <math.h>
 #include <string.h>
 #pragma clang fp contract(off)
@@ -33,35 +34,6 @@ struct PoptState {
     int c_ok, c_rej, c_inl;             // the integer counters of a pass and of a classification
     double K[5], d2m, d2s, dm, ds, min_rel_decrease;    // the call's constants, out of the scalar registers
 };
-
-__device__ __forceinline__ void pt_rotation(const double *q, double *R)
-{
-    const double x = q[0], y = q[1], z = q[2], w = q[3];
-    R[0] = 1.0 - 2.0 * (y * y + z * z); R[1] = 2.0 * (x * y - w * z);       R[2] = 2.0 * (x * z + w * y);
-    R[3] = 2.0 * (x * y + w * z);       R[4] = 1.0 - 2.0 * (x * x + z * z); R[5] = 2.0 * (y * z - w * x);
-    R[6] = 2.0 * (x * z - w * y);       R[7] = 2.0 * (y * z + w * x);       R[8] = 1.0 - 2.0 * (x * x + y * y);
-}
-
-// T <- Delta(d) o T (pr_retract)
-__device__ void pt_retract(const double *T, const double *d, double *out)
-{
-    double dq[4] = { 0.5 * d[0], 0.5 * d[1], 0.5 * d[2], 1.0 };
-    const double dn = sqrt(dq[0] * dq[0] + dq[1] * dq[1] + dq[2] * dq[2] + dq[3] * dq[3]);
-    for (int k = 0; k < 4; ++k) dq[k] = dq[k] / dn;
-    const double ax = dq[0], ay = dq[1], az = dq[2], aw = dq[3], bx = T[0], by = T[1], bz = T[2], bw = T[3];
-    double q[4];
-    q[0] = aw * bx + ax * bw + ay * bz - az * by;
-    q[1] = aw * by - ax * bz + ay * bw + az * bx;
-    q[2] = aw * bz + ax * by - ay * bx + az * bw;
-    q[3] = aw * bw - ax * bx - ay * by - az * bz;
-    const double qn = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-    for (int k = 0; k < 4; ++k) out[k] = q[k] / qn;
-    double dR[9];
-    pt_rotation(dq, dR);
-    for (int i = 0; i < 3; ++i) out[4 + i] = (dR[3 * i] * T[4] + dR[3 * i + 1] * T[5] + dR[3 * i + 2] * T[6]) + d[3 + i];
-}
-
-__device__ __forceinline__ double pt_weight(int level) { return 1.0 / (double)(1 << (2 * level)); }
 
 // P = R X + t and the residuals (pr_residual); false when the edge is rejected
 __device__ __forceinline__ bool pt_residual(const double *R, const double *t, const double *X, const double *ob, int kind, const double *K, double *P,
@@ -102,7 +74,7 @@ __device__ __forceinline__ bool pt_edge(const double *R, const double *t, const 
 {
     double P[3], r[3], rho0, rho1;
     if (!pt_residual(R, t, X, ob, kind, K, P, r)) return false;
-    const double w = pt_weight(level);
+    const double w = ygz_level_weight(level);
     pt_robust(pt_chi2(r, kind, w), d2, delta, &rho0, &rho1);
     if (full) {
         double J[18];
@@ -145,7 +117,7 @@ __device__ __forceinline__ void pt_pass(const PoptArgs &A, PoptState &S, int beg
 {
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     double R[9], t[3], K[5];
-    pt_rotation(pose, R);
+    ygz_quat_rotation(pose, R);
     t[0] = pose[4]; t[1] = pose[5]; t[2] = pose[6];
 #pragma unroll
     for (int k = 0; k < 5; ++k) K[k] = S.K[k];
@@ -257,7 +229,7 @@ __device__ void pt_next_trial(const PoptArgs &A, PoptState &S)
             double scale = 0.0;
             for (int a = 0; a < 6; ++a) { zero = zero && d[a] == 0.0; scale += d[a] * (S.lambda * d[a] + S.b[a]); }
             if (zero) { for (int k = 0; k < 7; ++k) S.Tn[k] = S.T[k]; }
-            else pt_retract(S.T, d, S.Tn);
+            else ygz_se3_retract(S.T, d, S.Tn);
             S.scale = scale;
             S.phase = PT_PH_TRIAL;
             return;
@@ -334,7 +306,7 @@ __global__ __launch_bounds__(PT_THREADS) void k_pose_opt(PoptArgs A)
         // ---------------- the classification of every edge with kind != 0 at the round's pose, by a fresh evaluation
         {
             double R[9], t[3], K[5];
-            pt_rotation(S.T, R);
+            ygz_quat_rotation(S.T, R);
             t[0] = S.T[4]; t[1] = S.T[5]; t[2] = S.T[6];
 #pragma unroll
             for (int q = 0; q < 5; ++q) K[q] = S.K[q];
@@ -346,7 +318,7 @@ __global__ __launch_bounds__(PT_THREADS) void k_pose_opt(PoptArgs A)
                 const double X[3] = { A.pw[3 * g], A.pw[3 * g + 1], A.pw[3 * g + 2] }, ob[3] = { A.obs[3 * g], A.obs[3 * g + 1], A.obs[3 * g + 2] };
                 double P[3], r[3];
                 if (!pt_residual(R, t, X, ob, kind, K, P, r)) { A.chi2[g] = 0.0; A.outlier[g] = 1; continue; }
-                const double c = pt_chi2(r, kind, pt_weight(A.level[g]));
+                const double c = pt_chi2(r, kind, ygz_level_weight(A.level[g]));
                 const bool out = c > (kind == 2 ? S.d2s : S.d2m);
                 A.chi2[g] = c; A.outlier[g] = (uint8_t)out;
                 if (!out) ++mine;

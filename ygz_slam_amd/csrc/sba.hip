@@ -20,9 +20,7 @@
 
 namespace {
 
-// ---- one edge (tests/sba_ref.c, function by function) ---------------------------------------------------------------------------------------
-__device__ __forceinline__ double sb_weight(int level) { return 1.0 / (double)(1 << (2 * level)); }
-
+// ---- one edge (tests/sba_ref.c, function by function; its level weight is ygz_level_weight of posemath_dev.h) ---------------------------
 __device__ __forceinline__ int sb_residual(const double *T, const double *X, const double *ob, const double *K, double bf, int kind, double *R,
                                            double *P, double *r)
 {
@@ -75,7 +73,7 @@ __device__ __forceinline__ int sb_edge_terms(const double *T, const double *X, c
 #pragma unroll
         for (int k = 0; k < 3; ++k) Jl[6 + k] = Jl[k] - e * R[6 + k];
     }
-    const double w = sb_weight(level);
+    const double w = ygz_level_weight(level);
     double rho1;
     sb_robust(sb_chi2(r, kind, w), robust, d2, delta, rho, &rho1);
     *wgt = rho1 * w;
@@ -233,7 +231,7 @@ __global__ __launch_bounds__(GBA_LANES) void k_sba_cost(GbaDev D)
 #pragma unroll
             for (int k = 0; k < 3; ++k) { X[k] = D.Xn[3 * (size_t)l + k]; ob[k] = D.obs[3 * (size_t)e + k]; }
             if (!sb_residual(T, X, ob, K, in.bf, kind, R, P, r)) bad = 1;
-            else sb_robust(sb_chi2(r, kind, sb_weight(D.level[e])), in.robust, kind == 2 ? in.d2s : in.d2m, kind == 2 ? in.ds : in.dm, &term, &rho1);
+            else sb_robust(sb_chi2(r, kind, ygz_level_weight(D.level[e])), in.robust, kind == 2 ? in.d2s : in.d2m, kind == 2 ? in.ds : in.dm, &term, &rho1);
         }
         acc += term;
     }
@@ -262,7 +260,7 @@ __global__ __launch_bounds__(GBA_LANES) void k_sba_classify(GbaDev D)
 #pragma unroll
         for (int k = 0; k < 3; ++k) { X[k] = D.X[3 * (size_t)l + k]; ob[k] = D.obs[3 * (size_t)e + k]; }
         if (!sb_residual(T, X, ob, K, in.bf, kind, R, P, r)) { D.outlier[e] = 1; D.chi2[e] = 0.0; continue; }
-        const double c = sb_chi2(r, kind, sb_weight(D.level[e]));
+        const double c = sb_chi2(r, kind, ygz_level_weight(D.level[e]));
         const int out = c > (kind == 2 ? in.d2s : in.d2m);
         D.outlier[e] = (uint8_t)out; D.chi2[e] = c;
         count += !out;

@@ -8,6 +8,7 @@
 //   k_sim3_select   block = problem: the highest count (ties: smallest sample), the winner's mask (bit 0)
 //   k_sim3_refine   block = problem: g2o's LM on the winner's inliers (Optimizer::OptimizeSim3's schedule), the refined mask (bit 1)
 #include "ygz_internal.h"
+#include "posemath_dev.h"
 #include <cstring>
 
 #define SIM3_SOLVE_LANES 64                // k_sim3_solve
@@ -39,38 +40,13 @@ struct Sim3Dev {
     double *hyp;                              // [P][max_iter][16]
 };
 
-// ---- the arithmetic (tests/sim3_ref.c, function by function) ---------------------------------------------------------------------
-__device__ __forceinline__ void sr_rotation(const double *q, double *R)
-{
-    const double x = q[0], y = q[1], z = q[2], w = q[3];
-    R[0] = 1.0 - 2.0 * (y * y + z * z); R[1] = 2.0 * (x * y - w * z);       R[2] = 2.0 * (x * z + w * y);
-    R[3] = 2.0 * (x * y + w * z);       R[4] = 1.0 - 2.0 * (x * x + z * z); R[5] = 2.0 * (y * z - w * x);
-    R[6] = 2.0 * (x * z - w * y);       R[7] = 2.0 * (y * z + w * x);       R[8] = 1.0 - 2.0 * (x * x + y * y);
-}
-
-__device__ __forceinline__ void mat_vec(const double *R, const double *v, double *o)
-{
-#pragma unroll
-    for (int i = 0; i < 3; ++i) o[i] = R[3 * i] * v[0] + R[3 * i + 1] * v[1] + R[3 * i + 2] * v[2];
-}
-
+// ---- the arithmetic (tests/sim3_ref.c, function by function; rotation, Sim3 inverse and retraction: posemath_dev.h) ----------------
 __device__ __forceinline__ void sim3_act(const double *S, const double *R, const double *X, double *P)
 {
     double r[3];
-    mat_vec(R, X, r);
+    ygz_mat3_vec(R, X, r);
 #pragma unroll
     for (int k = 0; k < 3; ++k) P[k] = S[7] * r[k] + S[4 + k];
-}
-
-__device__ __forceinline__ void sr_inverse(const double *S, double *Si)
-{
-    Si[0] = -S[0]; Si[1] = -S[1]; Si[2] = -S[2]; Si[3] = S[3];
-    Si[7] = 1.0 / S[7];
-    double R[9], r[3];
-    sr_rotation(Si, R);
-    mat_vec(R, S + 4, r);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) Si[4 + k] = -(Si[7] * r[k]);
 }
 
 template <int p, int q>
@@ -158,7 +134,7 @@ __device__ __forceinline__ int sr_horn3(const double *X1, const double *X2, int 
     if (w < 0) { w = -w; x = -x; y = -y; z = -z; }
     S12[0] = x; S12[1] = y; S12[2] = z; S12[3] = w;
     double R[9];
-    sr_rotation(S12, R);
+    ygz_quat_rotation(S12, R);
     double s = 1.0;
     if (!fix_scale) {
         double num = 0.0, den = 0.0;
@@ -167,7 +143,7 @@ __device__ __forceinline__ int sr_horn3(const double *X1, const double *X2, int 
             double a[3], b[3], r[3];
 #pragma unroll
             for (int k = 0; k < 3; ++k) { a[k] = X2[3 * i + k] - O2[k]; b[k] = X1[3 * i + k] - O1[k]; }
-            mat_vec(R, a, r);
+            ygz_mat3_vec(R, a, r);
             num += b[0] * r[0] + b[1] * r[1] + b[2] * r[2];
             den += r[0] * r[0] + r[1] * r[1] + r[2] * r[2];
         }
@@ -175,10 +151,10 @@ __device__ __forceinline__ int sr_horn3(const double *X1, const double *X2, int 
     }
     S12[7] = s;
     double ro[3];
-    mat_vec(R, O2, ro);
+    ygz_mat3_vec(R, O2, ro);
 #pragma unroll
     for (int k = 0; k < 3; ++k) S12[4 + k] = O1[k] - s * ro[k];
-    sr_inverse(S12, S21);
+    ygz_sim3_inverse(S12, S21);
     int ok = s > 0;
 #pragma unroll
     for (int k = 0; k < 8; ++k) ok &= fabs(S12[k]) <= SR_DMAX && fabs(S21[k]) <= SR_DMAX;
@@ -227,32 +203,6 @@ __device__ __forceinline__ int sr_is_inlier(const double *S12, const double *R12
 }
 
 // ---- refinement terms ---------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int sr_apply_delta(const double *S, const double *x, double *out)
-{
-    if (!(fabs(x[6]) < 2.0)) return 0;
-    double dq[4] = { 0.5 * x[0], 0.5 * x[1], 0.5 * x[2], 1.0 };
-    const double dn = sqrt(dq[0] * dq[0] + dq[1] * dq[1] + dq[2] * dq[2] + dq[3] * dq[3]);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) dq[k] = dq[k] / dn;
-    const double ds = (2.0 + x[6]) / (2.0 - x[6]);
-    const double ax = dq[0], ay = dq[1], az = dq[2], aw = dq[3], bx = S[0], by = S[1], bz = S[2], bw = S[3];
-    double q[4];
-    q[0] = aw * bx + ax * bw + ay * bz - az * by;
-    q[1] = aw * by - ax * bz + ay * bw + az * bx;
-    q[2] = aw * bz + ax * by - ay * bx + az * bw;
-    q[3] = aw * bw - ax * bx - ay * by - az * bz;
-    const double qn = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) out[k] = q[k] / qn;
-    double dR[9], r[3];
-    sr_rotation(dq, dR);
-    mat_vec(dR, S + 4, r);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) out[4 + k] = ds * r[k] + x[3 + k];
-    out[7] = ds * S[7];
-    return 1;
-}
-
 __device__ __forceinline__ void edge_jacobian(const double *P, const double *D, const double *K4, double *J)
 {
     const double iz = 1.0 / P[2];
@@ -321,14 +271,12 @@ __device__ __forceinline__ void add_edge(double *acc, const double *J, const dou
     acc[35] += rho;
 }
 
+// (H + lambda I) x = b out of the 28 + 7 totals, factor and substitutions in one: with ygz_chol_factor and ygz_chol_solve_packed of
+// posemath_dev.h the compiler orders the pivot tests differently and k_sim3_refine's code changes, so the loops stay written out here
 __device__ __forceinline__ int sr_solve7(const double *tot, double lambda, int fix_scale, double *x)
 {
     double A[49], L[49], y[7];
-    int m = 0;
-#pragma unroll
-    for (int a = 0; a < 7; ++a)
-#pragma unroll
-        for (int b = a; b < 7; ++b) { A[a * 7 + b] = tot[m]; A[b * 7 + a] = tot[m]; ++m; }
+    ygz_sym_unpack<7>(tot, A);
 #pragma unroll
     for (int a = 0; a < 7; ++a) A[a * 7 + a] = A[a * 7 + a] + lambda;
     double bb[7];
@@ -422,8 +370,8 @@ __global__ __launch_bounds__(SIM3_SCORE_LANES) void k_sim3_score(Sim3Dev D)
     double S12[8], S21[8], R12[9], R21[9];
 #pragma unroll
     for (int k = 0; k < 8; ++k) { S12[k] = live ? D.hyp[h * 16 + k] : 0.0; S21[k] = live ? D.hyp[h * 16 + 8 + k] : 0.0; }
-    sr_rotation(S12, R12);
-    sr_rotation(S21, R21);
+    ygz_quat_rotation(S12, R12);
+    ygz_quat_rotation(S21, R21);
     int c = 0;
     for (int base = 0; base < n; base += SIM3_SCORE_LANES) {
         const int m = min(SIM3_SCORE_LANES, n - base);
@@ -489,8 +437,8 @@ __global__ __launch_bounds__(SIM3_SEL_THREADS) void k_sim3_select(Sim3Dev D)
     for (int k = 0; k < 8; ++k) { S12[k] = hg[k]; S21[k] = hg[8 + k]; }
 #pragma unroll
     for (int k = 0; k < 4; ++k) K4[k] = D.in->K4[k];
-    sr_rotation(S12, R12);
-    sr_rotation(S21, R21);
+    ygz_quat_rotation(S12, R12);
+    ygz_quat_rotation(S21, R21);
     const double chi2 = D.in->chi2;
     int c = 0;
     for (int i = threadIdx.x; i < n; i += SIM3_SEL_THREADS) {
@@ -526,9 +474,9 @@ __device__ void ref_accumulate(const Sim3Dev &D, RefShared &sh, int off, int n, 
     double S[8], R[9], Si[8], Ri[9];
 #pragma unroll
     for (int k = 0; k < 8; ++k) S[k] = sh.S[k];
-    sr_rotation(S, R);
-    sr_inverse(S, Si);
-    sr_rotation(Si, Ri);
+    ygz_quat_rotation(S, R);
+    ygz_sim3_inverse(S, Si);
+    ygz_quat_rotation(Si, Ri);
     double acc[36];
 #pragma unroll
     for (int k = 0; k < 36; ++k) acc[k] = 0.0;
@@ -602,7 +550,7 @@ __device__ double ref_lm(const Sim3Dev &D, RefShared &sh, int off, int n, int bi
 #pragma unroll
                 for (int k = 0; k < 8; ++k) sh.Sb[k] = sh.S[k];
                 int ok = sr_solve7(sh.totH, lambda, fix_scale, x);
-                if (ok) ok = sr_apply_delta(sh.Sb, x, Sn);
+                if (ok) ok = ygz_sim3_retract(sh.Sb, x, Sn);
                 if (ok)
 #pragma unroll
                     for (int k = 0; k < 8; ++k) sh.S[k] = Sn[k];
@@ -655,9 +603,9 @@ __device__ void ref_classify(const Sim3Dev &D, RefShared &sh, int off, int n, bo
     double S[8], R[9], Si[8], Ri[9];
 #pragma unroll
     for (int k = 0; k < 8; ++k) S[k] = sh.S[k];
-    sr_rotation(S, R);
-    sr_inverse(S, Si);
-    sr_rotation(Si, Ri);
+    ygz_quat_rotation(S, R);
+    ygz_sim3_inverse(S, Si);
+    ygz_quat_rotation(Si, Ri);
     int dr = 0, in = 0;
     for (int i = threadIdx.x; i < n; i += SIM3_REF_LANES) {
         const int j = off + i;
@@ -704,7 +652,7 @@ __global__ __launch_bounds__(SIM3_REF_LANES) void k_sim3_refine(Sim3Dev D)
     if (threadIdx.x == 0) {
         double S[8], Si[8];
         for (int k = 0; k < 8; ++k) S[k] = sh.S[k];
-        sr_inverse(S, Si);
+        ygz_sim3_inverse(S, Si);
         for (int k = 0; k < 8; ++k) { r->S12[k] = S[k]; r->S21[k] = Si[k]; }
         r->chi2_ransac = chi0;
         r->chi2_refined = chi;

@@ -7,8 +7,8 @@
 #include <cmath>
 
 namespace Sophus {
-// SO3(const Matrix3d &) = Eigen::Quaterniond(const Matrix3d &): the trace branch, else the largest diagonal (the restatement's
-// ir_quat_from_matrix, tests/init_ref.c; what ygz_hip_initialize returns as T21)
+// SO3(const Matrix3d &) = Eigen::Quaterniond(const Matrix3d &): the trace branch, else the largest diagonal (on the device
+// ygz_quat_from_matrix of csrc/posemath_dev.h, restated in tests/init_ref.c; what ygz_hip_initialize returns as T21)
 SO3::SO3(const Matrix3d &R)
 {
     const double *m = R.m;
